@@ -2,6 +2,7 @@
 """bench.py -- novel-view frames/sec @256x256 (reproject + AR outpaint) on MI355X.
 
     python bench.py --gpus N --steps K --warmup W          (N>1: launched by torch.distributed.run)
+    python bench.py ... --dump-outputs DIR                 (also saves what the last timed step computed: dump_outputs)
 
 One STEP = one pass of the hot path over one batch of V independent novel views per GPU.  Default V = 128 = BASELINE.json's
 config C5 -- Matterport-shaped 256x256 inputs, 8 source images x 16 novel views each -- which fits one GPU, so at N = 1
@@ -924,6 +925,33 @@ def cpu_baseline(host, out, V, budget_s=20.0):
             "host_cpus": os.cpu_count()}
 
 
+DUMP_BYTES = 64_000_000    # --dump-outputs: at most this much in all
+
+
+def dump_outputs(path, out):
+    """--dump-outputs DIR: what the timed path handed back for its last step, as DIR/<name>.npy in float32 -- the completed 32x32
+    code grids (`codes`), the reprojected views' features (`gen_fs`) and background masks (`background_mask`), and on the
+    multi-rank path what the gathers delivered (`all_codes`, `all_features_u8`).  The inputs are seeded, so two runs with the same
+    arguments see the same ones.  Code grids whole; the per-view images, when all of them would pass DUMP_BYTES, for a fixed,
+    seeded sample of views -- the same rows for every array of the same length, listed in DIR/<name>_rows.npy."""
+    whole = {"codes": out["codes"]}
+    rows = {"gen_fs": out["gen_fs"], "background_mask": out["background_mask"]}
+    if "all_codes" in out:
+        whole["all_codes"] = out["all_codes"]
+        rows["all_features_u8"] = out["all_features_u8"]
+    fixed = sum(t.numel() * 4 for t in whole.values()) + sum(t.shape[0] * 8 for t in rows.values()) + 128 * (len(whole) + 2 * len(rows))
+    frac = min(1.0, max(0.0, (DUMP_BYTES - fixed) / sum(t.numel() * 4 for t in rows.values())))    # (128 bytes: an .npy header)
+    os.makedirs(path, exist_ok=True)
+    for name, t in whole.items():
+        np.save(os.path.join(path, f"{name}.npy"), t.float().cpu().numpy())
+    for name, t in rows.items():
+        n = t.shape[0]
+        k = int(n * frac)
+        sel = np.arange(n) if k >= n else np.sort(np.random.RandomState(0).choice(n, k, replace=False))
+        np.save(os.path.join(path, f"{name}.npy"), t[torch.from_numpy(sel).to(t.device)].float().cpu().numpy())
+        np.save(os.path.join(path, f"{name}_rows.npy"), sel.astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -942,7 +970,11 @@ def main():
     ap.add_argument("--no-extra", action="store_true", help="skip the C3 single-view / C2 splat-only side measurements")
     ap.add_argument("--live-pmc", action="store_true", help="the rocprofv3 --pmc passes of this command even with --no-extra")
     ap.add_argument("--dump-gather", metavar="NPZ", help="rank 0 saves what the last step gathered from all ranks (tests)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="rank 0 saves what the last timed step handed back as DIR/<name>.npy "
+                    "(float32, at most 64 MB in all: see dump_outputs), to compare two builds output for output")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -1002,6 +1034,8 @@ def main():
 
     if rank == 0 and args.dump_gather and (world > 1 or FORCE_COLLECTIVE):
         np.savez_compressed(args.dump_gather, all_codes=out["all_codes"].cpu().numpy(), all_features_u8=out["all_features_u8"].cpu().numpy())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, out)
     if rank == 0:
         frames = V * world * args.steps   # (strong: V * world = the job's total)
         plan = out["plan"]

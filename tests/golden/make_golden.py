@@ -179,6 +179,19 @@ def gen_orders_masks(R):
     print("orders_masks.npz", len(fx))
 
 
+def gen_custom_idx(R):
+    """The reference's get_custom_order.custom_idx called directly (centre n/2, n/2) on random distance maps of 4x4 .. 32x32."""
+    fx = {}
+    rs = np.random.RandomState(77)
+    for k in range(12):
+        n = [4, 8, 16, 32][k % 4]
+        D = rs.randint(-4, 5, size=(n, n)).astype(np.int64)
+        fx[f"D_{k}"] = D.astype(np.int8)
+        fx[f"order_{k}"] = np.asarray(R["gco"].custom_idx(n, n, D.copy(), (n // 2, n // 2))).astype(np.int16)
+    np.savez_compressed(os.path.join(HERE, "custom_idx.npz"), **fx)
+    print("custom_idx.npz", len(fx))
+
+
 def gen_lmconv_layers(R):
     fx = {}
     for name, ci, co, dil, H in cases.LAYER_CASES:
@@ -581,11 +594,14 @@ def gen_scorers(R):
 if __name__ == "__main__":
     torch.set_num_threads(8)
     R = _import_reference()
-    which = sys.argv[1:] or ["projection", "orders", "layers", "blocks", "network", "ar", "vqvae", "networks", "poses", "zbuffer", "scorers"]
+    which = sys.argv[1:] or ["projection", "orders", "custom_idx", "layers", "blocks", "network", "ar", "vqvae", "networks", "poses",
+                             "zbuffer", "scorers"]
     if "projection" in which:
         gen_projection(R)
     if "orders" in which:
         gen_orders_masks(R)
+    if "custom_idx" in which:
+        gen_custom_idx(R)
     if "layers" in which:
         gen_lmconv_layers(R)
     if "blocks" in which:

@@ -76,6 +76,36 @@ def test_bench_line_with_the_counter_passes_says_what_is_executed():
             assert row["executed_flops_per_launch"] <= row["dense_flops_per_launch"] * 1.02, row      # per tile a tap is computed for all 16 items
 
 
+def test_bench_dumps_what_the_last_timed_step_computed(tmp_path):
+    """--dump-outputs: the last timed step's code grids, features and background masks as float32 .npy files (16 views: all of them,
+    well under the 64 MB cap) -- exactly what one step on the same inputs gives in a process of its own."""
+    import numpy as np
+    import torch
+    dump = tmp_path / "outputs"
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--views", "16",
+                          "--no-cpu-baseline", "--no-extra", "--dump-outputs", str(dump)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    d = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][0])
+    assert d["steps"] == 3 and d["ms_per_step"] > 0
+    names = sorted(p.name for p in dump.iterdir())
+    assert names == ["background_mask.npy", "background_mask_rows.npy", "codes.npy", "gen_fs.npy", "gen_fs_rows.npy"], names
+    assert sum(p.stat().st_size for p in dump.iterdir()) <= 64_000_000
+    got = {p.stem: np.load(p) for p in dump.iterdir()}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert np.array_equal(got["gen_fs_rows"], np.arange(16)) and np.array_equal(got["background_mask_rows"], np.arange(16))
+    sys.path.insert(0, ROOT)
+    import bench
+    dev = torch.device("cuda", 0)
+    model = bench.build_model(dev)
+    dd, _ = bench.make_inputs(0, 16, dev)
+    o = bench.run_step(model, dd, 1)
+    torch.cuda.synchronize()
+    model.outpaint2.engine(32, 32, 16).check()
+    assert np.array_equal(got["codes"], o["codes"].float().cpu().numpy())
+    assert np.array_equal(got["gen_fs"], o["gen_fs"].cpu().numpy())
+    assert np.array_equal(got["background_mask"], o["background_mask"].float().cpu().numpy())
+
+
 def _torchrun(script_args, env_extra, nproc=2, timeout=900):
     import socket
     with socket.socket() as sk:

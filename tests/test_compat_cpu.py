@@ -29,25 +29,43 @@ def test_aliases_resolve_in_a_fresh_interpreter():
     assert out.returncode == 0 and "ok" in out.stdout, out.stderr[-2000:]
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/models"), reason="needs the reference checkout (build container only)")
-def test_aliases_keep_the_reference_tree_importable():
-    """INTEGRATION.md option A: demo.py run from a reference checkout.  With the reference on sys.path the aliased modules
+def _checkout_tree(root):
+    """A stand-in for a checkout of the reference, laid out as it is: `models` and its subpackages are namespace packages (no
+    __init__.py).  The modules the aliases replace refuse to be imported; the others are empty and say where they lie."""
+    aliased = ["lmconv/model.py", "lmconv/masking.py", "lmconv/layers.py", "lmconv/sample.py", "lmconv/utils.py",
+               "lmconv/locally_masked_convolution.py", "vqvae2/vqvae.py", "projection/z_buffer_manipulator.py",
+               "layers/z_buffer_layers.py"]
+    own = ["networks/configs.py", "lmconv/average_checkpoints.py", "vqvae2/scheduler.py"]
+    for rel in aliased + own:
+        path = os.path.join(root, "models", rel)
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+        with open(path, "w") as fh:
+            fh.write("raise ImportError('the checkout\\'s own module, not the mirror')\n" if rel in aliased else "CHECKOUT = True\n")
+    return str(root)
+
+
+def test_aliases_keep_the_reference_tree_importable(tmp_path):
+    """INTEGRATION.md option A: demo.py run from a reference checkout.  With the checkout on sys.path the aliased modules
     resolve to the mirrors AND everything that is not aliased (models.networks.configs, ...) still imports from the
-    reference's own packages -- a synthesised empty parent package would hide them."""
+    checkout's own packages -- a synthesised empty parent package would hide them."""
+    tree = _checkout_tree(tmp_path / "checkout")
     code = (
-        "import sys; sys.path.insert(0, %r); sys.path.insert(0, '/root/reference')\n"
+        "import sys; sys.path.insert(0, %r); sys.path.insert(0, %r)\n"
         "import pixelsynth_amd.compat as c; c.install_reference_aliases()\n"
         "import models.networks.configs as cfg\n"
-        "assert cfg.__file__.startswith('/root/reference/'), cfg.__file__\n"
+        "assert cfg.__file__.startswith(%r) and cfg.CHECKOUT, cfg.__file__\n"
         "from models.lmconv.model import OurPixelCNN\n"
         "assert OurPixelCNN.__module__ == 'pixelsynth_amd.lmconv.model'\n"
         "import models.lmconv.masking as m\n"
         "assert m.__name__ == 'pixelsynth_amd.lmconv.masking'\n"
         "import models.vqvae2.vqvae as v\n"
         "assert v.__name__ == 'pixelsynth_amd.vqvae2.vqvae'\n"
-        "import models.lmconv.average_checkpoints\n"       # a non-aliased sibling of aliased modules
-        "print('ok')\n" % ROOT)
-    out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
+        "import models.lmconv.average_checkpoints as a\n"       # a non-aliased sibling of aliased modules
+        "assert a.CHECKOUT\n"
+        "import models.vqvae2.scheduler as s\n"
+        "assert s.CHECKOUT\n"
+        "print('ok')\n" % (ROOT, tree, tree + os.sep))
+    out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300, cwd=str(tmp_path))
     assert out.returncode == 0 and "ok" in out.stdout, out.stderr[-2000:]
 
 

@@ -1,15 +1,13 @@
 """Pin the CPU oracle against the golden vectors produced by the reference itself
-(tests/golden/make_golden.py) and against oracle/_ref (the reference's own Cython C, compiled).
+(tests/golden/make_golden.py), among them what oracle/_ref (the reference's own Cython C, compiled) computes.
 CPU only."""
-import importlib.util
 import os
 
 import numpy as np
-import pytest
 import torch
 
 import cases
-from oracle import build_oracle, c_oracle, lmconv_oracle as lo
+from oracle import c_oracle, lmconv_oracle as lo
 from pixelsynth_amd import synthetic as syn
 
 
@@ -96,21 +94,17 @@ def test_custom_idx_exact(golden_dir):
         assert len({(int(r), int(c)) for r, c in order}) == 1024  # a permutation of the grid
 
 
-def test_custom_idx_vs_ref_build():
-    """oracle/_ref = the reference's own get_custom_order.c compiled in place."""
-    so = build_oracle.build_ref()
-    if so is None or not os.path.exists(so):
-        pytest.skip("oracle/_ref not built and /root/reference absent")
-    spec = importlib.util.spec_from_file_location("get_custom_order", so)
-    gco = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(gco)
+def test_custom_idx_vs_ref_build(golden_dir):
+    """The reference's own get_custom_order.c (compiled into oracle/_ref by oracle/build_oracle.py), called directly on random
+    distance maps of 4x4 .. 32x32: its orders are stored in custom_idx.npz (tests/golden/make_golden.py custom_idx)."""
+    fx = load(golden_dir, "custom_idx.npz")
     rs = np.random.RandomState(77)
     for k in range(12):
         n = [4, 8, 16, 32][k % 4]
         D = rs.randint(-4, 5, size=(n, n)).astype(np.int64)
-        ref = np.asarray(gco.custom_idx(n, n, D.copy(), (n // 2, n // 2)))
+        assert np.array_equal(D, fx[f"D_{k}"])
         got, _ = c_oracle.custom_idx(n, n, D)
-        assert np.array_equal(got, ref.astype(np.int32))
+        assert np.array_equal(got, fx[f"order_{k}"].astype(np.int32)), k
 
 
 def test_unfolded_masks_exact(golden_dir):
