@@ -218,6 +218,8 @@ int ps_pixelcnn_forward_f32(ps_pixelcnn *h, const int32_t *codes, const float *m
  *   forced (F,L) int32 by location or NULL: teacher-forced codes (parity tests);
  *   uniforms (F,L) f32 by location or NULL: u in [0,1) for the inverse-CDF draw from
  *     softmax(logits / temperature) (sample.py:60-63; RNG streams differ from torch.multinomial);
+ *     the class drawn always has positive probability in fp32 (a class whose exp(logit / T - max)
+ *     underflows to 0 is never drawn, whatever u is);
  *   out_logits (F,L,512) f32 by location or NULL: the logits each location was decided from.
  * Exactly one of forced / uniforms must be given.
  *   first_step: order positions < first_step are not walked one by one: they must all be observed

@@ -268,7 +268,12 @@ __device__ __forceinline__ void signal_done(unsigned *counter, int lane)
 // six); 2^24 polls are seconds -- still finite, so a lost workgroup ends as an error from ps_pixelcnn_status, not as a hung GPU.
 constexpr int WAIT_SPINS = 1 << 24;
 
-// categorical draw from logits / T by inverse CDF with one uniform (sample.py:60-66); lane l holds classes 8l..8l+7
+// categorical draw from logits / T by inverse CDF with one uniform u in [0, 1) (sample.py:60-66); lane l holds classes 8l..8l+7.
+// The class drawn is the smallest one with e > 0 whose running sum exceeds u * total; where rounding leaves none (u within a
+// few ulps of 1), the largest one with e > 0.  So a class whose expf underflowed to 0 is never drawn.  (Counting the classes
+// whose sum is <= u * total, as this draw did before, returned such classes: the running sums are rounded apart from total,
+// which counted the zero classes after the last positive one at u near 1, and a lane's start, incl - ls, can lose the sums
+// before it.  Where the running sums are monotone and the class they pick is positive, both rules give the same class.)
 __device__ __forceinline__ int draw_code(const float (&lg)[8], float temperature, float u, int lane)
 {
     float x[8], m = -INFINITY;
@@ -286,11 +291,20 @@ __device__ __forceinline__ int draw_code(const float (&lg)[8], float temperature
     const float total = __shfl(incl, 63, 64);
     const float target = u * total;
     float run = incl - ls;
-    int cnt = 0;
+    // one min-reduction decides both cases: key = the lane's first class with e > 0 whose sum exceeds target; else
+    // 2 NCLS - 1 - its last class with e > 0 (>= NCLS, smaller for a later class); else 2 NCLS (no class with e > 0)
+    int key = 2 * NCLS, last = -1;
 #pragma unroll
-    for (int k = 0; k < 8; ++k) { run += e[k]; cnt += run <= target ? 1 : 0; }  // classes whose cdf <= target
-    for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off, 64);
-    return min(cnt, NCLS - 1);
+    for (int k = 0; k < 8; ++k) {
+        run += e[k];
+        if (e[k] > 0.0f) {
+            last = lane * 8 + k;
+            if (run > target && key == 2 * NCLS) key = last;
+        }
+    }
+    if (key == 2 * NCLS && last >= 0) key = 2 * NCLS - 1 - last;
+    for (int off = 32; off > 0; off >>= 1) key = min(key, __shfl_xor(key, off, 64));
+    return key < NCLS ? key : max(2 * NCLS - 1 - key, 0);
 }
 
 // Workgroup barrier that only drains LDS traffic.  __syncthreads() also waits for every outstanding

@@ -418,6 +418,11 @@ def test_ar_fused_sampling_inverse_cdf_and_determinism():
             if not (lo_ - 1e-5 <= u[b, q] <= hi_ + 1e-5):
                 bad += 1
     assert bad == 0
+    # ... and, with no slack, a class of positive fp32 softmax probability (a class of probability 0 has a bin of width 0,
+    # which the slack above would accept)
+    for b in range(F_):
+        for q in np.nonzero(reg[b])[0]:
+            assert lo.draw_distribution(logits[b, q], 0.7)[1][codes[b, q]], (b, q)
     # batch independence: image 1 alone gives the same codes
     eng1 = make_net(3).engine(32, 32, 1)
     c = tt(codes0[1:2].copy())
@@ -430,6 +435,157 @@ def test_ar_fused_sampling_inverse_cdf_and_determinism():
     for b in range(F_):
         walked = order_loc[b][first:]
         assert np.array_equal(full[b][walked], logits[b][walked])
+
+
+# ---- the fused categorical draw (csrc/lmconv_device.h: draw_code) at its edges, through the product column kernels ----
+# nin_out's weight_g = 0 makes every location's logits exactly nin_out's bias, so every sampled location draws from ONE chosen
+# distribution with a uniform of its own.  The walk is the last 242 order positions, two lattices of spacing 3: (3a, 3b), then
+# (3a + 1, 3b + 1).  No two positions of one lattice are tap neighbours (the taps reach 2), so each lattice is one wavefront level
+# of 121 columns per frame, and at 32 / 40 frames every launch of the schedule takes the throughput form.
+DRAW_WALK = 242
+DRAW_TEMPS = (0.05, 0.7, 1.0, 5.0)
+DRAW_ZERO = -6000.0     # at least 1200 below the max after / T at every temperature here: exp is 0 in fp32 and in fp64
+DRAW_EDGE = 2.0 ** -20  # bin edges the fp32 sums of the kernel may place differently from the fp64 reference
+
+
+def _draw_order():
+    lat1 = [3 * a * 32 + 3 * b for a in range(11) for b in range(11)]
+    lat2 = [(3 * a + 1) * 32 + 3 * b + 1 for a in range(11) for b in range(11)]
+    last = set(lat1 + lat2)
+    return np.array([q for q in range(1024) if q not in last] + lat1 + lat2, np.int32)
+
+
+def _draw_families():
+    """name -> ((512,) fp32 logits, temperatures).  Every class is within 1.5 of the max (30 after / T at T = 0.05) or at
+    DRAW_ZERO, so "probability 0" means the same in fp32 and fp64 -- but for the natural logits, whose tail underflows through
+    the temperature alone.  The draw's lane l holds classes 8l .. 8l + 7."""
+    rs = np.random.RandomState(17)
+    pos = lambda: rs.uniform(-1.5, 0.0, 512).astype(np.float32)
+    fam = {}
+    for j in (0, 7, 8, 255, 263, 504, 510):               # zero classes after the last positive one
+        lg = pos()
+        lg[j], lg[j + 1:] = 0.0, DRAW_ZERO
+        fam[f"zeros_after_{j}"] = lg
+    lg = pos()
+    lg[:263], lg[300] = DRAW_ZERO, 0.0                    # zero classes before the first positive one
+    fam["zeros_before_263"] = lg
+    lg = pos()
+    lg[[c for l in range(1, 64) for c in (8 * l - 1, 8 * l)]] = DRAW_ZERO   # pairs of zero classes across every lane boundary
+    lg[rs.choice(512, 40, replace=False)] = DRAW_ZERO
+    lg[[0, 511]], lg[200] = -0.5, 0.0
+    fam["zeros_across_lanes"] = lg
+    lg = np.full(512, DRAW_ZERO, np.float32)
+    lg[300] = 0.0
+    fam["one_positive"] = lg
+    lg = pos()
+    lg[[100, 401]] = 0.0
+    fam["tied_max"] = lg
+    fam["all_equal"] = np.zeros(512, np.float32)
+    fam = {k: (v, DRAW_TEMPS) for k, v in fam.items()}
+    fam["natural_randn_x3"] = ((rs.randn(512) * 3).astype(np.float32), (0.05,))
+    return fam
+
+
+def _draw_edge_uniforms(p):
+    """The fixed edge uniforms, and fp32(cdf) at the upper edge of several positive classes (the first, the last two, some
+    between) with their fp32 neighbours.  The last class's upper edge is 1, outside [0, 1): 1 - 2^-24 stands in for it."""
+    fixed = [0.0, 2.0 ** -24, 0.5, 1 - 3 * 2.0 ** -24, 1 - 2.0 ** -23, 1 - 2.0 ** -24]
+    cdf = np.cumsum(p) / p.sum()
+    posk = np.nonzero(p > 0)[0]
+    ks = np.unique(np.concatenate([posk[np.linspace(0, len(posk) - 1, 6).round().astype(int)], posk[-2:]]))
+    at = cdf[ks].astype(np.float32)
+    near = np.concatenate([at, np.nextafter(at, np.float32(0)), np.nextafter(at, np.float32(1))])
+    return np.unique(np.concatenate([np.float32(fixed), near[near < 1]]).astype(np.float32))
+
+
+def _check_draws(tag, drawn, u, logits, T, fails, grid=False):
+    """Every draw: a class of positive probability (exactly), and the fp64 inverse CDF at u -- or, for u within DRAW_EDGE of
+    a bin edge, the positive class across it.  A quantile grid: every class drawn n p_k +- 2 times."""
+    p, pos32 = lo.draw_distribution(logits, T)
+    ref, accepted = lo.inverse_cdf(p, u, edge=DRAW_EDGE)
+    zero = np.nonzero(~pos32[drawn])[0]
+    off = np.nonzero(~accepted[np.arange(len(u)), drawn])[0]
+    for what, idx in (("drew a class of probability 0", zero), ("missed the inverse CDF", off)):
+        if len(idx):
+            i = idx[0]
+            fails.append(f"{tag}: {len(idx)} of {len(u)} draws {what}, e.g. u = {float(u[i])!r} -> {drawn[i]} "
+                         f"(p {p[drawn[i]]:.3g}; inverse CDF {ref[i]})")
+    if grid:
+        dev = np.abs(np.bincount(drawn, minlength=512) - len(u) * p)
+        if dev.max() > 2:
+            fails.append(f"{tag}: quantile grid of {len(u)}: class {dev.argmax()} drawn {dev.max():.1f} times off n p")
+
+
+@pytest.mark.parametrize("form,F_", [("walk", 3), ("waves", 8), ("waves", 32), ("waves", 40), ("prefix_columns", 32)])
+def test_ar_fused_draw_edges_vs_fp64_inverse_cdf(form, F_):
+    """The fused draw of both column forms -- k_column (3 frames walked position by position, 8 frames on latency-form waves)
+    and k_column_tp (32 and 40 frames) -- and of the split prefix / columns calls outpaint_pipelined makes, for chosen
+    distributions: zero classes after the last positive class (at lane boundaries), before the first, across lane boundaries;
+    one positive class; a tied max; all classes equal; natural logits whose tail underflows at T = 0.05.  Each at edge
+    uniforms (0, 2^-24, 1/2, 1 - 2^-24 ..., the fp32 bin edges) and, from 24 frames on, on a quantile grid of n >= 4096."""
+    from pixelsynth_amd.lmconv.model import TP_MIN_FRAMES, wavefronts
+    net = make_net(3)
+    with torch.no_grad():
+        net.nin_out.lin_a.weight_g.zero_()
+    order = _draw_order()
+    first = 1024 - DRAW_WALK
+    o2 = np.stack(np.divmod(order, 32), 1)
+    ms = [tt(np.concatenate([c_oracle.unfolded_masks(o2, 32, 32, 3, dil, typ)] * F_)) for dil, typ in ((1, "A"), (1, "B"), (2, "B"))]
+    order_loc = np.stack([order] * F_)
+    sampled = np.sort(order[first:])
+    reg = np.zeros((F_, 1024), np.uint8)
+    reg[:, sampled] = 1
+    codes0 = syn.codes(21, F_).reshape(F_, 1024).astype(np.int32)
+    waves = None if form == "walk" else wavefronts(order_loc, 32, 32, first, DEV)
+    tp = F_ >= TP_MIN_FRAMES
+    n = F_ * DRAW_WALK
+    assert (n >= 4096) == tp
+    rs = np.random.RandomState(F_)
+    fails = []
+    for name, (logits, temps) in _draw_families().items():
+        with torch.no_grad():
+            net.nin_out.lin_a.bias.copy_(torch.from_numpy(logits))
+        eng = net.engine(32, 32, F_)                       # (rebuilt: the parameters changed)
+        if waves is not None and tp:                       # every launch of the schedule in the throughput form
+            assert (np.diff(waves[1]) >= eng.get_tuning("tp_min_cols")).all()
+        bias = tt(logits)
+        for T in temps:
+            edges = _draw_edge_uniforms(lo.draw_distribution(logits, T)[0])
+            u_edge = np.minimum(rs.rand(n), 1 - 2.0 ** -24).astype(np.float32)
+            u_edge[::2] = np.resize(edges, len(u_edge[::2]))
+            for kind, ud in (("edges", u_edge), ("grid", ((np.arange(n) + 0.5) / n).astype(np.float32))):
+                if kind == "grid" and not tp:
+                    continue
+                u = np.full((F_, 1024), 0.5, np.float32)
+                u[:, sampled] = ud.reshape(F_, DRAW_WALK)
+                c = tt(codes0.copy())
+                n0 = eng.launch_counts()
+                if form == "prefix_columns":
+                    eng.ar_prefix(c, tt(order_loc), tt(reg), *ms, first)
+                    eng.ar_columns(c, tt(order_loc), tt(reg), *ms, waves, temperature=T, uniforms=tt(u), first_step=first)
+                    out = None
+                else:
+                    out = eng.ar_run(c, tt(order_loc), tt(reg), *ms, temperature=T, uniforms=tt(u), first_step=first,
+                                     want_logits=True, waves=waves)
+                eng.check()
+                n1 = eng.launch_counts()
+                lat = sum(n1[k] - n0[k] for k in ("k_column", "k_column_la"))
+                thr = sum(n1[k] - n0[k] for k in ("k_column_tp", "k_column_tp8"))
+                assert (lat == 0 and thr > 0) if tp else (lat > 0 and thr == 0), (form, F_, n1)
+                # the harness itself: every sampled location was decided from exactly the chosen logits
+                if out is not None:
+                    assert torch.equal(out[:, sampled], bias.expand(F_, DRAW_WALK, 512)), (form, F_, name)
+                codes = c.cpu().numpy()
+                assert np.array_equal(codes[reg == 0], codes0[reg == 0])
+                drawn = codes[:, sampled].reshape(-1)
+                assert ((drawn >= 0) & (drawn < 512)).all()
+                _check_draws(f"{form} {F_} frames, {name}, T {T}, {kind}", drawn, ud, logits, T, fails, grid=kind == "grid")
+                if name == "one_positive":
+                    assert (drawn == 300).all()
+                if name == "all_equal":                    # the sums are exact: u -> floor(512 u)
+                    away = np.abs(ud * 512 - np.round(ud * 512)) > 512 * DRAW_EDGE
+                    assert np.array_equal(drawn[away], np.floor(ud[away].astype(np.float64) * 512).astype(np.int64))
+    assert not fails, "\n".join(fails)
 
 
 def test_sample_dropin_modes_agree():
