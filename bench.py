@@ -3,6 +3,7 @@
 
     python bench.py --gpus N --steps K --warmup W          (N>1: launched by torch.distributed.run)
     python bench.py ... --dump-outputs DIR                 (also saves what the last timed step computed: dump_outputs)
+    python bench.py ... --full                             (also the side measurements: roofline, cpu_baseline, other configs)
 
 One STEP = one pass of the hot path over one batch of V independent novel views per GPU.  Default V = 128 = BASELINE.json's
 config C5 -- Matterport-shaped 256x256 inputs, 8 source images x 16 novel views each -- which fits one GPU, so at N = 1
@@ -10,10 +11,12 @@ the step IS C5; under `torch.distributed.run` every rank renders its own 8 x 16 
 reprojection + soft z-buffer splat, generation order + masks (a7-a9), autoregressive outpainting of
 the 32x32 VQ code grid (a13).  Inputs are synthetic and already resident in HBM when the timed region starts; weights
 are random-init with the reference's shapes.  The VQ-VAE / depth / refinement networks around the path are next-row
-components, timed separately under `other_single_gpu_configs`; the codes of the reprojected view are
+components, timed separately under `other_single_gpu_configs` (--full); the codes of the reprojected view are
 synthetic.  The only collective is the RCCL all_gather of the finished frames (no data-path exchange).
 
-Prints ONE JSON line (rank 0) with the contract fields plus `roofline` and `cpu_baseline`.
+Prints ONE JSON line (rank 0) with the contract fields.  A plain run does only what they need: set up, warm up, time the steps,
+dump (--dump-outputs) and print.  With --full a single-rank run goes on after the timed region and adds what takes runs of its
+own: `roofline` (column launch, per-kernel table, the rocprofv3 --pmc passes), `cpu_baseline` and `other_single_gpu_configs`.
 """
 import argparse
 import gc
@@ -965,16 +968,20 @@ def main():
     ap.add_argument("--frames", type=int, default=64, help="--trajectory circle: frames of the circle in total")
     ap.add_argument("--cameras", choices=["mp3d", "demo"], default=None, help="Matterport-shaped (C5, default) or demo / RealEstate10K-shaped inputs (default for the circle)")
     ap.add_argument("--depth", choices=["smooth", "uniform"], default="smooth")
+    ap.add_argument("--full", action="store_true", help="after the timed region, the side measurements (one rank only): roofline and per-kernel "
+                    "figures, the CPU baseline, the other single-GPU configurations; the four options below narrow them down")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-live-pmc", action="store_true", help="roofline.traffic from the committed PMC record only (no rocprofv3 --pmc passes)")
     ap.add_argument("--no-extra", action="store_true", help="skip the C3 single-view / C2 splat-only side measurements")
-    ap.add_argument("--live-pmc", action="store_true", help="the rocprofv3 --pmc passes of this command even with --no-extra")
+    ap.add_argument("--live-pmc", action="store_true", help="the rocprofv3 --pmc passes of this command even with --no-extra (needs --full)")
     ap.add_argument("--dump-gather", metavar="NPZ", help="rank 0 saves what the last step gathered from all ranks (tests)")
     ap.add_argument("--dump-outputs", metavar="DIR", help="rank 0 saves what the last timed step handed back as DIR/<name>.npy "
                     "(float32, at most 64 MB in all: see dump_outputs), to compare two builds output for output")
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if args.live_pmc and not args.full:
+        ap.error("--live-pmc is one of the side measurements of --full")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -1076,7 +1083,7 @@ def main():
                                  "forced_on_one_rank": bool(FORCE_COLLECTIVE and world == 1)}
         if world == 1 and os.environ.get("PS_BENCH_PMC_CHILD") == "1":
             pass      # (a counter pass of live_pmc_traffic: only the timed steps' kernels are wanted in it)
-        elif world == 1:
+        elif world == 1 and args.full:
             try:
                 res["roofline"] = measure_roofline(model, d, out, V, live_pmc=(not args.no_extra or args.live_pmc) and not args.no_live_pmc)
                 # the step as a whole against the same peak: every view is ONE whole-grid forward's worth of matrix work (SURVEY 8d:

@@ -11,7 +11,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_bench_prints_one_json_line_with_the_contract_fields():
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--full",
                           "--no-cpu-baseline", "--no-extra"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -50,14 +50,29 @@ def test_bench_prints_one_json_line_with_the_contract_fields():
     assert "executed_frac" not in r["step"]          # (no counter pass in this short run: nothing is made up)
 
 
+def test_plain_bench_line_is_the_headline_only():
+    """Without --full: the contract fields of the timed steps, and none of the side measurements that take runs of their own."""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1"],
+                         capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype", "config"):
+        assert k in d, k
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["unit"] == "frames/s" and d["dtype"] == "f32"
+    assert abs(d["value"] - d["config"]["views_per_gpu"] * 1e3 / d["ms_per_step"]) / d["value"] < 1e-3
+    assert not {"roofline", "cpu_baseline", "other_single_gpu_configs"} & set(d), sorted(d)
+
+
 def test_bench_line_with_the_counter_passes_says_what_is_executed():
-    """With the run's own rocprofv3 --pmc passes (what the default `python bench.py` does): executed MFMA flops per kernel, both
+    """With the run's own rocprofv3 --pmc passes (what `python bench.py --full` does): executed MFMA flops per kernel, both
     fractions, and the step's executed fraction beside the dense-equivalent one -- executed <= dense everywhere (closed taps and the
     prefix cone are skipped work)."""
     import shutil
     if not (shutil.which("rocprofv3") or os.path.exists("/opt/rocm/bin/rocprofv3")):
         pytest.skip("rocprofv3 not installed")
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2", "--full",
                           "--no-cpu-baseline", "--no-extra", "--live-pmc"], capture_output=True, text=True, timeout=1500, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     d = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][0])

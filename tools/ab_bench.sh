@@ -1,13 +1,14 @@
 #!/bin/bash
 # A/B of library builds / tuning values on one box: tools/ab_bench.sh <rounds> <steps> name=ENV1=v+ENV2=v ... ; alternating runs of the
-# headline step (python bench.py --no-extra --no-cpu-baseline --no-live-pmc), one JSON line per run under gpurun_out/ab_<name>_<round>.json
+# headline step with the roofline's per-kernel figures (python bench.py --full --no-extra --no-cpu-baseline --no-live-pmc), one JSON line
+# per run as ab_<name>_<round>.json in the output folder
 # and a summary (ms per step, event-timed us per launch by kernel) on stdout.
 rounds=$1; steps=$2; shift 2
 mkdir -p gpurun_out
 for r in $(seq 1 $rounds); do
   for cfg in "$@"; do
     name=${cfg%%=*}; envs=${cfg#*=}; [ "$envs" = "$cfg" ] && envs=""
-    env $(echo $envs | tr '+' ' ') python bench.py --no-extra --no-cpu-baseline --no-live-pmc --steps $steps --warmup 5 $PS_AB_ARGS \
+    env $(echo $envs | tr '+' ' ') python bench.py --full --no-extra --no-cpu-baseline --no-live-pmc --steps $steps --warmup 5 $PS_AB_ARGS \
         > gpurun_out/ab_${name}_${r}.json 2> gpurun_out/ab_${name}_${r}.err || tail -5 gpurun_out/ab_${name}_${r}.err
   done
 done

@@ -10,7 +10,7 @@ for spec in "$@"; do
   out=gpurun_out/sweep_$name; mkdir -p $out
   (
     IFS=, ; for kv in $envs; do [ -n "$kv" ] && export "$kv"; done; unset IFS
-    if [ -z "${PS_SWEEP_TRACE_ONLY:-}" ]; then python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-extra $ARGS > $out/bench.json 2> $out/bench.err; else rm -f $out/bench.json; fi
+    if [ -z "${PS_SWEEP_TRACE_ONLY:-}" ]; then python bench.py --steps 10 --warmup 3 --full --no-cpu-baseline --no-extra $ARGS > $out/bench.json 2> $out/bench.err; else rm -f $out/bench.json; fi
     rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -o bench -- python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-extra $ARGS > $out/bench_trace.json 2> $out/stats.log
   )
   f=$(find $out -name "*kernel_stats.csv" | head -1)

@@ -1,4 +1,4 @@
-"""Print the numbers of interest from bench.py's JSON line (a file argument, else stdin)."""
+"""Print the numbers of interest from the JSON line of `bench.py --full` (a file argument, else stdin)."""
 import sys, json
 text = open(sys.argv[1]).read() if len(sys.argv) > 1 else sys.stdin.read()
 d = json.loads(text.strip().splitlines()[-1])
