@@ -451,6 +451,25 @@ int ps_conv1x1_ex_nhwc_f32(const float *x, int ldx, const float *w, const float 
 int ps_vq_stem_s2d_f32(const float *x, const float *w, const float *bias, int B, int H, int W, float *y, void *stream);
 int ps_vq_head_f32(const float *h, const float *wt, const float *bias, int B, int Hh, int Wh, float *y, void *stream);
 
+/* ---- image quality metrics (csrc/metrics.hip): the reference's evaluation/metrics.py:6-23 psnr / ssim_metric and
+ * models/losses/ssim.py:33-67 _ssim, with the visibility masks of calc_errors_quality.py:28-35.
+ * ps_image_metrics: image pairs img1, img2 (B, C, H, W), C in {1, 3}, any H, W >= 1, read through element strides
+ *   strides[4] = (b, c, h, w) (host arrays; NCHW and channels-last storage alike, no copy), dtype PS_DTYPE_F32 (values in [0, 1]) or
+ *   PS_DTYPE_U8 (converted as x / 255.0f, true division: TF.to_tensor's values bit for bit); mask (B, 1, H, W) f32 contiguous or NULL.
+ *   out (B, 6) f32 per image: psnr, psnr_vis, psnr_invis, ssim, ssim_vis, ssim_invis; "vis" weights a pixel by m, "invis" by 1 - m;
+ *   without a mask the vis / invis columns are NaN.
+ *     psnr = 10 log10(1 / mse): mse = mean over C H W of (img1 - img2)^2; masked: sum(d^2 m) / (3 max(sum_pixels m, 1)) -- the 3 is the
+ *       reference's literal, also for C = 1.  Not clamped: identical images or an empty mask give +inf.
+ *     ssim: 11-tap Gaussian window, sigma 1.5, zero padding 5, channels filtered separately, C1 = 0.01^2, C2 = 0.03^2; mean over C H W;
+ *       masked: sum_pixels(mean_c(ssim map) m) / max(sum_pixels m, 1) (an empty mask gives 0).  Moments in fp64: see csrc/metrics.hip.
+ *   workspace: >= ps_image_metrics_workspace_bytes(B, C, H, W) bytes of device memory (per-tile partial sums).  Two launches on
+ *   `stream`, no allocation, no synchronisation, no atomics: bit-reproducible, and an image's row does not depend on its batch.
+ * ps_image_metrics_workspace_bytes: host-only arithmetic. */
+enum { PS_DTYPE_F32 = 0, PS_DTYPE_U8 = 1 };
+size_t ps_image_metrics_workspace_bytes(int B, int C, int H, int W);
+int ps_image_metrics(const void *img1, const int64_t *strides1, const void *img2, const int64_t *strides2, int dtype, const float *mask,
+                     int B, int C, int H, int W, float *out, void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

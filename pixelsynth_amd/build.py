@@ -29,6 +29,7 @@ UNITS = [
     ("conv_thin.hip", ["-ffp-contract=off"]),
     ("conv1x1.hip", ["-ffp-contract=off"]),
     ("vq_ends.hip", ["-ffp-contract=off"]),
+    ("metrics.hip", ["-ffp-contract=off"]),
     ("host_order.cpp", []),
 ]
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function"]

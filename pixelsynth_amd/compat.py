@@ -3,6 +3,8 @@ drivers written against crockwell/pixelsynth (`demo.py`, `create_vid.py`, `evalu
 path without source edits:
 
     import pixelsynth_amd.compat; pixelsynth_amd.compat.install_reference_aliases()
+
+The reference's metric modules (`evaluation.metrics`, `models.losses.ssim`) are aliased separately, by install_evaluation_aliases().
 """
 import importlib
 import importlib.util
@@ -49,6 +51,33 @@ def install_reference_aliases(force=False):
     """Register the mirrors under the reference's module names."""
     installed = []
     for ref, ours in ALIASES.items():
+        if ref in sys.modules and not force:
+            continue
+        parts = ref.split(".")
+        for i in range(1, len(parts)):
+            pkg = ".".join(parts[:i])
+            parent = _parent_package(pkg)
+            if i > 1:
+                setattr(sys.modules[".".join(parts[:i - 1])], parts[i - 1], parent)
+        mod = importlib.import_module(ours)
+        sys.modules[ref] = mod
+        setattr(sys.modules[".".join(parts[:-1])], parts[-1], mod)
+        installed.append(ref)
+    return installed
+
+
+EVAL_ALIASES = {
+    "evaluation.metrics": "pixelsynth_amd.evaluation.metrics",
+    "models.losses.ssim": "pixelsynth_amd.losses.ssim",
+}
+
+
+def install_evaluation_aliases(force=False):
+    """Register the metric mirrors (PSNR / SSIM on the HIP kernel) under the reference's module names, so its scoring scripts
+    (`from evaluation.metrics import psnr, ssim_metric`) run unchanged.  Separate from install_reference_aliases: it claims the
+    reference's `evaluation` package name."""
+    installed = []
+    for ref, ours in EVAL_ALIASES.items():
         if ref in sys.modules and not force:
             continue
         parts = ref.split(".")

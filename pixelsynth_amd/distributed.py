@@ -178,3 +178,23 @@ def gather_scores(disc_local, entr_local, n, force_collective=False):
     stacked = torch.stack([b.cpu() for b in bufs], 2)            # (2, per, W): candidate k * W + r
     flat = stacked.reshape(2, -1)[:, :n].numpy()
     return flat[0].copy(), flat[1].copy()
+
+
+def gather_rows(local, n, force_collective=False):
+    """Per-item rows of numbers across ranks (the evaluation CLI: the metrics of every image): every rank computed the k numbers of
+    the items shard_views(n) gave it, as the columns of `local` (k, n_local) float64 -- k the same on every rank.  One all_gather of a
+    (k, ceil(n / W)) float64 block per rank, like gather_scores.  -> (k, n) numpy array, column i = item i."""
+    rank, w = world()
+    local = torch.as_tensor(local, dtype=torch.float64).cpu()
+    k = local.shape[0]
+    per = (n + w - 1) // w
+    block = torch.zeros(k, per, dtype=torch.float64)
+    block[:, :local.shape[1]] = local
+    if not _collective(force_collective):
+        return block[:, :n].numpy().copy()
+    if dist.get_backend() != "gloo":
+        block = block.cuda()
+    bufs = [torch.empty_like(block) for _ in range(w)]
+    dist.all_gather(bufs, block)
+    stacked = torch.stack([b.cpu() for b in bufs], 2)            # (k, per, W): item j * W + r
+    return stacked.reshape(k, -1)[:, :n].numpy().copy()

@@ -1,0 +1,22 @@
+"""Quality of rendered views (the reference's evaluation/, calc_errors_quality.py): PSNR and SSIM on the HIP kernel, overall and split
+into the pixels the splat covered ("vis") and the outpainted ones ("invis").  PercSim (VGG / AlexNet weights), FID (Inception weights)
+and the homography consistency score (OpenCV and the reference's point files) are not provided."""
+from ..image_metrics import COLUMNS, image_metrics
+
+__all__ = ["score_views", "COLUMNS"]
+
+
+def score_views(pred, gt, background_mask=None):
+    """pred, gt (B, 3, H, W) frames in the model's [-1, 1] space (mapped by 0.5 x + 0.5, as base_model.py:97-99 does before
+    scoring); background_mask (B, H, W) bool, True where no point was splatted (outpaint_views / synthesize_views) -- "vis" is
+    ~background_mask, "invis" the outpainted region.  -> dict of (B,) f32 tensors: psnr, ssim, and with a mask the vis / invis
+    columns as well."""
+    a, b = pred * 0.5 + 0.5, gt * 0.5 + 0.5
+    mask = None
+    if background_mask is not None:
+        if background_mask.dim() != 3 or tuple(background_mask.shape) != (pred.shape[0],) + tuple(pred.shape[2:]):
+            raise ValueError(f"background_mask must be (B, H, W), got {tuple(background_mask.shape)} for frames {tuple(pred.shape)}")
+        mask = (~background_mask.bool()).unsqueeze(1)
+    rows = image_metrics(a, b, mask)
+    keep = COLUMNS if mask is not None else ("psnr", "ssim")
+    return {k: rows[:, COLUMNS.index(k)] for k in keep}

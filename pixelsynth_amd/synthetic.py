@@ -322,3 +322,46 @@ def network_opts(**kw):
              normalize_before_residual=False)
     o.update(kw)
     return argparse.Namespace(**o)
+
+
+# ------------------------------------------------------------------------------------------------
+# Image pairs and masks for the quality metrics (pixelsynth_amd.image_metrics; tests/golden/metrics.npz)
+# ------------------------------------------------------------------------------------------------
+def metric_pair(seed, B=1, C=3, H=256, W=256, kind="noise_blur"):
+    """(img1, img2), (B,C,H,W) in [0, 1]: float32, or uint8 for kind "uint8".  Elementwise numpy arithmetic only (the same bytes on
+    every machine).  Kinds: "noise_blur" U(0,1) noise against its 3 x 3 box blur (edges replicated); "identical" that noise twice;
+    "flat" 0.7 against 0.6; "flat_noise" the same plus N(0, 1e-3) noise; "uint8" noise_blur rounded to 8 bits."""
+    rs = np.random.RandomState(seed)
+    if kind in ("flat", "flat_noise"):
+        a = np.full((B, C, H, W), 0.7, np.float32)
+        b = np.full((B, C, H, W), 0.6, np.float32)
+        if kind == "flat_noise":
+            a = (a + np.float32(1e-3) * rs.randn(B, C, H, W).astype(np.float32)).astype(np.float32)
+            b = (b + np.float32(1e-3) * rs.randn(B, C, H, W).astype(np.float32)).astype(np.float32)
+        return a, b
+    a = rs.rand(B, C, H, W).astype(np.float32)
+    if kind == "identical":
+        return a, a.copy()
+    p = np.pad(a, ((0, 0), (0, 0), (1, 1), (1, 1)), mode="edge")
+    b = np.zeros_like(a)
+    for dy in range(3):
+        for dx in range(3):
+            b = b + p[:, :, dy:dy + H, dx:dx + W]
+    b = (b / np.float32(9.0)).astype(np.float32)
+    if kind == "uint8":
+        q = lambda x: np.clip(np.round(x * np.float32(255.0)), 0, 255).astype(np.uint8)
+        return q(a), q(b)
+    assert kind == "noise_blur", kind
+    return a, b
+
+
+def metric_mask(kind, seed, B, H, W):
+    """(B,1,H,W) float32 visibility mask, or None for kind "none": "empty", "full", "ragged" (background_masks' ragged edge, the
+    same mask at 256 x 256), "fractional" U(0,1)."""
+    if kind == "none":
+        return None
+    if kind == "fractional":
+        return np.random.RandomState(seed).rand(B, 1, H, W).astype(np.float32)
+    yy, xx = np.meshgrid(np.arange(H), np.arange(W), indexing="ij")
+    m = {"empty": np.zeros((H, W), bool), "full": np.ones((H, W), bool), "ragged": (xx + (yy // 3) % 11) >= (W * 3) // 5}[kind]
+    return np.ascontiguousarray(np.broadcast_to(m.astype(np.float32), (B, 1, H, W)))
