@@ -1,0 +1,135 @@
+"""The AR plan of a batch: what the sampler needs on the device -- generation orders, sampled regions, the three kernel masks and
+the wavefront schedules -- built from background masks (build_ar_plan, the product path) or from values in the reference's form
+(plan_from_reference_args: get_best_sample and sample() as the reference calls them)."""
+import collections
+import os
+import threading
+
+import numpy as np
+import torch
+
+from . import _lib
+from .lmconv.locally_masked_convolution import compact_mask
+from .lmconv.model import TP_MIN_FRAMES, wavefronts
+
+PER_FRAME_PREFIX = os.environ.get("PS_PER_FRAME_PREFIX", "1") != "0"   # plans also carry the schedule of per-frame prefixes (waves_frames)
+
+_PINNED = collections.OrderedDict()
+_PINNED_MAX = 12                       # staging buffers kept (four per batch shape): the oldest shapes are released
+_PLAN_LOCK = threading.RLock()         # the staging buffers are shared state: one plan is staged at a time per process
+
+
+def _pinned(name, shape, dtype):
+    """Page-locked staging buffers (pageable copies ran at ~0.6 GB/s on the MI355X hosts), kept per (name, shape) in a small
+    LRU: callers that vary their batch size do not pile up pinned host memory.  Used under _PLAN_LOCK."""
+    key = (name, tuple(shape), dtype)
+    t = _PINNED.pop(key, None)
+    if t is None:
+        t = torch.empty(shape, dtype=dtype, pin_memory=True)
+    _PINNED[key] = t
+    while len(_PINNED) > _PINNED_MAX:
+        _PINNED.popitem(last=False)
+    return t
+
+
+class ARPlan:
+    """Device-resident, compact result of get_masks_for_batch for B images (see ps_ar_plan).  order_host / region_host: the
+    (B,L) orders (location by rank) and sampled regions (by location) on the host, shape: the (H, W) code grid."""
+
+    def __init__(self, order_loc, region, mask_init, mask_undilated, mask_dilated, order_host, region_host, shape):
+        self.order_loc, self.region = order_loc, region
+        self.mask_init, self.mask_undilated, self.mask_dilated = mask_init, mask_undilated, mask_dilated
+        self.order_host = order_host
+        self.H, self.W = shape
+        L = self.H * self.W
+        # per-frame prefixes: a frame's first SAMPLED position (L: none) -- the observed positions in front of it need no column;
+        # the batch's columns start at the first of them (what ps_ar_plan reports as first_step)
+        sampled = np.take_along_axis(region_host, order_host.astype(np.int64), 1) != 0
+        self.first_steps = np.where(sampled.any(1), sampled.argmax(1), L).astype(np.int32)
+        self.first_step = int(self.first_steps.min())
+        self.n_sampled = region_host.sum(1).astype(int)
+        # the schedule of per-frame prefixes (cols on the device, wave_start on the host) and first_steps on the device: where
+        # build_ar_plan made them, None otherwise
+        self.waves_frames = self.first_steps_dev = None
+        self._waves = None
+
+    @property
+    def gen_order(self):
+        """list of (L,2) int arrays (row, col) by rank: the reference's gen_order (built on demand)."""
+        return [np.stack([o // self.W, o % self.W], 1).astype(np.int64) for o in self.order_host]
+
+    # The wavefront schedule of ONE first step for the whole batch: (cols on the device, wave_start on the host).  A plan that carries
+    # the schedule of per-frame prefixes (waves_frames: what the batched paths run) builds this one on first use -- 3.6 of the 9.8 ms of
+    # host work per 128-view plan, and only the measurement / parity callers ask for it.
+    @property
+    def waves(self):
+        if self._waves is None:
+            self._waves = wavefronts(self.order_host, self.H, self.W, self.first_step, self.order_loc.device)
+        return self._waves
+
+    def schedule(self, per_frame):
+        """The schedule of an AR run of this plan -> (waves, the prefix keywords of PixelCNNEngine.ar_prefix that go with it).
+        per_frame: the caller runs per-frame prefixes where the plan carries their schedule."""
+        if per_frame and self.waves_frames is not None:
+            return self.waves_frames, dict(first_steps=self.first_steps_dev, max_first_step=int(self.first_steps.max()))
+        return self.waves, {}
+
+    def device_tensors(self):
+        """The plan's device tensors (the whole-batch schedule only once it has been built)."""
+        cols = [w[0] for w in (self._waves, self.waves_frames) if w is not None]
+        return [t for t in [self.order_loc, self.region, self.mask_init, self.mask_undilated, self.mask_dilated, self.first_steps_dev] + cols
+                if t is not None]
+
+
+def build_ar_plan(background_mask, G=32, device=None):
+    """background_mask (B,S,S) bool/uint8 tensor (device or host) -> ARPlan on `device`.
+    One device->host copy of the mask (the reference does four, z_buffermodel.py:662-669), the integer work (pooling,
+    distance transforms, generation order) in C++ on the host (csrc/host_order.cpp), the orders back up, and the three
+    kernel masks built from them on the device (ps_order_masks_f32) -- nothing bigger than the orders crosses PCIe."""
+    device = device or (background_mask.device if background_mask.is_cuda else torch.device("cuda", torch.cuda.current_device()))
+    B, S, _ = background_mask.shape
+    L = G * G
+    with _PLAN_LOCK:
+        if background_mask.is_cuda:
+            stage = _pinned("bg", (B, S, S), torch.uint8)
+            as_u8 = (background_mask.view(torch.uint8) if background_mask.dtype == torch.bool and background_mask.is_contiguous()
+                     else background_mask.to(torch.uint8))      # (a bool mask IS bytes of 0 / 1: no conversion pass in front of the copy)
+            stage.copy_(as_u8, non_blocking=True)
+            torch.cuda.current_stream().synchronize()
+            bg = stage.numpy()
+        else:
+            bg = background_mask.to(torch.uint8).contiguous().numpy()
+        order_t, region_t = _pinned("order", (B, L), torch.int32), _pinned("region", (B, L), torch.uint8)
+        order_loc, region = order_t.numpy(), region_t.numpy()
+        rc = _lib.lib().ps_ar_plan(_lib.ptr(bg), B, S, G, _lib.ptr(order_loc), _lib.ptr(region), None, None, None, None)
+        _lib.check(rc, "ps_ar_plan")
+        d_order, d_region = order_t.to(device, non_blocking=True), region_t.to(device, non_blocking=True)
+        masks = [torch.empty(B, 9, L, dtype=torch.float32, device=device) for _ in range(3)]
+        rc = _lib.lib().ps_order_masks_f32(_lib.ptr(d_order), B, G, G, _lib.ptr(masks[0]), _lib.ptr(masks[1]), _lib.ptr(masks[2]),
+                                           _lib.ptr(_lib.status_word(device)), _lib.current_stream())
+        _lib.check(rc, "ps_order_masks_f32")
+        plan = ARPlan(d_order, d_region, *masks, order_loc.copy(), region, (G, G))   # (the staging buffers are reused by the next plan)
+        if PER_FRAME_PREFIX and int(plan.first_steps.max()) > plan.first_step:
+            fs_t = _pinned("first_steps", (B,), torch.int32)
+            fs_t.numpy()[:] = plan.first_steps
+            plan.first_steps_dev = fs_t.to(device, non_blocking=True)
+            plan.waves_frames = wavefronts(plan.order_host, G, G, plan.first_step, device, first_steps=plan.first_steps)
+        if plan.waves_frames is None or B < TP_MIN_FRAMES:
+            plan.waves   # (no per-frame schedule, or a small batch, whose outpaint_planned runs this one: built here, off the AR stream)
+        _lib.read_status("ps_order_masks_f32", device)   # synchronises: the staging buffers are free again, and a bad order is an error
+    return plan
+
+
+def plan_from_reference_args(gen_order, masks, sample_region, device=None):
+    """The ARPlan of values in the REFERENCE's form (what get_masks_for_batch returns without compact=True and what
+    get_best_sample / sample() are handed, z_buffermodel.py:244-248): gen_order = list of (L,2) (row, col) arrays by rank,
+    masks = (masks_init (b*513,9,L), masks_undilated (b*160,9,L), masks_dilated (b*80,9,L)) or their compact (b,9,L) forms,
+    sample_region (b,H,W) = self.downsample(background_mask.float()): a block is sampled where it equals 1 (sample.py:24-41).
+    Draws nothing from numpy's or torch's generators."""
+    device = device or torch.device("cuda", torch.cuda.current_device())
+    B, (H, W) = len(gen_order), sample_region.shape[-2:]
+    order_host = np.stack([np.asarray(g, np.int64)[:, 0] * W + np.asarray(g, np.int64)[:, 1] for g in gen_order]).astype(np.int32)
+    region_host = (sample_region.detach().reshape(B, H * W).cpu().numpy() == 1).astype(np.uint8)
+    m = [compact_mask(t.to(device), B, c).to(torch.float32) for t, c in zip(masks, (513, 160, 80))]
+    m = [(t.expand(B, -1, -1) if t.size(0) == 1 and B > 1 else t).contiguous() for t in m]
+    return ARPlan(torch.from_numpy(order_host).to(device), torch.from_numpy(region_host).to(device), *m, order_host, region_host, (H, W))

@@ -489,6 +489,62 @@ def pack_launches(batches, cap, until_oldest_done=True, budget=None):
     return slices, np.asarray(starts, np.int32)
 
 
+class LaunchPipeline:
+    """The host side of z_buffermodel.outpaint_pipelined: the batches in flight, oldest first, as the records pack_launches advances
+    ('ws', 'w', 'off'; admit adds the caller's own fields), at most `depth` of them."""
+
+    def __init__(self, depth):
+        self.depth = depth
+        self.inflight = []
+        self.done = []               # complete batches not handed back yet, in submission order
+        self.seq = self.next_out = 0
+
+    def free_slot(self):
+        """A share of the handle no batch in flight lives in."""
+        return min(set(range(self.depth)) - {b["slot"] for b in self.inflight})
+
+    def admit(self, ws, first_step, temperature, **fields):
+        assert len(self.inflight) < self.depth
+        self.inflight.append(dict(ws=ws, w=0, off=0, first_step=first_step, temperature=temperature, seq=self.seq, **fields))
+        self.seq += 1
+
+    def step(self, cap, drain=False):
+        """Yields the launch groups of one call as (group, starts, first step, temperature, finished): group = [(record, begin,
+        end)] column ranges in launch order, starts = the launch boundaries (launches take `cap` columns at most), finished = the
+        batches whose last columns are in the group.  With `depth` batches in flight a group runs until the oldest batch is complete
+        (one batch in, one out: the steady state); while the pipeline fills, one group of a `depth`-th of the newest batch's
+        wavefronts' worth of launches; drain: groups until nothing is left."""
+        infl = self.inflight
+        while infl:
+            first, temperature = min(b["first_step"] for b in infl), infl[0]["temperature"]
+            full = len(infl) >= self.depth
+            slices, starts = pack_launches(infl, cap, budget=None if (drain or full) else -(-(len(infl[-1]["ws"]) - 1) // self.depth))
+            group = [(infl[k], a, b) for k, a, b in slices]
+            finished = [b for b in infl if b["w"] >= len(b["ws"]) - 1]
+            infl[:] = [b for b in infl if b["w"] < len(b["ws"]) - 1]
+            self.done = sorted(self.done + finished, key=lambda b: b["seq"])
+            yield group, starts, first, temperature, finished
+            if not drain:
+                return
+
+    def pop(self):
+        """The next batch in SUBMISSION order, if it is complete (a short batch may be through before an older, longer one: it
+        waits), or None."""
+        if self.done and self.done[0]["seq"] == self.next_out:
+            self.next_out += 1
+            return self.done.pop(0)
+        return None
+
+    def flush(self):
+        """The complete batches not handed back yet, oldest first; they are forgotten."""
+        out, self.done, self.next_out = self.done, [], self.seq
+        return out
+
+    def reset(self):
+        """Forget every batch, in flight or complete."""
+        self.inflight, self.done, self.next_out = [], [], self.seq
+
+
 def _wavefronts(order_host, F_, L, H, W, first_step, device, max_cols, keep_host=False, first_steps=None):
     import ctypes
     nsteps = L - first_step

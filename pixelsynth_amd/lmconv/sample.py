@@ -20,7 +20,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .locally_masked_convolution import compact_mask
+from ..ar_plan import plan_from_reference_args
 
 
 def _sample_indices(generation_idx, background_mask, obs):
@@ -48,10 +48,10 @@ def sample(model, generation_idx, mask_init, mask_undilated, mask_dilated, batch
     torch.manual_seed(seed2)
     model.eval()
 
-    sample_indices = _sample_indices(generation_idx, background_mask, obs)
     codes = batch_to_complete.to(dev).to(torch.int64).clone()
 
     if mode == "reference":
+        sample_indices = _sample_indices(generation_idx, background_mask, obs)
         data = F.one_hot(codes, num_classes).permute(0, 3, 1, 2).to(torch.float32)
         for b in range(B):
             if len(sample_indices[b]) > 0:
@@ -67,36 +67,21 @@ def sample(model, generation_idx, mask_init, mask_undilated, mask_dilated, batch
                 data[b, :, i, j] = F.one_hot(new_samples[b], num_classes).to(torch.float32)
     else:
         eng = model.engine(H, W, B)
-        m_i = compact_mask(mask_init.to(dev), B, num_classes + 1)
-        m_u = compact_mask(mask_undilated.to(dev), B, 160)
-        m_d = compact_mask(mask_dilated.to(dev), B, 80)
-        if m_i.size(0) == 1 and B > 1:
-            m_i, m_u, m_d = (m.expand(B, -1, -1).contiguous() for m in (m_i, m_u, m_d))
-        order_np = np.stack([np.asarray(g, dtype=np.int64)[:, 0] * W + np.asarray(g, dtype=np.int64)[:, 1]
-                             for g in generation_idx[:B]]).astype(np.int32)
-        region_np = np.zeros((B, L), np.uint8)
-        first = L
-        for b in range(B):
-            if len(sample_indices[b]) > 0:
-                loc = sample_indices[b][:, 0] * W + sample_indices[b][:, 1]
-                region_np[b, loc] = 1
-                first = min(first, int(np.nonzero(region_np[b][order_np[b]])[0][0]))
-        order = torch.from_numpy(order_np).to(dev)
-        region = torch.from_numpy(region_np).to(dev)
+        plan = plan_from_reference_args(generation_idx[:B], (mask_init, mask_undilated, mask_dilated), background_mask[:B], dev)
+        masks = (plan.mask_init, plan.mask_undilated, plan.mask_dilated)
         c32 = codes.view(B, L).to(torch.int32).contiguous()
         if mode == "fused":
-            from .model import wavefronts
             uniforms = torch.rand(B, L, device=dev, dtype=torch.float32)
-            eng.ar_run(c32, order, region, m_i, m_u, m_d, temperature=temperature, uniforms=uniforms,
-                       first_step=first, waves=wavefronts(order_np, H, W, first, dev))
+            eng.ar_run(c32, plan.order_loc, plan.region, *masks, temperature=temperature, uniforms=uniforms,
+                       first_step=plan.first_step, waves=plan.waves)
             eng.check()   # a column launch that gave up on an in-launch wait raises here instead of returning wrong codes
         elif mode == "multinomial":
-            c32[region.bool()] = -1
-            flat_region = region.bool()
-            for step in range(first, L):
-                logits = eng.ar_step(c32, order, m_i, m_u, m_d, step, first)
+            region_np = plan.region.cpu().numpy()
+            c32[plan.region.bool()] = -1
+            for step in range(plan.first_step, L):
+                logits = eng.ar_step(c32, plan.order_loc, *masks, step, plan.first_step)
                 for b in range(B):
-                    q = int(order_np[b, step])
+                    q = int(plan.order_host[b, step])
                     if not region_np[b, q]:
                         continue
                     prob = torch.softmax(logits / temperature, 1)
@@ -104,7 +89,6 @@ def sample(model, generation_idx, mask_init, mask_undilated, mask_dilated, batch
                     for _ in range(seed):
                         new_samples = torch.multinomial(prob, 1).squeeze(-1)
                     c32[b, q] = new_samples[b].to(torch.int32)
-            del flat_region
             eng.check()
         else:
             raise ValueError(f"unknown AR mode {mode!r}")

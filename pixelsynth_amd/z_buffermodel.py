@@ -12,166 +12,21 @@ absent the batch must carry the tensors it would have produced (`depths`, `codes
 benchmark drives the hot path on its own.
 """
 import math
+import os
 import types
 
 import numpy as np
 import torch
 import torch.nn as nn
 
-from . import _lib
+from .ar_plan import ARPlan, build_ar_plan, plan_from_reference_args
 from .lmconv.layers import PONO
-from .lmconv.model import OurPixelCNN
+from .lmconv.model import TP_MIN_FRAMES, LaunchPipeline, OurPixelCNN, launch_capacity, wavefronts
 from .lmconv.sample import sample
 from .networks.architectures import check_f16x3_overflow, clear_f16x3_overflow, decoder_conv
 from .projection.z_buffer_manipulator import PtsManipulator
 
-
-class ARPlan:
-    """Device-resident, compact result of get_masks_for_batch for B images (see ps_ar_plan)."""
-
-    def __init__(self, order_loc, region, mask_init, mask_undilated, mask_dilated, first_step, order_host, G):
-        self.order_loc, self.region = order_loc, region
-        self.mask_init, self.mask_undilated, self.mask_dilated = mask_init, mask_undilated, mask_dilated
-        self.first_step = first_step
-        self._order_host, self._G = order_host, G
-
-    @property
-    def gen_order(self):
-        """list of (L,2) int arrays (row, col) by rank: the reference's gen_order (built on demand)."""
-        G = self._G
-        return [np.stack([o // G, o % G], 1).astype(np.int64) for o in self._order_host]
-
-    @property
-    def n_sampled(self):
-        return self._n_sampled
-
-    # The wavefront schedule of ONE first step for the whole batch: (cols on the device, wave_start on the host) and the columns on the
-    # host.  A plan that carries the schedule of per-frame prefixes (waves_frames: what the batched paths run) builds this one on first
-    # use -- 3.6 of the 9.8 ms of host work per 128-view plan, and only the measurement / parity callers ask for it.
-    def _schedule(self):
-        if self._waves is None:
-            from .lmconv.model import wavefronts
-            w = wavefronts(self._order_host, self._G, self._G, self.first_step, self.order_loc.device, keep_host=True)
-            self._waves, self._waves_host = w[:2], w[2]
-        return self._waves, self._waves_host
-
-    _waves = _waves_host = None
-
-    @property
-    def waves(self):
-        return self._schedule()[0]
-
-    @waves.setter
-    def waves(self, value):
-        self._waves = value
-
-    @property
-    def waves_host(self):
-        return self._schedule()[1]
-
-
-import collections
-import os
-import threading
-
 _PREFIX_STREAMS = {}    # (device, n) -> the prefix pass's side streams (ZbufferModelPts._prefix_streams)
-PER_FRAME_PREFIX = os.environ.get("PS_PER_FRAME_PREFIX", "1") != "0"   # plans also carry the schedule of per-frame prefixes (waves_frames)
-
-_PINNED = collections.OrderedDict()
-_PINNED_MAX = 12                       # staging buffers kept (four per batch shape): the oldest shapes are released
-_PLAN_LOCK = threading.RLock()         # the staging buffers are shared state: one plan is staged at a time per process
-
-
-def _pinned(name, shape, dtype):
-    """Page-locked staging buffers (pageable copies ran at ~0.6 GB/s on the MI355X hosts), kept per (name, shape) in a small
-    LRU: callers that vary their batch size do not pile up pinned host memory.  Used under _PLAN_LOCK."""
-    key = (name, tuple(shape), dtype)
-    t = _PINNED.pop(key, None)
-    if t is None:
-        t = torch.empty(shape, dtype=dtype, pin_memory=True)
-    _PINNED[key] = t
-    while len(_PINNED) > _PINNED_MAX:
-        _PINNED.popitem(last=False)
-    return t
-
-
-def build_ar_plan(background_mask, G=32, device=None):
-    """background_mask (B,S,S) bool/uint8 tensor (device or host) -> ARPlan on `device`.
-    One device->host copy of the mask (the reference does four, z_buffermodel.py:662-669), the integer work (pooling,
-    distance transforms, generation order) in C++ on the host (csrc/host_order.cpp), the orders back up, and the three
-    kernel masks built from them on the device (ps_order_masks_f32) -- nothing bigger than the orders crosses PCIe."""
-    with _PLAN_LOCK:
-        return _build_ar_plan(background_mask, G, device)
-
-
-def _build_ar_plan(background_mask, G, device):
-    import ctypes
-    device = device or (background_mask.device if background_mask.is_cuda else torch.device("cuda", torch.cuda.current_device()))
-    B, S, _ = background_mask.shape
-    L = G * G
-    if background_mask.is_cuda:
-        stage = _pinned("bg", (B, S, S), torch.uint8)
-        as_u8 = (background_mask.view(torch.uint8) if background_mask.dtype == torch.bool and background_mask.is_contiguous()
-                 else background_mask.to(torch.uint8))      # (a bool mask IS bytes of 0 / 1: no conversion pass in front of the copy)
-        stage.copy_(as_u8, non_blocking=True)
-        torch.cuda.current_stream().synchronize()
-        bg = stage.numpy()
-    else:
-        bg = background_mask.to(torch.uint8).contiguous().numpy()
-    order_t, region_t = _pinned("order", (B, L), torch.int32), _pinned("region", (B, L), torch.uint8)
-    order_loc, region = order_t.numpy(), region_t.numpy()
-    first = ctypes.c_int32(0)
-    rc = _lib.lib().ps_ar_plan(_lib.ptr(bg), B, S, G, _lib.ptr(order_loc), _lib.ptr(region), None, None, None,
-                               ctypes.cast(ctypes.byref(first), ctypes.c_void_p))
-    _lib.check(rc, "ps_ar_plan")
-    d_order, d_region = order_t.to(device, non_blocking=True), region_t.to(device, non_blocking=True)
-    masks = [torch.empty(B, 9, L, dtype=torch.float32, device=device) for _ in range(3)]
-    rc = _lib.lib().ps_order_masks_f32(_lib.ptr(d_order), B, G, G, _lib.ptr(masks[0]), _lib.ptr(masks[1]), _lib.ptr(masks[2]),
-                                       _lib.ptr(_lib.status_word(device)), _lib.current_stream())
-    _lib.check(rc, "ps_order_masks_f32")
-    order_host = order_loc.copy()       # (the staging buffer is reused by the next plan)
-    plan = ARPlan(d_order, d_region, masks[0], masks[1], masks[2], int(first.value), order_host, G)
-    plan._n_sampled = region.sum(1).astype(int)
-    from .lmconv.model import wavefronts
-    # per-frame prefixes: a frame's first SAMPLED position (L: none) -- the observed positions in front of it need no column
-    sampled = np.take_along_axis(region, order_loc.astype(np.int64), 1) != 0
-    plan.first_steps = np.where(sampled.any(1), sampled.argmax(1), L).astype(np.int32)
-    if PER_FRAME_PREFIX and int(plan.first_steps.min()) >= plan.first_step and int(plan.first_steps.max()) > plan.first_step:
-        fs_t = _pinned("first_steps", (B,), torch.int32)
-        fs_t.numpy()[:] = plan.first_steps
-        plan.first_steps_dev = fs_t.to(device, non_blocking=True)
-        w = wavefronts(order_host, G, G, plan.first_step, device, keep_host=True, first_steps=plan.first_steps)
-        plan.waves_frames = w[:2]
-    from .lmconv.model import TP_MIN_FRAMES
-    if getattr(plan, "waves_frames", None) is None or B < TP_MIN_FRAMES:
-        plan._schedule()   # (no per-frame schedule, or a small batch, whose outpaint_planned runs this one: built here, off the AR stream)
-    _lib.read_status("ps_order_masks_f32", device)   # synchronises: the staging buffers are free again, and a bad order is an error
-    return plan
-
-
-def plan_from_reference_args(gen_order, masks, sample_region, G=32, device=None):
-    """The ARPlan of values in the REFERENCE's form (what get_masks_for_batch returns without compact=True and what
-    get_best_sample / sample() are handed, z_buffermodel.py:244-248): gen_order = list of (L,2) (row, col) arrays by rank,
-    masks = (masks_init (b*513,9,L), masks_undilated (b*160,9,L), masks_dilated (b*80,9,L)) or their compact (b,9,L) forms,
-    sample_region (b,G,G) = self.downsample(background_mask.float()): a block is sampled where it equals 1 (sample.py:24-41)."""
-    from .lmconv.locally_masked_convolution import compact_mask
-    from .lmconv.model import wavefronts
-    device = device or torch.device("cuda", torch.cuda.current_device())
-    B, L = len(gen_order), G * G
-    order_host = np.stack([np.asarray(g, np.int64)[:, 0] * G + np.asarray(g, np.int64)[:, 1] for g in gen_order]).astype(np.int32)
-    region_host = (sample_region.detach().reshape(B, L).cpu().numpy() == 1).astype(np.uint8)
-    first = L
-    for b in range(B):
-        hit = np.nonzero(region_host[b][order_host[b]])[0]
-        if hit.size:
-            first = min(first, int(hit[0]))
-    m = [compact_mask(t.to(device), B, c).to(torch.float32) for t, c in zip(masks, (513, 160, 80))]
-    m = [(t.expand(B, -1, -1) if t.size(0) == 1 and B > 1 else t).contiguous() for t in m]
-    plan = ARPlan(torch.from_numpy(order_host).to(device), torch.from_numpy(region_host).to(device), m[0], m[1], m[2], first,
-                  order_host, G)
-    plan._n_sampled = region_host.sum(1).astype(int)
-    plan.waves = wavefronts(order_host, G, G, first, device)
-    return plan
 
 
 def rank_samples(discrim_scores, entropy_scores):
@@ -197,6 +52,25 @@ class _SceneState:
         self.out_RTinv = None         # inverse pose of the last rendered frame
         self.numerator = None
         self.direction = None
+
+
+class _PipeBuffers:
+    """What outpaint_pipelined keeps between calls.  The batches in flight live in ONE engine handle of depth x V frames: batch i in
+    frames [V slot, ...), its slot dealt by `sched` (lmconv.model.LaunchPipeline, the host side).  The per-frame arrays of the C ABI
+    (codes, order, region, the three masks, uniforms) are persistent (depth x V, ...) tensors; a batch's plan is copied into its share
+    on the stream of the AR run (14 MB, ~10 us), so that planning on a side stream never writes under a launch that still reads another
+    batch's share."""
+
+    def __init__(self, V, depth, L, device):
+        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=device)
+        F_ = depth * V
+        self.V, self.device, self.sched = V, device, LaunchPipeline(depth)
+        self.codes, self.order, self.region = z((F_, L), torch.int32), z((F_, L), torch.int32), z((F_, L), torch.uint8)
+        self.masks = [z((F_, 9, L), torch.float32) for _ in range(3)]
+        self.uniforms, self.first_steps = z((F_, L), torch.float32), z((F_,), torch.int32)
+        self.offset = [torch.tensor([k * V, 0], dtype=torch.int32, device=device) for k in range(depth)]   # a slot's frame offset
+        self.order[:] = torch.arange(L, device=device, dtype=torch.int32)   # (a frame nobody has planned yet still holds a permutation)
+        self.args = (self.codes, self.order, self.region, *self.masks)
 
 
 class ZbufferModelPts(nn.Module):
@@ -329,10 +203,7 @@ class ZbufferModelPts(nn.Module):
     def adopt_planned(planned, stream):
         """A plan made on a side stream is about to be consumed on `stream`: tell the caching allocator, so that the
         plan's buffers are not recycled on the side stream while work queued on `stream` still reads them."""
-        plan = planned["plan"]
-        more = (plan.waves_frames[0], plan.first_steps_dev) if getattr(plan, "waves_frames", None) is not None else ()
-        for t in (planned["gen_fs"], planned["background_mask"], plan.order_loc, plan.region, plan.mask_init,
-                  plan.mask_undilated, plan.mask_dilated) + ((plan._waves[0],) if plan._waves is not None else ()) + more:
+        for t in [planned["gen_fs"], planned["background_mask"]] + planned["plan"].device_tensors():
             if t.numel():
                 t.record_stream(stream)
 
@@ -358,42 +229,45 @@ class ZbufferModelPts(nn.Module):
         # sampled position, the columns start there (ps_pixelcnn_ar_prefix_frames / ps_ar_wavefronts_frames: the same codes)
         # (batches of the throughput form only: the launches of a small batch are bound by their latency, not by their columns --
         # 16 views: 5.55 ms per step with one prefix for the batch, 5.66 with per-frame ones)
-        from .lmconv.model import TP_MIN_FRAMES
-        waves_f = getattr(plan, "waves_frames", None) if self.PER_FRAME_PREFIX and V >= TP_MIN_FRAMES else None
-        pf = dict(first_steps=plan.first_steps_dev, max_first_step=int(plan.first_steps.max())) if waves_f is not None else {}
-        waves = waves_f if waves_f is not None else plan.waves
-        if (between is None and nsplit == 1 and waves_f is None) or plan.first_step >= L:   # (nothing to walk: only the whole-grid pass runs)
-            eng.ar_run(c32, plan.order_loc, plan.region, plan.mask_init, plan.mask_undilated, plan.mask_dilated,
-                       temperature=temperature, uniforms=uniforms, forced=forced, first_step=plan.first_step, waves=plan.waves)
+        waves, pf = plan.schedule(self.PER_FRAME_PREFIX and V >= TP_MIN_FRAMES)
+        args = (c32, plan.order_loc, plan.region, plan.mask_init, plan.mask_undilated, plan.mask_dilated)
+        if (between is None and nsplit == 1 and not pf) or plan.first_step >= L:   # (nothing to walk: only the whole-grid pass runs)
+            eng.ar_run(*args, temperature=temperature, uniforms=uniforms, forced=forced, first_step=plan.first_step, waves=waves)
             if between is not None:
                 between()
         else:
-            args = (c32, plan.order_loc, plan.region, plan.mask_init, plan.mask_undilated, plan.mask_dilated, plan.first_step)
-            if nsplit == 1:
-                eng.ar_prefix(*args, **pf)
-            else:
-                # The whole-grid prefix pass of disjoint frame ranges on streams of their own (ps_pixelcnn_ar_prefix is built for it: every
-                # range has its part of the scratch): a launch empties over its last tenth, and the next stage's launch cannot start
-                # before it has -- with a second range's launches in flight, their workgroups take the places as they fall free.
-                main = torch.cuda.current_stream()
-                ready = torch.cuda.Event()
-                ready.record(main)
-                per = V // nsplit
-                for k, st in enumerate(self._prefix_streams(nsplit - 1, c32.device)):
-                    st.wait_event(ready)
-                    with torch.cuda.stream(st):
-                        eng.ar_prefix(*args, frame_begin=(k + 1) * per, frame_end=(k + 2) * per if k + 2 < nsplit else V, **pf)
-                    for t in (c32,) + args[1:6] + ((pf["first_steps"],) if pf else ()):
-                        t.record_stream(st)
-                eng.ar_prefix(*args, frame_begin=0, frame_end=per, **pf)
-                for st in self._prefix_streams(nsplit - 1, c32.device):
-                    main.wait_stream(st)
+            self._prefix_pass(eng, args, plan.first_step, 0, V, nsplit, pf, record=True)
             if between is not None:
                 between()
-            eng.ar_columns(c32, plan.order_loc, plan.region, plan.mask_init, plan.mask_undilated, plan.mask_dilated, waves,
-                           temperature=temperature, uniforms=uniforms, forced=forced, first_step=plan.first_step)
+            eng.ar_columns(*args, waves, temperature=temperature, uniforms=uniforms, forced=forced, first_step=plan.first_step)
         planned["codes"] = c32.view(V, self.obs[1], self.obs[2])
         return planned
+
+    def _prefix_pass(self, eng, args, first_step, lo, hi, nsplit, pf, record=False):
+        """The whole-grid prefix pass of frames [lo, hi) of `args` (codes, order, region, the three masks), dealt to nsplit ranges
+        (_prefix_split): the first on the current stream, the others each on a side stream of their own (_prefix_streams), which the
+        current stream then waits for.  ps_pixelcnn_ar_prefix is built for it -- every range has its part of the scratch: a launch
+        empties over its last tenth, and the next stage's launch cannot start before it has -- with a second range's launches in
+        flight, their workgroups take the places as they fall free.  record: the tensors are the caller's own (outpaint_planned's
+        are per batch), so the caching allocator is told that the side streams read them."""
+        if nsplit == 1:
+            eng.ar_prefix(*args, first_step, frame_begin=lo, frame_end=hi, **pf)
+            return
+        main = torch.cuda.current_stream()
+        ready = torch.cuda.Event()
+        ready.record(main)
+        per = (hi - lo) // nsplit
+        sides = self._prefix_streams(nsplit - 1, args[0].device)
+        for k, side in enumerate(sides):
+            side.wait_event(ready)
+            with torch.cuda.stream(side):
+                eng.ar_prefix(*args, first_step, frame_begin=lo + (k + 1) * per, frame_end=lo + (k + 2) * per if k + 2 < nsplit else hi, **pf)
+            if record:
+                for t in args + ((pf["first_steps"],) if pf else ()):
+                    t.record_stream(side)
+        eng.ar_prefix(*args, first_step, frame_begin=lo, frame_end=lo + per, **pf)
+        for side in sides:
+            main.wait_stream(side)
 
     # ---------------------------------------------------------------- the AR runs of consecutive batches, overlapped
     PIPE_CAP = 1024         # columns a merged launch takes (lmconv.model.COLUMNS_PER_LAUNCH_TP)
@@ -410,8 +284,6 @@ class ZbufferModelPts(nn.Module):
     def pipe_depth(self, V):
         """Batches of V views that outpaint_pipelined keeps in flight at most (PS_PIPE_DEPTH overrides): the frames of its engine handle
         are that many batches'; a batch's result comes back at most depth - 1 calls late."""
-        import os
-        from .lmconv.model import TP_MIN_FRAMES
         d = os.environ.get("PS_PIPE_DEPTH")
         if d:
             return max(2, min(8, int(d)))
@@ -424,25 +296,15 @@ class ZbufferModelPts(nn.Module):
         return self.pipe_depth(V) * V
 
     def _pipe_buffers(self, V, device):
-        """The batches in flight live in ONE engine handle of depth x V frames: batch i in frames [V (i % depth), ...).  The per-frame
-        arrays of the C ABI (codes, order, region, the three masks, uniforms) are persistent (depth x V, ...) tensors; a batch's plan is
-        copied into its share on the stream of the AR run (14 MB, ~10 us), so that planning on a side stream never writes under a
-        launch that still reads another batch's share."""
+        """The pipeline of batches of V views (_PipeBuffers), made anew when V, the device or the depth has changed."""
         st = self.__dict__.get("_pipe")
         D = self.pipe_depth(V)
-        if st is not None and (st["V"] != V or st["device"] != device or st["depth"] != D):
-            if st["inflight"] or st["done"]:
+        if st is not None and (st.V != V or st.device != device or st.sched.depth != D):
+            if st.sched.inflight or st.sched.done:
                 raise RuntimeError("outpaint_pipelined: a batch of another size is still in flight (call outpaint_flush first)")
             st = None
         if st is None:
-            L = self.obs[1] * self.obs[2]
-            z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=device)
-            st = self.__dict__["_pipe"] = dict(
-                V=V, depth=D, device=device, inflight=[], done=[], seq=0, next_out=0, codes=z((D * V, L), torch.int32), order=z((D * V, L), torch.int32),
-                region=z((D * V, L), torch.uint8), masks=[z((D * V, 9, L), torch.float32) for _ in range(3)],
-                uniforms=z((D * V, L), torch.float32), first_steps=z((D * V,), torch.int32),
-                offset=[torch.tensor([k * V, 0], dtype=torch.int32, device=device) for k in range(D)])
-            st["order"][:] = torch.arange(L, device=device, dtype=torch.int32)   # (a frame nobody has planned yet still holds a permutation)
+            st = self.__dict__["_pipe"] = _PipeBuffers(V, D, self.obs[1] * self.obs[2], device)
         return st
 
     @torch.no_grad()
@@ -461,109 +323,61 @@ class ZbufferModelPts(nn.Module):
         V, G = gen_fs.shape[0], self.obs[1]
         L = G * self.obs[2]
         st = self._pipe_buffers(V, gen_fs.device)
-        D = st["depth"]
         if codes is None:
             codes = self.vqvae.encode_codes(gen_fs)
         if uniforms is None:
             uniforms = torch.rand(V, L, device=gen_fs.device, dtype=torch.float32)
-        eng = self.outpaint2.engine(G, self.obs[2], D * V)
-        args = (st["codes"], st["order"], st["region"], st["masks"][0], st["masks"][1], st["masks"][2])
-        if st["inflight"] and st["inflight"][0]["temperature"] != temperature:
+        eng = self.outpaint2.engine(G, self.obs[2], st.sched.depth * V)
+        if st.sched.inflight and st.sched.inflight[0]["temperature"] != temperature:
             # what is in flight was planned with ANOTHER temperature: it cannot ride in this batch's launches (a launch has one
             # temperature), so it is finished now, as launches of its own, with its own -- the codes stay those of outpaint_planned
-            self._pipe_step(eng, st, args, V, drain=True)
-        h = min(set(range(D)) - {b["slot"] for b in st["inflight"]})      # a share of the handle nobody in flight lives in
+            self._pipe_step(eng, st, drain=True)
+        h = st.sched.free_slot()
         lo, hi = h * V, (h + 1) * V
         # (as elementwise kernels, not Tensor.copy_: same-type copies go through hipMemcpyAsync, which on the stream of the AR run stalled
         # for ~60 ms every few steps)
         put = lambda dst, src: torch.add(src, 0, out=dst) if src.dtype == dst.dtype else dst.copy_(src)
-        put(st["codes"][lo:hi], codes.reshape(V, L))
-        put(st["order"][lo:hi], plan.order_loc)
-        put(st["region"][lo:hi], plan.region)
-        for dst, src in zip(st["masks"], (plan.mask_init, plan.mask_undilated, plan.mask_dilated)):
+        put(st.codes[lo:hi], codes.reshape(V, L))
+        put(st.order[lo:hi], plan.order_loc)
+        put(st.region[lo:hi], plan.region)
+        for dst, src in zip(st.masks, (plan.mask_init, plan.mask_undilated, plan.mask_dilated)):
             put(dst[lo:hi], src.expand(V, -1, -1) if src.size(0) == 1 else src)
-        put(st["uniforms"][lo:hi], uniforms)
+        put(st.uniforms[lo:hi], uniforms)
         # PER-FRAME prefixes (plans that carry their schedule): the whole-grid pass takes every frame up to ITS first sampled position --
         # a location costs it half of what a column costs, and the bits are the same
-        waves = getattr(plan, "waves_frames", None) if self.PER_FRAME_PREFIX else None
-        pf = {}
-        if waves is not None:
-            put(st["first_steps"][lo:hi], plan.first_steps_dev)
-            pf = dict(first_steps=st["first_steps"], max_first_step=int(plan.first_steps.max()))
-        else:
-            waves = plan.waves
+        waves, pf = plan.schedule(self.PER_FRAME_PREFIX)
+        if pf:
+            put(st.first_steps[lo:hi], pf["first_steps"])
+            pf["first_steps"] = st.first_steps
         # the prefix pass of this batch's frames (two ranges on two streams, as in outpaint_planned)
-        nsplit = self._prefix_split(V, busy=between is not None)
-        if nsplit == 1:
-            eng.ar_prefix(*args, plan.first_step, frame_begin=lo, frame_end=hi, **pf)
-        else:
-            main = torch.cuda.current_stream()
-            ready = torch.cuda.Event()
-            ready.record(main)
-            per = V // nsplit
-            for k, side in enumerate(self._prefix_streams(nsplit - 1, gen_fs.device)):
-                side.wait_event(ready)
-                with torch.cuda.stream(side):
-                    eng.ar_prefix(*args, plan.first_step, frame_begin=lo + (k + 1) * per, frame_end=lo + (k + 2) * per if k + 2 < nsplit else hi, **pf)
-            eng.ar_prefix(*args, plan.first_step, frame_begin=lo, frame_end=lo + per, **pf)
-            for side in self._prefix_streams(nsplit - 1, gen_fs.device):
-                main.wait_stream(side)
+        self._prefix_pass(eng, st.args, plan.first_step, lo, hi, self._prefix_split(V, busy=between is not None), pf)
         if between is not None:
             between()
         # this batch's schedule, in the handle's frame numbering, joins the batches in flight.  The columns are on the device already (the
         # plan's upload); a call's launches are put together THERE, from slices of the batches' columns (one concatenation) -- nothing
         # crosses PCIe on the stream of the AR run.
-        ws = np.asarray(waves[1])
-        dcols = waves[0] + st["offset"][h] if h else waves[0]
-        st["inflight"].append(dict(planned=planned, cols=dcols, ws=ws, w=0, off=0, first_step=plan.first_step, slot=h, temperature=temperature,
-                                   seq=st["seq"]))
-        st["seq"] += 1
-        self._pipe_step(eng, st, args, V)
-        return self._pipe_pop(st)
+        st.sched.admit(np.asarray(waves[1]), plan.first_step, temperature, planned=planned, slot=h,
+                       cols=waves[0] + st.offset[h] if h else waves[0])
+        self._pipe_step(eng, st)
+        done = st.sched.pop()
+        return None if done is None else done["planned"]
 
-    @staticmethod
-    def _pipe_pop(st):
-        """The next batch in SUBMISSION order, if it is complete (a short batch may be through before an older, longer one: it waits)."""
-        if st["done"] and st["done"][0][0] == st["next_out"]:
-            st["next_out"] += 1
-            return st["done"].pop(0)[1]
-        return None
+    def _pipe_step(self, eng, st, drain=False):
+        """One call's launches out of the batches in flight (lmconv.model.LaunchPipeline.step), each group of them put together from
+        slices of the batches' columns; batches whose last column has been queued are complete: their codes are taken out of the handle
+        behind the launches."""
+        cap = min(int(os.environ.get("PS_PIPE_CAP", self.PIPE_CAP)), self.PIPE_CAP, launch_capacity(st.V))
+        for group, starts, first, temperature, finished in st.sched.step(cap, drain):
+            if group:
+                self._pipe_columns(eng, st, torch.cat([b["cols"][a:e] for b, a, e in group]), starts, first, temperature)
+            for b in finished:
+                lo = b["slot"] * st.V
+                b["planned"]["codes"] = st.codes[lo:lo + st.V].clone().view(st.V, self.obs[1], self.obs[2])
 
-    def _pipe_step(self, eng, st, args, V, drain=False):
-        """One call's launches out of the batches in flight (lmconv.model.pack_launches: every launch takes what is left of each batch's
-        current wavefront, oldest first, under the launch capacity).  With the handle full -- `depth` batches in flight -- launches run
-        until the oldest batch is complete (one batch in, one out: the steady state); while it fills, a `depth`-th of the new batch's
-        wavefronts' worth; drain: until nothing is left.  Batches whose last column has been queued are complete: their codes are
-        taken out of the handle behind the launches."""
-        from .lmconv.model import launch_capacity, pack_launches
-        infl = st["inflight"]
-        cap = min(int(os.environ.get("PS_PIPE_CAP", self.PIPE_CAP)), self.PIPE_CAP, launch_capacity(V))
-        while infl:
-            first = min(b["first_step"] for b in infl)
-            temperature = infl[0]["temperature"]
-            full = len(infl) >= st["depth"]
-            slices, starts = pack_launches(infl, cap, until_oldest_done=True,
-                                           budget=None if (drain or full) else -(-(len(infl[-1]["ws"]) - 1) // st["depth"]))
-            if slices:
-                cols = torch.cat([infl[k]["cols"][a:b] for k, a, b in slices])
-                self._pipe_columns(eng, st, args, cols, starts, first, temperature)
-            finished = [b for b in infl if b["w"] >= len(b["ws"]) - 1]
-            infl[:] = [b for b in infl if b["w"] < len(b["ws"]) - 1]
-            st["done"] = sorted(st["done"] + [(b["seq"], self._pipe_done(st, b)) for b in finished], key=lambda t: t[0])
-            if not drain:
-                break
-
-    def _pipe_columns(self, eng, st, args, cols, ws, first, temperature):
+    def _pipe_columns(self, eng, st, cols, ws, first, temperature):
         if len(ws) > 1 and ws[-1] > 0:
-            eng.ar_columns(*args, (cols.contiguous(), np.ascontiguousarray(ws, np.int32)), temperature=temperature, uniforms=st["uniforms"],
+            eng.ar_columns(*st.args, (cols.contiguous(), np.ascontiguousarray(ws, np.int32)), temperature=temperature, uniforms=st.uniforms,
                            first_step=int(first))
-
-    def _pipe_done(self, st, b):
-        """The batch whose last columns have just been queued: its codes out of the handle's share."""
-        V, lo = st["V"], b["slot"] * st["V"]
-        out = b["planned"]
-        out["codes"] = st["codes"][lo:lo + V].clone().view(V, self.obs[1], self.obs[2])
-        return out
 
     @torch.no_grad()
     def outpaint_flush(self):
@@ -572,13 +386,9 @@ class ZbufferModelPts(nn.Module):
         st = self.__dict__.get("_pipe")
         if st is None:
             return []
-        if st["inflight"]:
-            eng = self.outpaint2.engine(self.obs[1], self.obs[2], st["depth"] * st["V"])
-            args = (st["codes"], st["order"], st["region"], st["masks"][0], st["masks"][1], st["masks"][2])
-            self._pipe_step(eng, st, args, st["V"], drain=True)
-        out, st["done"] = [d for _, d in st["done"]], []
-        st["next_out"] = st["seq"]
-        return out
+        if st.sched.inflight:
+            self._pipe_step(self.outpaint2.engine(self.obs[1], self.obs[2], st.sched.depth * st.V), st, drain=True)
+        return [b["planned"] for b in st.sched.flush()]
 
     def outpaint_reset(self):
         """Forget the batches outpaint_pipelined still holds (their remaining wavefronts never run; their codes are lost).  For a caller
@@ -587,7 +397,7 @@ class ZbufferModelPts(nn.Module):
         it on their way out of a failed run)."""
         st = self.__dict__.get("_pipe")
         if st is not None:
-            st["inflight"], st["done"], st["next_out"] = [], [], st["seq"]
+            st.sched.reset()
 
     PREFIX_SPLIT_MIN_VIEWS = 64   # below this a launch of half the frames no longer fills the chip
     PREFIX_STREAMS = 2            # 128 views: 18.16 -> 17.95 ms per step (three alternating pairs); 4 ranges lose (18.59)
@@ -599,7 +409,6 @@ class ZbufferModelPts(nn.Module):
         between=) -- with the runtime's default of four hardware queues one more stream then shares a queue with another and the step
         gets SLOWER (19.5 against 18.4 ms), so the pass is split only when the process runs with GPU_MAX_HW_QUEUES >= 8 (18.1 ms;
         bench.py sets it, tools/hwq_ab.sh measured it)."""
-        import os
         n = int(os.environ.get("PS_PREFIX_STREAMS", self.PREFIX_STREAMS))
         if busy and "PS_PREFIX_STREAMS" not in os.environ and int(os.environ.get("GPU_MAX_HW_QUEUES", "4")) < 8:
             n = 1
@@ -613,7 +422,6 @@ class ZbufferModelPts(nn.Module):
         key = (str(device), n)
         cache = _PREFIX_STREAMS
         if key not in cache:
-            import os
             skip = int(os.environ.get("PS_PREFIX_STREAM_SKIP", "0"))    # tuning: streams created (and kept) in front of them
             cache[("skip",) + key] = [torch.cuda.Stream(device=device) for _ in range(skip)]
             cache[key] = [torch.cuda.Stream(device=device) for _ in range(n)]
@@ -767,7 +575,7 @@ class ZbufferModelPts(nn.Module):
             plan, codes, background_mask, gen_fs, netD, input_img = args
         else:
             gen_order, masks, codes, background_mask, gen_fs, netD, input_img = args
-            plan = plan_from_reference_args(gen_order, masks, self.downsample(background_mask.float()), self.obs[1], gen_fs.device)
+            plan = plan_from_reference_args(gen_order, masks, self.downsample(background_mask.float()), gen_fs.device)
         n = max(int(getattr(self.opt, "num_samples", 1)), 1)
         if n > 1 and (netD is None or self.classifier is None):
             raise RuntimeError("num_samples > 1 ranks candidates with the discriminator (netD: pixelsynth_amd.losses.DiscriminatorLoss "
@@ -791,8 +599,7 @@ class ZbufferModelPts(nn.Module):
             rep = lambda t: t.repeat((k,) + (1,) * (t.dim() - 1)).contiguous()
             waves = plan.waves
             if k > 1:
-                from .lmconv.model import wavefronts
-                waves = wavefronts(np.tile(plan._order_host, (k, 1)), G, self.obs[2], plan.first_step, dev)
+                waves = wavefronts(np.tile(plan.order_host, (k, 1)), G, self.obs[2], plan.first_step, dev)
             c = rep(codes.reshape(B, L).to(torch.int32))
             eng = self.outpaint2.engine(G, self.obs[2], k * B)
             eng.ar_run(c, rep(plan.order_loc), rep(plan.region), rep(plan.mask_init), rep(plan.mask_undilated),

@@ -1,11 +1,11 @@
-"""CPU: the host logic that lets several batches share the column launches (lmconv.model.pack_launches, what
+"""CPU: the host logic that lets several batches share the column launches (lmconv.model.LaunchPipeline over pack_launches, what
 z_buffermodel.outpaint_pipelined runs): whatever the depth, every column of every batch runs exactly once, a batch's waves keep their
 order -- a column of wave w + 1 never shares a launch with, or precedes, a column of wave w of the same batch -- no launch takes more than
-the capacity, and with a few batches in flight the launches are full."""
+the capacity, with a few batches in flight the launches are full, and batches come back in submission order."""
 import numpy as np
 import pytest
 
-from pixelsynth_amd.lmconv.model import pack_launches
+from pixelsynth_amd.lmconv.model import LaunchPipeline, pack_launches
 
 
 def schedule(rs, n_waves, width):
@@ -14,27 +14,27 @@ def schedule(rs, n_waves, width):
 
 
 def run_pipeline(schedules, depth, cap):
-    """outpaint_pipelined's loop on the host -> (launches: lists of (batch, column) pairs, completion order, launches per call)."""
-    inflight, launches, finished, per_call = [], [], [], []
+    """LaunchPipeline driven as outpaint_pipelined drives it -> (launches: lists of (batch, column) pairs, completion order, launches
+    per call)."""
+    pipe, launches, finished, per_call, returned = LaunchPipeline(depth), [], [], [], []
 
     def step(drain=False):
         n0 = len(launches)
-        while inflight:
-            full = len(inflight) >= depth
-            slices, starts = pack_launches(inflight, cap, budget=None if (drain or full) else -(-(len(inflight[-1]["ws"]) - 1) // depth))
-            flat = [(inflight[k]["id"], c) for k, a, b in slices for c in range(a, b)]
+        for group, starts, _, _, done in pipe.step(cap, drain):
+            flat = [(b["id"], c) for b, a, e in group for c in range(a, e)]
             assert starts[-1] == len(flat)
             launches.extend(flat[starts[j]:starts[j + 1]] for j in range(len(starts) - 1))
-            finished.extend(b["id"] for b in inflight if b["w"] >= len(b["ws"]) - 1)
-            inflight[:] = [b for b in inflight if b["w"] < len(b["ws"]) - 1]
-            if not drain:
-                break
+            finished.extend(b["id"] for b in done)
         per_call.append(len(launches) - n0)
     for i, ws in enumerate(schedules):
-        assert len(inflight) < depth          # (a share of the handle is free when a batch arrives)
-        inflight.append(dict(ws=ws, w=0, off=0, id=i))
+        assert len(pipe.inflight) < depth          # (a share of the handle is free when a batch arrives)
+        pipe.admit(ws, 0, 0.7, id=i, slot=pipe.free_slot())
         step()
+        out = pipe.pop()
+        returned += [] if out is None else [out["id"]]
     step(drain=True)
+    returned += [b["id"] for b in pipe.flush()]
+    assert returned == list(range(len(schedules)))  # results come back in submission order
     return launches, finished, per_call
 
 

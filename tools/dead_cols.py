@@ -9,7 +9,7 @@ model = bench.build_model(dev)
 d, _ = bench.make_inputs(0, V, dev)
 out = bench.run_step(model, d, 1)
 plan = out["plan"]
-order = plan._order_host            # (F, L) location by rank
+order = plan.order_host             # (F, L) location by rank
 region = plan.region.cpu().numpy() # (F, L) by location
 first = plan.first_step
 F, L = order.shape
