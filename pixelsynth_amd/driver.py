@@ -30,6 +30,7 @@ import numpy as np
 import torch
 
 from . import distributed as D, synthetic as syn
+from .networks.f16x3 import checked
 
 
 def make_opts(**kw):
@@ -65,19 +66,23 @@ def trajectory(model, input_RT, kind, n):
 @torch.no_grad()
 def render_views(model, img, depth, cam, poses, temperature=0.7, seed=0):
     """img (1,3,S,S) in [-1,1], depth (1,1,S,S), cam dict of (1,4,4) tensors, poses as from trajectory()
-    -> dict(frames (V,3,S,S), features, background_mask, codes): the views of `poses`, batched through outpaint_views."""
+    -> dict(frames (V,3,S,S), features, background_mask, codes): the views of `poses`, batched through outpaint_views.  One scope of the
+    split-fp16 overflow guard (networks/f16x3.checked): checked once, rerun in fp32 if an activation left fp16's range."""
     V = len(poses)
     rep = lambda t: t.expand(V, *t.shape[1:]).contiguous()
     RT2 = torch.cat([p[2] for p in poses]).contiguous()
     RT2inv = torch.cat([p[1] for p in poses]).contiguous()
     g = torch.Generator(device="cpu").manual_seed(seed)
     uniforms = torch.rand(V, 1024, generator=g).to(img.device)
-    out = model.outpaint_views(rep(img), rep(depth), rep(cam["K"]), rep(cam["Kinv"]), rep(cam["P"]), rep(cam["Pinv"]), RT2, RT2inv,
-                               None, temperature=temperature, uniforms=uniforms)
-    model.outpaint2.engine(32, 32, V).check()
-    sample = model.vqvae.decode_code(out["codes"])
-    frames = model.get_combined(out["gen_fs"], sample, out["background_mask"])
-    return dict(frames=frames, features=out["gen_fs"], background_mask=out["background_mask"], codes=out["codes"])
+
+    def run():
+        out = model.outpaint_views(rep(img), rep(depth), rep(cam["K"]), rep(cam["Kinv"]), rep(cam["P"]), rep(cam["Pinv"]), RT2, RT2inv,
+                                   None, temperature=temperature, uniforms=uniforms)
+        model.outpaint2.engine(32, 32, V).check()
+        sample = model.vqvae.decode_code(out["codes"])
+        frames = model.get_combined(out["gen_fs"], sample, out["background_mask"])
+        return dict(frames=frames, features=out["gen_fs"], background_mask=out["background_mask"], codes=out["codes"])
+    return checked(img.device, run)
 
 
 def scene_outputs_to_disk(outputs, directions, num_split, out_dir):
@@ -122,51 +127,54 @@ def _side_stream():
 @torch.no_grad()
 def render_pipelined(model, img, depth, cam, chunks, seeds, temperature=0.7):
     """render_views for several batches of poses (seeds: per batch, one seed per view), with the host half of batch i + 1 (splat on a side stream, masks back,
-    orders / masks / wavefront schedule, uploads) overlapped with the AR run of batch i.  -> list of frames (V_i,3,S,S)."""
-    main, side = torch.cuda.current_stream(), _side_stream()
+    orders / masks / wavefront schedule, uploads) overlapped with the AR run of batch i.  -> list of frames (V_i,3,S,S).  One scope of the
+    overflow guard, as render_views (on an exception the pipeline is reset: outpaint_reset)."""
+    def run():
+        main, side = torch.cuda.current_stream(), _side_stream()
 
-    def inputs(chunk):
-        V = len(chunk)
-        rep = lambda t: t.expand(V, *t.shape[1:]).contiguous()
-        return (rep(img), rep(depth), rep(cam["K"]), rep(cam["Kinv"]), rep(cam["P"]), rep(cam["Pinv"]),
-                torch.cat([p[2] for p in chunk]).contiguous(), torch.cat([p[1] for p in chunk]).contiguous())
-
-    frames, planned = [], None
-    # batches of one size (a trajectory cut into equal chunks): their AR runs overlap -- the narrow last wavefronts of a batch inside the
-    # launches of the next batch's first ones (outpaint_pipelined; the same codes); a batch then comes back one call late
-    overlap = len(chunks) > 1 and len({len(c) for c in chunks}) == 1 and len(chunks[0]) >= 2
-
-    def finish(out):
-        if out is not None:
-            sample = model.vqvae.decode_code(out["codes"])
-            frames.append(model.get_combined(out["gen_fs"], sample, out["background_mask"]))
-    try:
-        for k, chunk in enumerate(chunks):
-            if planned is None:
-                planned = model.plan_views(*inputs(chunk))
+        def inputs(chunk):
             V = len(chunk)
-            # the draws of a view are seeded by the VIEW (its index in the trajectory), not by where the sharding put it: a frame is
-            # the same picture on one GPU or eight
-            uniforms = torch.stack([torch.rand(1024, generator=torch.Generator(device="cpu").manual_seed(int(sd))) for sd in seeds[k]]).to(img.device)
-            out = (model.outpaint_pipelined if overlap else model.outpaint_planned)(planned, None, temperature=temperature, uniforms=uniforms)
-            planned = None
-            if k + 1 < len(chunks):
-                if k == 0:
-                    side.wait_stream(main)      # (the shared inputs were produced on the main stream)
-                with torch.cuda.stream(side):
-                    planned = model.plan_views(*inputs(chunks[k + 1]))
-                model.adopt_planned(planned, main)
-                main.wait_stream(side)
-            finish(out)
-        if overlap:
-            for out in model.outpaint_flush():
+            rep = lambda t: t.expand(V, *t.shape[1:]).contiguous()
+            return (rep(img), rep(depth), rep(cam["K"]), rep(cam["Kinv"]), rep(cam["P"]), rep(cam["Pinv"]),
+                    torch.cat([p[2] for p in chunk]).contiguous(), torch.cat([p[1] for p in chunk]).contiguous())
+
+        frames, planned = [], None
+        # batches of one size (a trajectory cut into equal chunks): their AR runs overlap -- the narrow last wavefronts of a batch inside the
+        # launches of the next batch's first ones (outpaint_pipelined; the same codes); a batch then comes back one call late
+        overlap = len(chunks) > 1 and len({len(c) for c in chunks}) == 1 and len(chunks[0]) >= 2
+
+        def finish(out):
+            if out is not None:
+                sample = model.vqvae.decode_code(out["codes"])
+                frames.append(model.get_combined(out["gen_fs"], sample, out["background_mask"]))
+        try:
+            for k, chunk in enumerate(chunks):
+                if planned is None:
+                    planned = model.plan_views(*inputs(chunk))
+                V = len(chunk)
+                # the draws of a view are seeded by the VIEW (its index in the trajectory), not by where the sharding put it: a frame is
+                # the same picture on one GPU or eight
+                uniforms = torch.stack([torch.rand(1024, generator=torch.Generator(device="cpu").manual_seed(int(sd))) for sd in seeds[k]]).to(img.device)
+                out = (model.outpaint_pipelined if overlap else model.outpaint_planned)(planned, None, temperature=temperature, uniforms=uniforms)
+                planned = None
+                if k + 1 < len(chunks):
+                    if k == 0:
+                        side.wait_stream(main)      # (the shared inputs were produced on the main stream)
+                    with torch.cuda.stream(side):
+                        planned = model.plan_views(*inputs(chunks[k + 1]))
+                    model.adopt_planned(planned, main)
+                    main.wait_stream(side)
                 finish(out)
-    except BaseException:
-        model.outpaint_reset()      # (a batch left in flight must not be merged into the next sequence's launches)
-        raise
-    if chunks:
-        model.outpaint2.engine(32, 32, len(chunks[-1])).check()
-    return frames
+            if overlap:
+                for out in model.outpaint_flush():
+                    finish(out)
+        except BaseException:
+            model.outpaint_reset()      # (a batch left in flight must not be merged into the next sequence's launches)
+            raise
+        if chunks:
+            model.outpaint2.engine(32, 32, len(chunks[-1])).check()
+        return frames
+    return checked(img.device, run)
 
 
 def save_png(path, chw):

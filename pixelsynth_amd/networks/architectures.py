@@ -7,8 +7,8 @@ Same constructor arguments, attribute / parameter names and shapes as the refere
 
   * NHWC (channels_last) on the GPU; inputs are converted on entry, results handed back NCHW-contiguous because the HIP kernels
     downstream take raw NCHW pointers;
-  * the DECODER's 3 x 3 convolutions are hand-written (csrc/conv_f16x3.hip: split-fp16 MFMA, fp32 in / out, the norm + ReLU in
-    front of them applied as the input is staged; csrc/conv_thin.hip for the 4 -> 64 and 128 -> 3 layers): 8.3 instead of 20 ms
+  * the DECODER's 3 x 3 convolutions are hand-written (csrc/conv_f16x3.hip through f16x3.py, which also owns its overflow guard: split-fp16
+    MFMA, fp32 in / out, the norm + ReLU in front applied as the input is staged; csrc/conv_thin.hip for the 4 -> 64 and 128 -> 3 layers): 8.3 instead of 20 ms
     per 16 views; its 1 x 1 projections run on the fp32 matrix pipe (csrc/conv1x1.hip, round 6).  PS_DECODER_CONV=fp32 /
     opt.decoder_conv = "fp32" sends them through torch.  The Unet's convolutions and the decoder's 3 -> 3 layer run through torch (MIOpen), the batch cut so that no call sees 2 GiB (MIOpen's fp32 NHWC
     kernels are silently wrong on 4 GiB activations -- 128 views of the decoder's widest layer);
@@ -26,6 +26,9 @@ import os
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
+
+from . import f16x3
+from .f16x3 import _FORCED_CONV, check_f16x3_overflow, decoder_conv, flag as _overflow_flag  # noqa: F401  (the names bench.py and the tests use)
 
 NOISE_SZ = 20
 
@@ -298,57 +301,13 @@ def _conv_split(conv, x, mode=None):
                            conv.out_channels, conv.stride[0]), conv.bias
 
 
-# ---- the wide 3 x 3 convolutions on the fp16 matrix pipe (csrc/conv_f16x3.hip) ------------------------------------------------
+# ---- the wide 3 x 3 convolutions on the fp16 matrix pipe (csrc/conv_f16x3.hip; packing, launch and overflow guard: f16x3.py) ---------
 DECODER_CONV = os.environ.get("PS_DECODER_CONV", "f16x3")   # "f16x3" | "fp32" (everything through torch / MIOpen)
-_FORCED_CONV = []    # decoder_conv(mode) in effect
-_overflow_flags = {}
 
 
 def _conv_mode(opt):
     """Which convolutions a decoder block takes: decoder_conv(...) in effect, else opt.decoder_conv, else PS_DECODER_CONV."""
     return _FORCED_CONV[-1] if _FORCED_CONV else (getattr(opt, "decoder_conv", None) or DECODER_CONV)
-
-
-class decoder_conv:
-    """with decoder_conv("fp32"): ... -- every decoder convolution inside through torch (MIOpen fp32), whatever the options say: how the
-    model reruns a pass whose split-fp16 convolutions met an activation beyond fp16's range."""
-
-    def __init__(self, mode):
-        if mode not in ("f16x3", "fp32"):
-            raise ValueError("decoder_conv: 'f16x3' or 'fp32'")
-        self.mode = mode
-
-    def __enter__(self):
-        _FORCED_CONV.append(self.mode)
-        return self
-
-    def __exit__(self, *exc):
-        _FORCED_CONV.pop()
-        return False
-
-
-def _overflow_flag(device):
-    key = str(device)
-    if key not in _overflow_flags:
-        _overflow_flags[key] = torch.zeros(1, dtype=torch.int32, device=device)
-    return _overflow_flags[key]
-
-
-def clear_f16x3_overflow(device):
-    """Asynchronous: forget what earlier passes left in the flag, so that the next check_f16x3_overflow speaks of the pass in between only."""
-    flag = _overflow_flags.get(str(device))
-    if flag is not None:
-        flag.zero_()
-
-
-def check_f16x3_overflow(device):
-    """Synchronises.  Raises if a split-fp16 convolution met an activation beyond fp16's range since the last call (its output is
-    then wrong); callers that can sit such activations out set PS_DECODER_CONV=fp32 / opt.decoder_conv = "fp32"."""
-    flag = _overflow_flags.get(str(device))
-    if flag is not None and int(flag.item()):
-        flag.zero_()
-        raise RuntimeError("refinement decoder: an activation beyond fp16's range (|v| > 65000, or not a number) reached a split-fp16 "
-                           "convolution; rerun with PS_DECODER_CONV=fp32")
 
 
 def _f16x3_takes(conv, x):
@@ -396,38 +355,26 @@ def _thin_conv(conv, x, scale=None, shift=None):
 
 
 def _f16x3_conv(conv, x, scale=None, shift=None, bias=None, res=None):
-    """conv(act(x)) WITHOUT the convolution's own bias through ps_conv3x3_f16x3_nhwc, act = max(x * scale - shift, 0) with scale /
-    shift (B, C) contiguous, or the identity; `bias` (Co) and `res` (an NHWC tensor of the output's shape) are added on the way out.
-    None when the kernel does not take this convolution (the caller then goes through torch)."""
+    """conv(act(x)) WITHOUT the convolution's own bias through the split-fp16 kernel (f16x3.conv3x3), act = max(x * scale - shift, 0)
+    with scale / shift (B, C) contiguous, or the identity; `bias` (Co) and `res` (an NHWC tensor of the output's shape) are added on the
+    way out.  None when the kernel does not take this convolution (the caller then goes through torch)."""
     if not _f16x3_takes(conv, x):
         return None
     weight = _plain_conv_weight(conv, x)
     if weight is None:
         return None
-    from .. import _lib
-    L = _lib.lib()
-    Co, Ci = conv.out_channels, conv.in_channels
     key = (weight.data_ptr(), weight._version, str(weight.device))
     cache = conv.__dict__.get("_ps_f16x3_cache")
     if cache is None or cache[0] != key:     # packed once per weight (with spectral norm in eval mode: per checkpoint, see _normalised_weight)
-        wl = weight.detach().permute(0, 2, 3, 1).contiguous()          # (Co, 3, 3, Ci): no copy for a channels_last weight
-        top = float(wl.abs().max())       # (synchronises -- once per weight) a weight fp16 cannot hold: this layer stays on torch
-        packed = None
-        if top == top and top < 6.0e4:
-            packed = torch.empty(L.ps_conv3x3_f16x3_packed_bytes(Co, Ci), dtype=torch.uint8, device=x.device)
-            _lib.check(L.ps_conv3x3_f16x3_pack(wl.data_ptr(), Co, Ci, packed.data_ptr(), _stream()), "ps_conv3x3_f16x3_pack")
-        cache = (key, packed, weight)      # (the weight is kept alive: its address is the key)
+        try:
+            packed = f16x3.pack3x3(weight.detach())
+        except ValueError:                   # a weight fp16 cannot hold: this layer stays on torch
+            packed = None
+        cache = (key, packed, weight)        # (the weight is kept alive: its address is the key)
         conv.__dict__["_ps_f16x3_cache"] = cache
-    packed = cache[1]
-    if packed is None:
+    if cache[1] is None or (res is not None and not (_is_nhwc_cuda(res) and res.shape == (x.size(0), conv.out_channels) + x.shape[2:])):
         return None
-    B, _, H, W = x.shape
-    y = _empty_nhwc(B, Co, H, W, x)
-    if res is not None and not (_is_nhwc_cuda(res) and res.shape == y.shape):
-        return None
-    _lib.check(L.ps_conv3x3_f16x3_nhwc(x.data_ptr(), _ptr(scale), _ptr(shift), packed.data_ptr(), _ptr(bias), _ptr(res), B, H, W, Ci, Co,
-                                       y.data_ptr(), _overflow_flag(x.device).data_ptr(), _stream()), "ps_conv3x3_f16x3_nhwc")
-    return y
+    return f16x3.conv3x3(x, cache[1], scale, shift, bias, res)
 
 
 def _sum_bias(*bs):

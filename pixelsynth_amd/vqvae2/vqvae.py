@@ -11,7 +11,9 @@ dec_t and the bottom quantiser, whose results the novel-view path discards).  On
 layers over space-to-depth blocks / towards depth-to-space blocks -- the 4 x 4 stride-2 convolutions and transposed convolutions run
 through csrc/conv_f16x3.hip (split-fp16 MFMA, fp32 in / out, ReLU applied as the patch is staged, bias on the way out), a ResBlock's
 tail (ReLU, 1 x 1, + the ReLU'd input) is one launch of csrc/conv1x1.hip; the 3-channel ends (3 -> 64, 64 -> 3) are csrc/vq_ends.hip.
-PS_VQVAE_CONV=fp32 (or networks.architectures.decoder_conv("fp32") in effect) sends everything through torch (MIOpen).
+A module whose layers break one of the kernels' rules goes through torch.  Each call of ``encode_codes`` / ``decode_code`` is one scope of
+the split-fp16 overflow guard (networks/f16x3.py: checked once, rerun in fp32 if an activation left fp16's range).
+PS_VQVAE_CONV=fp32 (or networks.f16x3.decoder_conv("fp32") in effect) sends everything through torch (MIOpen).
 Training (the EMA codebook update, :53-70) is out of scope.
 
 One reference quirk is part of the numerics: ResBlock starts with an *in-place* ReLU, so the residual it adds is
@@ -24,6 +26,7 @@ from torch import nn
 from torch.nn import functional as F
 
 from .. import _lib
+from ..networks.f16x3 import checked, conv3x3, forced_mode, pack3x3
 
 VQVAE_CONV = os.environ.get("PS_VQVAE_CONV", "f16x3")   # "f16x3" | "fp32" (every convolution through torch / MIOpen)
 
@@ -83,61 +86,44 @@ def convt_weight(wt):
 class _FastPath:
     """encode_codes / decode_code of a VQVAETop with the convolutions through csrc/conv_f16x3.hip and csrc/conv1x1.hip (module docstring).
     Built per (module, device) from the module's parameters as they are -- packed weights, padded biases -- and rebuilt when one of
-    them changes (storage or version counter)."""
+    them changes (storage or version counter).  Construction raises ValueError when a layer breaks one of the kernels' rules (channel
+    counts, a weight fp16 cannot hold): the module then goes through torch."""
 
     def __init__(self, m, device):
         self.device = device
-        self.key = self.key_of(m)
-        L = _lib.lib()
-        self.L = L
-
-        def layer3(w3, bias):
-            """(Co, Ci, 3, 3) fp32 + bias -> packed for ps_conv3x3_f16x3_nhwc, Co padded to a multiple of 64 with zero channels."""
-            Co, Ci = w3.shape[:2]
-            Cop = -(-Co // 64) * 64
-            if Ci % 32:
-                raise ValueError("VQ-VAE fast path: %d input channels" % Ci)
-            w = w3.new_zeros(Cop, Ci, 3, 3)
-            w[:Co] = w3
-            b = w3.new_zeros(Cop)
-            b[:Co] = bias
-            wl = w.permute(0, 2, 3, 1).contiguous()
-            top = float(wl.abs().max())
-            if not (top == top and top < 6.0e4):
-                raise ValueError("VQ-VAE fast path: a weight fp16 cannot hold")
-            packed = torch.empty(L.ps_conv3x3_f16x3_packed_bytes(Cop, Ci), dtype=torch.uint8, device=device)
-            _lib.check(L.ps_conv3x3_f16x3_pack(wl.data_ptr(), Cop, Ci, packed.data_ptr(), _lib.current_stream()), "ps_conv3x3_f16x3_pack")
-            return dict(packed=packed, Ci=Ci, Co=Cop, live=Co, bias=b.contiguous())
+        self.L = L = _lib.lib()
 
         def conv(c):
             return c.weight.detach().float(), c.bias.detach().float()
 
+        def conv1(c):
+            w, b = conv(c)
+            if not L.ps_conv1x1_takes(w.size(1), w.size(0)):
+                raise ValueError("VQ-VAE fast path: a %d -> %d 1 x 1 convolution" % (w.size(1), w.size(0)))
+            return w.reshape(w.size(0), w.size(1)).contiguous(), b.contiguous()
+
         def res(block):
-            c3, c1 = block.conv[1], block.conv[3]
-            w1, b1 = conv(c1)
-            return dict(c3=layer3(*conv(c3)), w1=w1.reshape(w1.size(0), w1.size(1)).contiguous(), b1=b1.contiguous(), mid=c3.out_channels)
+            w1, b1 = conv1(block.conv[3])
+            return dict(c3=pack3x3(*conv(block.conv[1])), w1=w1, b1=b1)
 
         with torch.no_grad():
             eb, et, dc = m.enc_b.blocks, m.enc_t.blocks, m.dec.blocks
             w, b = conv(eb[2])
-            self.e2 = layer3(s2d_weight(w), b)
-            self.e3 = layer3(*conv(eb[4]))
+            self.e2 = pack3x3(s2d_weight(w), b)
+            self.e3 = pack3x3(*conv(eb[4]))
             self.eb_res = [res(eb[5]), res(eb[6])]
             w, b = conv(et[0])
-            self.t1 = layer3(s2d_weight(w), b)
+            self.t1 = pack3x3(s2d_weight(w), b, s2d=True)
             self.t1_out = et[0].out_channels
-            self.t2 = layer3(*conv(et[2]))
+            self.t2 = pack3x3(*conv(et[2]))
             self.et_res = [res(et[3]), res(et[4])]
-            wq, bq = conv(m.quantize_conv_t)
-            self.wq, self.bq = wq.reshape(wq.size(0), wq.size(1)).contiguous(), bq.contiguous()
+            self.wq, self.bq = conv1(m.quantize_conv_t)
             w, b = conv(m.upsample_t)
-            self.up = layer3(convt_weight(w), b.repeat(4))
-            self.up_out = m.upsample_t.out_channels
-            self.d1 = layer3(*conv(dc[0]))
+            self.up = pack3x3(convt_weight(w), b.repeat(4), d2s=True)
+            self.d1 = pack3x3(*conv(dc[0]))
             self.dc_res = [res(dc[1]), res(dc[2])]
             w, b = conv(dc[4])
-            self.d2 = layer3(convt_weight(w), b.repeat(4))
-            self.d2_out = dc[4].out_channels
+            self.d2 = pack3x3(convt_weight(w), b.repeat(4), d2s=True)
             # the 3-channel ends (csrc/vq_ends.hip) where they are the shapes it is written for; otherwise torch
             self.ends = (tuple(eb[0].weight.shape) == (64, 3, 4, 4) and tuple(dc[6].weight.shape) == (64, 3, 4, 4)
                          and eb[0].bias is not None and dc[6].bias is not None)
@@ -156,7 +142,6 @@ class _FastPath:
         try:
             eb, et, dc = m.enc_b.blocks, m.enc_t.blocks, m.dec.blocks
             ok = (len(eb) == 8 and len(et) == 6 and len(dc) == 7 and H % 128 == 0 and W % 128 == 0
-                  and eb[2].in_channels % 8 == 0 and et[0].in_channels % 8 == 0 and eb[5].conv[1].out_channels in (32, 64, 128, 256)
                   and all(isinstance(c, nn.Conv2d) for c in (eb[0], eb[2], eb[4], et[0], et[2]))
                   and all(isinstance(c, nn.ConvTranspose2d) for c in (m.upsample_t, dc[4], dc[6])))
             return bool(ok)
@@ -170,27 +155,15 @@ class _FastPath:
             self.zeros[(B, C)] = torch.zeros(B, C, device=self.device)
         return self.ones[(B, C)], self.zeros[(B, C)]
 
-    def conv3(self, x, layer, relu_in, s2d=False, d2s=False):
-        """The layer on x (B, C, H, W) channels_last.  s2d: x is the tensor BEFORE the space-to-depth step -- (B, Ci / 4, 2 H, 2 W) -- and the
-        kernel reads it in that form; d2s: the result leaves as (B, Co / 4, 2 H, 2 W), the depth-to-space step done by the stores."""
-        from ..networks.architectures import _overflow_flag, _empty_nhwc
-        B, C, H, W = x.shape
-        if s2d:
-            C, H, W = 4 * C, H // 2, W // 2
-        assert C == layer["Ci"] and x.is_contiguous(memory_format=torch.channels_last)
-        y = _empty_nhwc(B, layer["Co"] // 4, 2 * H, 2 * W, x) if d2s else _empty_nhwc(B, layer["Co"], H, W, x)
-        sc, sh = self._act(B, C) if relu_in else (None, None)
-        p = lambda t: None if t is None else t.data_ptr()
-        _lib.check(self.L.ps_conv3x3_f16x3_ex_nhwc(x.data_ptr(), p(sc), p(sh), layer["packed"].data_ptr(), layer["bias"].data_ptr(), None, B, H, W,
-                                                   C, layer["Co"], layer["live"], int(s2d), int(d2s), y.data_ptr(), _overflow_flag(x.device).data_ptr(),
-                                                   _lib.current_stream()), "ps_conv3x3_f16x3_ex_nhwc")
-        return y
+    def conv3(self, x, layer, relu_in):
+        """The layer on x channels_last through f16x3.conv3x3 (a layer packed for s2d reads x BEFORE the space-to-depth step; one packed
+        for d2s leaves its result after the depth-to-space step, done by the stores)."""
+        return conv3x3(x, layer, *(self._act(x.size(0), layer["Ci"]) if relu_in else ()))
 
     def conv1(self, x, ldx, w, bias, res, flags):
-        from ..networks.architectures import _empty_nhwc
         B, _, H, W = x.shape
         Co, Ci = w.shape
-        y = _empty_nhwc(B, Co, H, W, x)
+        y = torch.empty((B, Co, H, W), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
         _lib.check(self.L.ps_conv1x1_ex_nhwc_f32(x.data_ptr(), ldx, w.data_ptr(), bias.data_ptr(), None if res is None else res.data_ptr(), flags,
                                                  B * H * W, Ci, Co, y.data_ptr(), _lib.current_stream()), "ps_conv1x1_ex_nhwc_f32")
         return y
@@ -216,7 +189,7 @@ class _FastPath:
         h = self.conv3(h, self.e3, True)
         for r in self.eb_res:
             h = self.res(h, r)
-        h = self.conv3(h, self.t1, True, s2d=True)                     # (the trailing ReLU of enc_b on the way in; 2 x 2 blocks read in place)
+        h = self.conv3(h, self.t1, True)                               # (the trailing ReLU of enc_b on the way in; 2 x 2 blocks read in place)
         if h.size(1) != self.t1_out:
             h = h[:, :self.t1_out].contiguous(memory_format=torch.channels_last)
         h = self.conv3(h, self.t2, True)
@@ -229,11 +202,11 @@ class _FastPath:
         """quant (B, H, W, embed_dim) contiguous -> image (B, 3, 8 H, 8 W)."""
         dc = m.dec.blocks
         q = quant_nhwc.permute(0, 3, 1, 2)
-        h = self.conv3(q, self.up, False, d2s=True)                    # (the four output parities stored where they belong)
+        h = self.conv3(q, self.up, False)                              # (the four output parities stored where they belong)
         h = self.conv3(h, self.d1, False)
         for r in self.dc_res:
             h = self.res(h, r)
-        h = self.conv3(h, self.d2, True, d2s=True)
+        h = self.conv3(h, self.d2, True)
         if self.ends:                                                  # ReLU, 64 -> 3 at twice the size: the image, NCHW
             B, _, Hh, Wh = h.shape
             img = torch.empty(B, 3, 2 * Hh, 2 * Wh, device=h.device)
@@ -364,34 +337,26 @@ class VQVAETop(nn.Module):
 
     @torch.no_grad()
     def encode_codes(self, input):
-        """(B,3,256,256) -> top codes (B,32,32) int32, on the device (= ``encode(input)[3]``, z_buffermodel.py:345)."""
+        """(B,3,256,256) -> top codes (B,32,32) int32, on the device (= ``encode(input)[3]``, z_buffermodel.py:345).  One guarded scope
+        (networks/f16x3.checked: synchronises, the codes steer everything that follows)."""
+        return checked(input.device, lambda: self._encode_codes(input))
+
+    def _encode_codes(self, input):
         n = self._views_per_call(input.size(2), input.size(3)) if input.is_cuda else input.size(0)
         if input.size(0) > n:
-            return torch.cat([self.encode_codes(input[i:i + n]) for i in range(0, input.size(0), n)])
+            return torch.cat([self._encode_codes(input[i:i + n]) for i in range(0, input.size(0), n)])
         fast = self._fast(input, input.size(2), input.size(3))
         if fast is not None:
-            from ..networks.architectures import check_f16x3_overflow, clear_f16x3_overflow, decoder_conv
-            clear_f16x3_overflow(input.device)
             lat = fast.encode_latent(self, input.float())            # (B, 32, 32, 64)
             B, H, W, D = lat.shape
-            codes = self.quantize_t.nearest(lat.reshape(-1, D), 0).view(B, H, W)
-            try:
-                check_f16x3_overflow(input.device)                   # (synchronises: the codes steer everything that follows)
-                return codes
-            except RuntimeError as err:
-                import warnings
-                warnings.warn(f"VQ-VAE encoder: {err}: run again in fp32")
-                with decoder_conv("fp32"):
-                    return self.encode_codes(input)
+            return self.quantize_t.nearest(lat.reshape(-1, D), 0).view(B, H, W)
         lat = self.quantize_conv_t(self.enc_t(self.enc_b(input)))  # (B,64,32,32)
         B, _, H, W = lat.shape
         return self.quantize_t.nearest(lat.float(), 1, H * W).view(B, H, W)
 
     def _fast(self, t, H, W):
         """The hand-written path for a float32 CUDA call on (H, W) images in eval mode, or None (module docstring)."""
-        from ..networks import architectures as A
-        mode = A._FORCED_CONV[-1] if A._FORCED_CONV else VQVAE_CONV
-        if (mode != "f16x3" or not t.is_cuda or self.training or torch.is_grad_enabled() or not _FastPath.takes(self, H, W)
+        if ((forced_mode() or VQVAE_CONV) != "f16x3" or not t.is_cuda or self.training or torch.is_grad_enabled() or not _FastPath.takes(self, H, W)
                 or any(p.dtype != torch.float32 or p.device != t.device for p in self.parameters())):
             return None
         key = (str(t.device), _FastPath.key_of(self))
@@ -406,12 +371,15 @@ class VQVAETop(nn.Module):
 
     @torch.no_grad()
     def decode_code(self, code_t):
-        """codes (B,32,32) int -> image (B,3,256,256) (vqvae.py:305-311, z_buffermodel.py:250)."""
+        """codes (B,32,32) int -> image (B,3,256,256) (vqvae.py:305-311, z_buffermodel.py:250).  One guarded scope, as encode_codes."""
+        return checked(code_t.device, lambda: self._decode_code(code_t))
+
+    def _decode_code(self, code_t):
         n = self._views_per_call(8 * code_t.size(-2), 8 * code_t.size(-1)) if code_t.is_cuda else code_t.size(0)
         if code_t.size(0) > n:
-            return torch.cat([self.decode_code(code_t[i:i + n]) for i in range(0, code_t.size(0), n)])
+            return torch.cat([self._decode_code(code_t[i:i + n]) for i in range(0, code_t.size(0), n)])
         fast = self._fast(code_t, 8 * code_t.size(-2), 8 * code_t.size(-1))
-        if fast is not None:    # (split-fp16 convolutions: the caller's overflow check -- z_buffermodel._decode_checked -- covers them)
+        if fast is not None:
             return fast.decode(self, self.quantize_t.embed_code(code_t))
         return self.decode(self.quantize_t.embed_grid(code_t))
 

@@ -23,7 +23,7 @@ from .ar_plan import ARPlan, build_ar_plan, plan_from_reference_args
 from .lmconv.layers import PONO
 from .lmconv.model import TP_MIN_FRAMES, LaunchPipeline, OurPixelCNN, launch_capacity, wavefronts
 from .lmconv.sample import sample
-from .networks.architectures import check_f16x3_overflow, clear_f16x3_overflow, decoder_conv
+from .networks.f16x3 import checked
 from .projection.z_buffer_manipulator import PtsManipulator
 
 _PREFIX_STREAMS = {}    # (device, n) -> the prefix pass's side streams (ZbufferModelPts._prefix_streams)
@@ -457,7 +457,7 @@ class ZbufferModelPts(nn.Module):
         out = self.outpaint_planned(planned, None, self.opt.temperature if temperature is None else temperature, uniforms)
         if check:
             self.outpaint2.engine(self.obs[1], self.obs[2], K.shape[0]).check()
-        pred = (self._decode_checked if check else self._decode_candidate)(out["gen_fs"], out["background_mask"], out["codes"])
+        pred = self._decode_checked(out["gen_fs"], out["background_mask"], out["codes"], check)
         return dict(PredImg=pred, FeaturesImg=out["gen_fs"], background_mask=out["background_mask"], codes=out["codes"],
                     depth=depth_src, plan=out["plan"])
 
@@ -523,39 +523,18 @@ class ZbufferModelPts(nn.Module):
         probs = np.sort(probs)[::-1]
         return float(-np.sum(probs * np.log(probs)))
 
-    def _decode_candidate(self, gen_fs, background_mask, codes):
-        """codes (B,32,32) -> image: decode, blend with the reprojected features (a14), refine if a projector exists."""
-        combined = self.get_combined(gen_fs, self.vqvae.decode_code(codes), background_mask)
-        return combined if self.projector is None else self.projector(combined, background_mask)
+    def _decode_checked(self, gen_fs, background_mask, codes, check=True):
+        """codes (B,32,32) -> image: decode, blend with the reprojected features (a14), refine -- one scope of the split-fp16 overflow guard
+        (networks/f16x3.checked; check=False: unchecked).  Every image that is returned, ranked or fed into the next frame of a chain goes
+        through here.  Weights under spectral norm behind normalisation layers do not overflow; a checkpoint that does should set
+        opt.decoder_conv = "fp32" and save itself the first attempt."""
+        return checked(gen_fs.device, lambda: self._project_checked(self.get_combined(gen_fs, self.vqvae.decode_code(codes), background_mask),
+                                                                    background_mask), check)
 
-    def _run_checked(self, device, fn):
-        """fn() -- any pass through the refinement decoder -- then (synchronising) the question whether one of ITS split-fp16 convolutions
-        met an activation beyond fp16's range (csrc/conv_f16x3.hip raises a device flag; the image is then wrong): if so the pass is run
-        again with every convolution through torch in fp32, with a warning.  The flag is cleared BEFORE the pass (what an earlier,
-        unchecked pass left there is not this one's) and by the check.  Weights under spectral norm behind normalisation layers do not
-        get there; a checkpoint that does should set opt.decoder_conv = "fp32" and save itself the first attempt."""
-        clear_f16x3_overflow(device)
-        out = fn()
-        try:
-            check_f16x3_overflow(device)
-        except RuntimeError as err:
-            import warnings
-            warnings.warn(f"{err}: the decoder pass is run again in fp32")
-            with decoder_conv("fp32"):
-                out = fn()
-        return out
-
-    def _decode_checked(self, gen_fs, background_mask, codes):
-        """_decode_candidate behind the overflow check of _run_checked: every image that is returned, ranked or fed into the next frame
-        of a chain goes through here."""
-        return self._run_checked(gen_fs.device, lambda: self._decode_candidate(gen_fs, background_mask, codes))
-
-    def _project_checked(self, gen_fs, *mask):
-        """The no_outpainting form: the refinement decoder on the reprojected features alone (z_buffermodel.py:383-384; the chained mode
-        calls it without the mask argument), checked likewise."""
-        if self.projector is None:
-            return gen_fs
-        return self._run_checked(gen_fs.device, lambda: self.projector(gen_fs, *mask))
+    def _project_checked(self, x, *mask):
+        """The refinement decoder, if the model has one, as a guarded scope; the no_outpainting form runs it on the reprojected features
+        alone (z_buffermodel.py:383-384; the chained mode calls it without the mask argument)."""
+        return x if self.projector is None else checked(x.device, lambda: self.projector(x, *mask))
 
     @torch.no_grad()
     def get_best_sample(self, *args, uniforms=None, shard=False):

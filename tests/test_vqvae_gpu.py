@@ -228,6 +228,23 @@ def test_encoder_runs_again_in_fp32_when_an_activation_leaves_fp16s_range():
     A.check_f16x3_overflow(img.device)          # (left clear)
 
 
+@pytest.mark.parametrize("kw", [dict(embed_dim=32), dict(channel=64), dict(n_res_channel=48)])
+def test_modules_the_kernels_do_not_take_go_through_torch(monkeypatch, kw):
+    """A VQVAETop with a layer the kernels do not take -- a depth-to-space output of 32 channels (embed_dim 32, channel 64), a 1 x 1
+    convolution of 48 inputs (n_res_channel 48) -- builds no fast path: encode_codes and decode_code run and give what the torch path
+    (PS_VQVAE_CONV=fp32) gives."""
+    from pixelsynth_amd.vqvae2 import vqvae as V
+    torch.manual_seed(4)
+    m = V.VQVAETop(**kw).eval().cuda()
+    img = dev(syn.image(4, 2, 3, 256))
+    with torch.no_grad():
+        codes = m.encode_codes(img)
+        image = m.decode_code(codes)
+        assert m._fast(img, 256, 256) is None and image.shape == (2, 3, 256, 256)
+        monkeypatch.setattr(V, "VQVAE_CONV", "fp32")
+        assert torch.equal(m.encode_codes(img), codes) and torch.equal(m.decode_code(codes), image)
+
+
 def test_large_batches_are_cut_per_call(monkeypatch):
     """VQVAETop.encode_codes / decode_code and Unet.forward cut a batch beyond MAX_BATCH into several calls (MIOpen's fp32 kernels
     index wrongly from 2 GiB activations on: networks/architectures.py:_conv2d_batches).  With MAX_BATCH lowered to 2, five views

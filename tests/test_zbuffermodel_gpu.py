@@ -356,6 +356,36 @@ def test_driver_renders_a_trajectory_and_writes_the_video_layout(tmp_path):
     np.testing.assert_allclose(sweep[-1][2].cpu().numpy(), syn.yaw_pose(syn.demo_cameras(1)["P"], 0.6)[1], rtol=1e-6, atol=1e-6)
 
 
+def test_an_overflow_in_the_middle_of_a_pipelined_render_runs_it_again_in_fp32(monkeypatch):
+    """driver.render_pipelined is one scope of the split-fp16 overflow guard (networks/f16x3.checked): a flag raised in the VQ-VAE decode
+    of its second batch gives a warning and the frames of the same render under decoder_conv("fp32"); the rerun takes no split-fp16 path."""
+    from pixelsynth_amd import driver
+    from pixelsynth_amd.networks import f16x3
+    from pixelsynth_amd.vqvae2 import vqvae as V
+    m = driver.build_model(torch.device(DEV))
+    img, depth = tt(syn.image(1000, 1, 3, 256)), tt(syn.depth_smooth(2000, 1, 256, 1.0, 100.0))
+    cam = {k: tt(v) for k, v in syn.demo_cameras(1).items()}
+    poses = driver.trajectory(m, cam["P"], "circle", 6)
+    chunks, seeds = [poses[:3], poses[3:]], [[1000, 1001, 1002], [1003, 1004, 1005]]
+    with f16x3.decoder_conv("fp32"):
+        want = driver.render_pipelined(m, img, depth, cam, chunks, seeds)
+    calls = []
+    real = V._FastPath.decode
+
+    def spy(self, *a, **k):
+        y = real(self, *a, **k)
+        calls.append(1)
+        if len(calls) == 2:
+            f16x3.flag(y.device).fill_(1)               # as the kernel would
+        return y
+    monkeypatch.setattr(V._FastPath, "decode", spy)
+    with pytest.warns(UserWarning, match="run again in fp32"):
+        got = driver.render_pipelined(m, img, depth, cam, chunks, seeds)
+    assert len(calls) == 2 and len(got) == len(want) == 2
+    assert all(torch.equal(a, b) for a, b in zip(got, want))
+    f16x3.check_f16x3_overflow(img.device)               # (cleared by the guard)
+
+
 def test_driver_chained_scene_writes_scene_and_video_layout(tmp_path):
     """--scene: forward_scene on one GPU, files in the reference's save_scene / save_video layout (demo.py:100-164)."""
     from pixelsynth_amd import driver
