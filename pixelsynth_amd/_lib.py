@@ -1,11 +1,14 @@
 """ctypes binding of libpixelsynth_hip.so (the C ABI declared in include/pixelsynth_hip.h; the measurement / tuning / debugging
 entry points tests, bench.py and tools use are declared in include/pixelsynth_hip_debug.h).
 
-The product path has NO fallback: if the shared library is missing or a call fails, a RuntimeError
-is raised.  Nothing here (or anywhere under pixelsynth_amd/) imports oracle/.
+The package calls the library through call() alone.  The product path has NO fallback: if the shared library is missing or a call
+fails, a RuntimeError is raised.  Nothing here (or anywhere under pixelsynth_amd/) imports oracle/.
 """
 import ctypes
 import os
+
+import numpy as np
+import torch   # (before the library is loaded: see lib())
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PS_HIP_LIB") or os.path.join(_HERE, "libpixelsynth_hip.so")   # (PS_HIP_LIB: tuning builds)
@@ -13,6 +16,9 @@ _lib = None
 
 c_void_p, c_int, c_float, c_double, c_size_t = (ctypes.c_void_p, ctypes.c_int, ctypes.c_float,
                                                  ctypes.c_double, ctypes.c_size_t)
+# Stand-ins of the table below.  RC as the restype: an int status, 0 = success (ps_last_error() says why not).  STREAM as the last
+# parameter: the void *stream the call is queued on, which call() appends.  Both are declared to ctypes as c_int / c_void_p.
+RC, STREAM = object(), object()
 
 _PROTOS = {
     "ps_abi_version": (c_int, []),
@@ -20,73 +26,73 @@ _PROTOS = {
     "ps_build_info": (ctypes.c_char_p, []),
     "ps_pixelcnn_launch_kinds": (c_int, []),
     "ps_pixelcnn_launch_kind_name": (ctypes.c_char_p, [c_int]),
-    "ps_pixelcnn_launch_counts": (c_int, [c_void_p, c_void_p, c_int]),
-    "ps_pixelcnn_profile_begin": (c_int, [c_void_p]),
-    "ps_pixelcnn_profile_end": (c_int, [c_void_p, c_int, c_void_p, c_void_p]),
-    "ps_project_pts_f32": (c_int, [c_void_p] * 5 + [c_int, c_int, c_void_p, c_void_p]),
-    "ps_project_pts_cumulative_f32": (c_int, [c_void_p] * 8 + [c_int] * 4 + [c_void_p] * 3),
+    "ps_pixelcnn_launch_counts": (RC, [c_void_p, c_void_p, c_int]),
+    "ps_pixelcnn_profile_begin": (RC, [c_void_p]),
+    "ps_pixelcnn_profile_end": (RC, [c_void_p, c_int, c_void_p, c_void_p]),
+    "ps_project_pts_f32": (RC, [c_void_p] * 5 + [c_int, c_int, c_void_p, STREAM]),
+    "ps_project_pts_cumulative_f32": (RC, [c_void_p] * 8 + [c_int] * 4 + [c_void_p] * 2 + [STREAM]),
     "ps_splat_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_double]),
-    "ps_splat_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_double, c_int, c_float, c_int,
-                             c_int, c_int] + [c_void_p] * 6 + [c_size_t, c_void_p]),
-    "ps_project_splat_f32": (c_int, [c_void_p] * 6 + [c_int, c_int, c_int, c_double, c_int, c_float, c_int, c_int,
-                                                      c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "ps_generation_order": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
-    "ps_ar_plan": (c_int, [c_void_p, c_int, c_int, c_int] + [c_void_p] * 6),
-    "ps_order_masks_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "ps_read_status": (c_int, [c_void_p, c_void_p]),
-    "ps_custom_order": (c_int, [c_int, c_int, c_void_p, c_void_p]),
-    "ps_kernel_masks_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "ps_splat_f32": (RC, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_double, c_int, c_float, c_int,
+                          c_int, c_int] + [c_void_p] * 6 + [c_size_t, STREAM]),
+    "ps_project_splat_f32": (RC, [c_void_p] * 6 + [c_int, c_int, c_int, c_double, c_int, c_float, c_int, c_int,
+                                                   c_int, c_void_p, c_void_p, c_void_p, c_size_t, STREAM]),
+    "ps_generation_order": (RC, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "ps_ar_plan": (RC, [c_void_p, c_int, c_int, c_int] + [c_void_p] * 6),
+    "ps_order_masks_f32": (RC, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, STREAM]),
+    "ps_read_status": (RC, [c_void_p, STREAM]),
+    "ps_custom_order": (RC, [c_int, c_int, c_void_p, c_void_p]),
+    "ps_kernel_masks_f32": (RC, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "ps_lmconv_workspace_bytes": (c_size_t, [c_int] * 5),
-    "ps_lmconv_forward_f32": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
-                                      c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "ps_pixelcnn_create": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "ps_lmconv_forward_f32": (RC, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                                   c_int, c_int, c_void_p, c_void_p, c_size_t, STREAM]),
+    "ps_pixelcnn_create": (RC, [c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "ps_pixelcnn_destroy": (None, [c_void_p]),
-    "ps_pixelcnn_forward_f32": (c_int, [c_void_p] * 5 + [c_int, c_void_p, c_void_p]),
-    "ps_pixelcnn_ar_run": (c_int, [c_void_p] * 9 + [c_float, c_int, c_int, c_void_p, c_void_p]),
-    "ps_pixelcnn_ar_run_waves": (c_int, [c_void_p] * 9 + [c_float, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
-    "ps_pixelcnn_ar_prefix": (c_int, [c_void_p] * 7 + [c_int, c_int, c_int, c_int, c_void_p]),
-    "ps_pixelcnn_ar_prefix_frames": (c_int, [c_void_p] * 7 + [c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
-    "ps_pixelcnn_ar_columns": (c_int, [c_void_p] * 9 + [c_float, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p]),
-    "ps_pixelcnn_set_compute_units": (c_int, [c_void_p, c_int]),
-    "ps_stream_create_cu_range": (c_int, [c_int, c_int, c_void_p]),
-    "ps_stream_destroy": (c_int, [c_void_p]),
-    "ps_pixelcnn_time_ar_run_waves": (c_int, [c_void_p] * 8 + [c_float, c_int, c_int, c_void_p, c_void_p, c_int] + [c_void_p] * 4),
-    "ps_pixelcnn_time_ar_run_waves_range": (c_int, [c_void_p] * 8 + [c_float, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int] + [c_void_p] * 4),
-    "ps_ar_wavefronts": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
-    "ps_ar_wavefronts_capped": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
-    "ps_ar_wavefronts_frames": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
-    "ps_pixelcnn_status": (c_int, [c_void_p, c_void_p]),
+    "ps_pixelcnn_forward_f32": (RC, [c_void_p] * 5 + [c_int, c_void_p, STREAM]),
+    "ps_pixelcnn_ar_run": (RC, [c_void_p] * 9 + [c_float, c_int, c_int, c_void_p, STREAM]),
+    "ps_pixelcnn_ar_run_waves": (RC, [c_void_p] * 9 + [c_float, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, STREAM]),
+    "ps_pixelcnn_ar_prefix": (RC, [c_void_p] * 7 + [c_int, c_int, c_int, c_int, STREAM]),
+    "ps_pixelcnn_ar_prefix_frames": (RC, [c_void_p] * 7 + [c_int, c_void_p, c_int, c_int, c_int, c_int, STREAM]),
+    "ps_pixelcnn_ar_columns": (RC, [c_void_p] * 9 + [c_float, c_int, c_int, c_void_p, c_void_p, c_int, STREAM]),
+    "ps_pixelcnn_set_compute_units": (RC, [c_void_p, c_int]),
+    "ps_stream_create_cu_range": (RC, [c_int, c_int, c_void_p]),
+    "ps_stream_destroy": (RC, [STREAM]),     # (the stream to destroy: call it with stream=)
+    "ps_pixelcnn_time_ar_run_waves": (RC, [c_void_p] * 8 + [c_float, c_int, c_int, c_void_p, c_void_p, c_int] + [c_void_p] * 3 + [STREAM]),
+    "ps_pixelcnn_time_ar_run_waves_range": (RC, [c_void_p] * 8 + [c_float, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int] + [c_void_p] * 3 + [STREAM]),
+    "ps_ar_wavefronts": (RC, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "ps_ar_wavefronts_capped": (RC, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "ps_ar_wavefronts_frames": (RC, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    "ps_pixelcnn_status": (RC, [c_void_p, STREAM]),
     "ps_pixelcnn_debug_cache": (c_void_p, [c_void_p, c_int, c_int]),
-    "ps_pixelcnn_set_tuning": (c_int, [c_void_p, ctypes.c_char_p, c_int]),
-    "ps_pixelcnn_get_tuning": (c_int, [c_void_p, ctypes.c_char_p, c_void_p]),
-    "ps_zbuffer_scatter_f32": (c_int, [c_void_p] * 4 + [c_int] * 4 + [c_void_p] * 4),
-    "ps_zbuffer_project_f32": (c_int, [c_void_p] * 6 + [c_int, c_int] + [c_void_p] * 5),
-    "ps_zbuffer_scatter_sorted_f32": (c_int, [c_void_p] * 5 + [c_int] * 4 + [c_void_p] * 4),
-    "ps_vq_nearest_f32": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
-    "ps_vq_embed_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
-    "ps_affine_relu_nhwc_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
-    "ps_pool_add_nhwc_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
-    "ps_pool_add_post_nhwc_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
-    "ps_upsample_add_nhwc_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
-    "ps_add_bias_nhwc_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
-    "ps_cat_mask_nhwc_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
-    "ps_noise_affine_f32": (c_int, [c_void_p] * 6 + [ctypes.c_float, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
-    "ps_conv3x3_thin_in_nhwc_f32": (c_int, [c_void_p] * 4 + [c_int] * 4 + [c_void_p, c_void_p]),
-    "ps_conv3x3_thin_in_f16x3_nhwc": (c_int, [c_void_p] * 4 + [c_int] * 4 + [c_void_p, c_void_p, c_void_p]),
-    "ps_conv3x3_thin_out_nhwc_f32": (c_int, [c_void_p] * 4 + [c_int] * 5 + [c_void_p, c_void_p]),
-    "ps_vq_stem_s2d_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
-    "ps_vq_head_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "ps_pixelcnn_set_tuning": (RC, [c_void_p, ctypes.c_char_p, c_int]),
+    "ps_pixelcnn_get_tuning": (RC, [c_void_p, ctypes.c_char_p, c_void_p]),
+    "ps_zbuffer_scatter_f32": (RC, [c_void_p] * 4 + [c_int] * 4 + [c_void_p] * 3 + [STREAM]),
+    "ps_zbuffer_project_f32": (RC, [c_void_p] * 6 + [c_int, c_int] + [c_void_p] * 4 + [STREAM]),
+    "ps_zbuffer_scatter_sorted_f32": (RC, [c_void_p] * 5 + [c_int] * 4 + [c_void_p] * 3 + [STREAM]),
+    "ps_vq_nearest_f32": (RC, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, STREAM]),
+    "ps_vq_embed_f32": (RC, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, STREAM]),
+    "ps_affine_relu_nhwc_f32": (RC, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, STREAM]),
+    "ps_pool_add_nhwc_f32": (RC, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, STREAM]),
+    "ps_pool_add_post_nhwc_f32": (RC, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, STREAM]),
+    "ps_upsample_add_nhwc_f32": (RC, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, STREAM]),
+    "ps_add_bias_nhwc_f32": (RC, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, STREAM]),
+    "ps_cat_mask_nhwc_f32": (RC, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, STREAM]),
+    "ps_noise_affine_f32": (RC, [c_void_p] * 6 + [ctypes.c_float, c_int, c_int, c_int, c_void_p, c_void_p, STREAM]),
+    "ps_conv3x3_thin_in_nhwc_f32": (RC, [c_void_p] * 4 + [c_int] * 4 + [c_void_p, STREAM]),
+    "ps_conv3x3_thin_in_f16x3_nhwc": (RC, [c_void_p] * 4 + [c_int] * 4 + [c_void_p, c_void_p, STREAM]),
+    "ps_conv3x3_thin_out_nhwc_f32": (RC, [c_void_p] * 4 + [c_int] * 5 + [c_void_p, STREAM]),
+    "ps_vq_stem_s2d_f32": (RC, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, STREAM]),
+    "ps_vq_head_f32": (RC, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, STREAM]),
     "ps_conv1x1_takes": (c_int, [c_int, c_int]),
-    "ps_conv1x1_nhwc_f32": (c_int, [c_void_p, c_void_p, ctypes.c_size_t, c_int, c_int, c_void_p, c_void_p]),
-    "ps_conv1x1_ex_nhwc_f32": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, ctypes.c_size_t, c_int, c_int, c_void_p, c_void_p]),
+    "ps_conv1x1_nhwc_f32": (RC, [c_void_p, c_void_p, ctypes.c_size_t, c_int, c_int, c_void_p, STREAM]),
+    "ps_conv1x1_ex_nhwc_f32": (RC, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, ctypes.c_size_t, c_int, c_int, c_void_p, STREAM]),
     "ps_conv3x3_f16x3_packed_bytes": (ctypes.c_size_t, [c_int, c_int]),
-    "ps_conv3x3_f16x3_pack": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
-    "ps_conv3x3_f16x3_nhwc": (c_int, [c_void_p] * 6 + [c_int] * 5 + [c_void_p, c_void_p, c_void_p]),
-    "ps_conv3x3_f16x3_ex_nhwc": (c_int, [c_void_p] * 6 + [c_int] * 8 + [c_void_p, c_void_p, c_void_p]),
-    "ps_pixelcnn_time_column_step": (c_int, [c_void_p] * 6 + [c_int, c_int, c_int] + [c_void_p] * 5),
-    "ps_pixelcnn_ar_step": (c_int, [c_void_p] * 6 + [c_int, c_int, c_int, c_void_p, c_void_p]),
+    "ps_conv3x3_f16x3_pack": (RC, [c_void_p, c_int, c_int, c_void_p, STREAM]),
+    "ps_conv3x3_f16x3_nhwc": (RC, [c_void_p] * 6 + [c_int] * 5 + [c_void_p, c_void_p, STREAM]),
+    "ps_conv3x3_f16x3_ex_nhwc": (RC, [c_void_p] * 6 + [c_int] * 8 + [c_void_p, c_void_p, STREAM]),
+    "ps_pixelcnn_time_column_step": (RC, [c_void_p] * 6 + [c_int, c_int, c_int] + [c_void_p] * 4 + [STREAM]),
+    "ps_pixelcnn_ar_step": (RC, [c_void_p] * 6 + [c_int, c_int, c_int, c_void_p, STREAM]),
     "ps_image_metrics_workspace_bytes": (c_size_t, [c_int] * 4),
-    "ps_image_metrics": (c_int, [c_void_p] * 4 + [c_int, c_void_p] + [c_int] * 4 + [c_void_p, c_void_p, c_size_t, c_void_p]),
+    "ps_image_metrics": (RC, [c_void_p] * 4 + [c_int, c_void_p] + [c_int] * 4 + [c_void_p, c_void_p, c_size_t, STREAM]),
 }
 
 
@@ -102,16 +108,15 @@ def lib():
             raise RuntimeError(
                 f"{LIB_PATH} is missing: build it with `python -m pixelsynth_amd.build` "
                 "(there is no CPU/PyTorch fallback for the HIP path)")
-        # torch must be imported first: it brings its own libamdhip64/libhsa-runtime64, and this library has
+        # torch is imported first (top of this module): it brings its own libamdhip64/libhsa-runtime64, and this library has
         # to bind to THAT runtime instance (same streams, same allocations) instead of loading a second one.
-        import torch  # noqa: F401
         L = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in _PROTOS.items():
             if not hasattr(L, name):
                 continue  # optional symbols are checked by tests/test_abi.py
             fn = getattr(L, name)
-            fn.restype = res
-            fn.argtypes = args
+            fn.restype = c_int if res is RC else res
+            fn.argtypes = [c_void_p if a is STREAM else a for a in args]
         _lib = L
     return _lib
 
@@ -120,6 +125,47 @@ def check(rc, what):
     if rc != 0:
         msg = lib().ps_last_error()
         raise RuntimeError(f"{what} failed (rc={rc}): {msg.decode() if msg else '?'}")
+
+
+_BY_REF = (ctypes.Array, ctypes._SimpleCData)
+_POINTERS = (c_void_p, ctypes.c_char_p, ctypes.c_wchar_p)
+
+
+def call(name, *args, stream=None):
+    """The entry point `name` of _PROTOS on args: a torch tensor or numpy array goes as its data pointer, None as NULL, a ctypes
+    scalar or array (an out-parameter, a small host table) by reference; anything else (ints, floats, bytes, the engine's handle) as
+    ctypes converts it.  An entry point that ends in a STREAM gets the current stream appended (or `stream`), and each of its tensor
+    arguments must be a CUDA tensor on the current device: else RuntimeError, before anything is queued.  A nonzero RC raises
+    RuntimeError (check); any other return value is handed back."""
+    res, types = _PROTOS[name]
+    queued = bool(types) and types[-1] is STREAM
+    if len(args) != len(types) - queued:
+        raise TypeError(f"{name} takes {len(types) - queued} arguments{' besides the stream' if queued else ''}, got {len(args)}")
+    fn = getattr(lib(), name)
+    conv, device = list(args), None
+    for i, a in enumerate(args):
+        if isinstance(a, torch.Tensor):
+            if queued:
+                if not a.is_cuda:
+                    raise RuntimeError(f"{name}: args[{i}] is a CPU tensor; the pixelsynth_amd HIP path needs tensors on the ROCm "
+                                       "device (there is no CPU fallback)")
+                if device is None:
+                    device = torch.cuda.current_device()
+                if a.device.index != device:
+                    raise RuntimeError(f"{name}: args[{i}] is on {a.device}, the call is queued on the current device cuda:{device}")
+            conv[i] = a.data_ptr()
+        elif isinstance(a, np.ndarray):
+            conv[i] = a.ctypes.data
+        elif isinstance(a, _BY_REF) and not isinstance(a, _POINTERS):
+            conv[i] = ctypes.byref(a)
+    if queued:
+        conv.append(torch.cuda.current_stream().cuda_stream if stream is None else stream)
+    elif stream is not None:
+        raise TypeError(f"{name} takes no stream")
+    rc = fn(*conv)
+    if res is RC:
+        check(rc, name)
+    return rc
 
 
 def ptr(t):
@@ -132,7 +178,6 @@ def ptr(t):
 
 
 def current_stream():
-    import torch
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
@@ -142,7 +187,6 @@ _STATUS = {}
 def status_word(device=None):
     """The caller-owned status word (int32, zero) of a device that asynchronous entry points raise bits in
     (include/pixelsynth_hip.h: PS_STATUS_*); one per device, owned by this binding -- the library keeps none."""
-    import torch
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     idx = dev.index if dev.index is not None else torch.cuda.current_device()
     t = _STATUS.get(idx)
@@ -152,11 +196,13 @@ def status_word(device=None):
 
 
 def read_status(what, device=None):
-    """Synchronise the current stream OF THE STATUS WORD'S DEVICE and raise if an asynchronous call raised a bit in it."""
-    import torch
+    """Synchronise the current stream OF THE STATUS WORD'S DEVICE and raise if an asynchronous call (`what`) raised a bit in it."""
     word = status_word(device)
     with torch.cuda.device(word.device):
-        check(lib().ps_read_status(ptr(word), ctypes.c_void_p(torch.cuda.current_stream(word.device).cuda_stream)), what)
+        try:
+            call("ps_read_status", word)
+        except RuntimeError as err:
+            raise RuntimeError(f"{what}: {err}") from None
 
 
 def require_cuda(*tensors):

@@ -101,13 +101,10 @@ def build_ar_plan(background_mask, G=32, device=None):
             bg = background_mask.to(torch.uint8).contiguous().numpy()
         order_t, region_t = _pinned("order", (B, L), torch.int32), _pinned("region", (B, L), torch.uint8)
         order_loc, region = order_t.numpy(), region_t.numpy()
-        rc = _lib.lib().ps_ar_plan(_lib.ptr(bg), B, S, G, _lib.ptr(order_loc), _lib.ptr(region), None, None, None, None)
-        _lib.check(rc, "ps_ar_plan")
+        _lib.call("ps_ar_plan", bg, B, S, G, order_loc, region, None, None, None, None)
         d_order, d_region = order_t.to(device, non_blocking=True), region_t.to(device, non_blocking=True)
         masks = [torch.empty(B, 9, L, dtype=torch.float32, device=device) for _ in range(3)]
-        rc = _lib.lib().ps_order_masks_f32(_lib.ptr(d_order), B, G, G, _lib.ptr(masks[0]), _lib.ptr(masks[1]), _lib.ptr(masks[2]),
-                                           _lib.ptr(_lib.status_word(device)), _lib.current_stream())
-        _lib.check(rc, "ps_order_masks_f32")
+        _lib.call("ps_order_masks_f32", d_order, B, G, G, *masks, _lib.status_word(device))
         plan = ARPlan(d_order, d_region, *masks, order_loc.copy(), region, (G, G))   # (the staging buffers are reused by the next plan)
         if PER_FRAME_PREFIX and int(plan.first_steps.max()) > plan.first_step:
             fs_t = _pinned("first_steps", (B,), torch.int32)

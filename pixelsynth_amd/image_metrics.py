@@ -54,16 +54,13 @@ def image_metrics(img1, img2, mask=None):
     if mask is not None:
         mask = mask.to(torch.float32).contiguous()
     out = torch.empty(B, 6, dtype=torch.float32, device=dev)
-    L = _lib.lib()
     strides = lambda t: (ctypes.c_int64 * 4)(*t.stride())
     with torch.cuda.device(dev):
-        stream = _lib.current_stream()
         for b0 in range(0, B, _MAX_B):
             b1 = min(B, b0 + _MAX_B)
             a, b = img1[b0:b1], img2[b0:b1]
             m = None if mask is None else mask[b0:b1]
-            nbytes = L.ps_image_metrics_workspace_bytes(b1 - b0, C, H, W)
+            nbytes = _lib.call("ps_image_metrics_workspace_bytes", b1 - b0, C, H, W)
             ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-            _lib.check(L.ps_image_metrics(_lib.ptr(a), strides(a), _lib.ptr(b), strides(b), _DTYPES[img1.dtype], _lib.ptr(m),
-                                          b1 - b0, C, H, W, _lib.ptr(out[b0:b1]), _lib.ptr(ws), nbytes, stream), "ps_image_metrics")
+            _lib.call("ps_image_metrics", a, strides(a), b, strides(b), _DTYPES[img1.dtype], m, b1 - b0, C, H, W, out[b0:b1], ws, nbytes)
     return out

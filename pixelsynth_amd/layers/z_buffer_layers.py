@@ -34,7 +34,7 @@ _WS = _Workspace()
 
 
 def splat_workspace(device, B, N, S, radius_px):
-    n = _lib.lib().ps_splat_workspace_bytes(B, N, S, float(radius_px))
+    n = _lib.call("ps_splat_workspace_bytes", B, N, S, float(radius_px))
     if n == 0:
         raise RuntimeError("ps_splat_workspace_bytes: invalid sizes")
     return _WS.get(device, n)
@@ -70,7 +70,6 @@ class RasterizePointsXYsBlending(nn.Module):
         # cloud and features must be arranged alike: (B,N,3) against (B,C,N)
         if pts3D.size(2) != 3 or pts3D.size(1) != src.size(2):
             raise AssertionError(f"splat: points {tuple(pts3D.shape)} do not match features {tuple(src.shape)}")
-        _lib.require_cuda(pts3D, src)
         os.environ.get("DEBUG")  # the reference reads os.environ["DEBUG"] (KeyError if unset); tolerated here
 
         B, N, C = bs, pts3D.size(1), src.size(1)
@@ -87,14 +86,9 @@ class RasterizePointsXYsBlending(nn.Module):
             zbuf = torch.empty(B, S, S, K, dtype=torch.float32, device=pts.device)
             dist = torch.empty(B, S, S, K, dtype=torch.float32, device=pts.device)
         ws = splat_workspace(pts.device, B, N, S, self.radius)
-        rc = _lib.lib().ps_splat_f32(
-            _lib.ptr(pts), _lib.ptr(feat), B, N, C, S, float(self.radius), K,
-            float(self._opt("tau", 1.0)), int(self._opt("rad_pow", 2)),
-            ACCUMULATION[self._opt("accumulation", "alphacomposite")],
-            int(self._opt("background_smoothing_kernel_size", 13)),
-            _lib.ptr(out), _lib.ptr(bg), _lib.ptr(idx), _lib.ptr(zbuf), _lib.ptr(dist),
-            _lib.ptr(ws), ws.numel(), _lib.current_stream())
-        _lib.check(rc, "ps_splat_f32")
+        _lib.call("ps_splat_f32", pts, feat, B, N, C, S, float(self.radius), K, float(self._opt("tau", 1.0)), int(self._opt("rad_pow", 2)),
+                  ACCUMULATION[self._opt("accumulation", "alphacomposite")], int(self._opt("background_smoothing_kernel_size", 13)),
+                  out, bg, idx, zbuf, dist, ws, ws.numel())
         if pts is not caller_pts:  # keep the reference's visible side effect on the caller's tensor
             caller_pts[:, :, 0:2] = pts[:, :, 0:2].to(caller_pts.dtype)
         background_mask = bg.view(torch.bool)    # (k_dilate writes 0 / 1: the same bytes are the boolean mask)

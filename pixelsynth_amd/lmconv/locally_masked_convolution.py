@@ -46,7 +46,6 @@ def lmconv_forward(x, mask, weight, bias=None, dilation=1):
                              f"weight wants {in_channels} / {k1 * k2}")
     if (k1, k2) != (3, 3):
         raise NotImplementedError("the HIP lmconv kernel implements the 3x3 kernels PixelSynth uses")
-    _lib.require_cuda(x, mask, weight, bias)
     B, _, H, W = x.shape
     m = compact_mask(mask, B, in_channels)
     stride = 0 if m.size(0) == 1 and B > 1 else 9 * H * W
@@ -54,12 +53,8 @@ def lmconv_forward(x, mask, weight, bias=None, dilation=1):
     wc = weight.float().contiguous()
     bc = None if bias is None else bias.float().contiguous()
     y = torch.empty(B, out_channels, H, W, dtype=torch.float32, device=x.device)
-    L = _lib.lib()
-    ws = _workspace(x.device, L.ps_lmconv_workspace_bytes(B, in_channels, out_channels, H, W))
-    rc = L.ps_lmconv_forward_f32(_lib.ptr(xc), _lib.ptr(m), stride, _lib.ptr(wc), _lib.ptr(bc), B, in_channels,
-                                 out_channels, H, W, int(dilation), _lib.ptr(y), _lib.ptr(ws), ws.numel(),
-                                 _lib.current_stream())
-    _lib.check(rc, "ps_lmconv_forward_f32")
+    ws = _workspace(x.device, _lib.call("ps_lmconv_workspace_bytes", B, in_channels, out_channels, H, W))
+    _lib.call("ps_lmconv_forward_f32", xc, m, stride, wc, bc, B, in_channels, out_channels, H, W, int(dilation), y, ws, ws.numel())
     return y
 
 

@@ -28,7 +28,7 @@ def custom_idx(rows, cols, distances, mass_center=None):
     if not (isinstance(distances, np.ndarray) and distances.dtype == np.int64 and distances.flags.c_contiguous):
         raise TypeError("custom_idx expects a C-contiguous int64 numpy array (it is modified in place)")
     order = np.empty((rows * cols, 2), np.int32)
-    _lib.check(_lib.lib().ps_custom_order(rows, cols, _lib.ptr(distances), _lib.ptr(order)), "ps_custom_order")
+    _lib.call("ps_custom_order", rows, cols, distances, order)
     return order.astype(np.int64)
 
 
@@ -48,8 +48,7 @@ def kernel_masks(generation_order_idx, nrows, ncols, k=3, dilation=1, mask_type=
     assert mask_type in ['A', 'B']
     order = np.ascontiguousarray(generation_order_idx, dtype=np.int32)
     m = np.empty((k * k, nrows * ncols), np.float32)
-    _lib.check(_lib.lib().ps_kernel_masks_f32(_lib.ptr(order), order.shape[0], nrows, ncols, k, dilation,
-                                              int(mask_type == 'B'), _lib.ptr(m)), "ps_kernel_masks_f32")
+    _lib.call("ps_kernel_masks_f32", order, order.shape[0], nrows, ncols, k, dilation, int(mask_type == 'B'), m)
     return m.T.reshape(nrows * ncols, k, k).astype(np.float64)
 
 
@@ -60,8 +59,7 @@ def get_unfolded_masks(generation_order_idx, nrows, ncols, k=3, dilation=1, mask
     assert mask_type in ['A', 'B']
     order = np.ascontiguousarray(generation_order_idx, dtype=np.int32)
     m = np.empty((k * k, nrows * ncols), np.float32)
-    _lib.check(_lib.lib().ps_kernel_masks_f32(_lib.ptr(order), order.shape[0], nrows, ncols, k, dilation,
-                                              int(mask_type == 'B'), _lib.ptr(m)), "ps_kernel_masks_f32")
+    _lib.call("ps_kernel_masks_f32", order, order.shape[0], nrows, ncols, k, dilation, int(mask_type == 'B'), m)
     return torch.from_numpy(m)[None]
 
 

@@ -57,54 +57,50 @@ class PixelCNNEngine:
         ptrs = (ctypes.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
         self.handle = ctypes.c_void_p()
         self.H, self.W, self.L, self.max_frames = H, W, H * W, max_frames
-        rc = _lib.lib().ps_pixelcnn_create(ptrs, len(arrs), H, W, max_frames, ctypes.byref(self.handle))
-        _lib.check(rc, "ps_pixelcnn_create")
+        _lib.call("ps_pixelcnn_create", ptrs, len(arrs), H, W, max_frames, ctypes.byref(self.handle))
 
     def check(self):
         """Synchronise and raise if any column launch of this engine gave up on an in-launch wait (ps_pixelcnn_status)."""
-        _lib.check(_lib.lib().ps_pixelcnn_status(self.handle, _lib.current_stream()), "ps_pixelcnn_status")
+        _lib.call("ps_pixelcnn_status", self.handle)
 
     def set_tuning(self, **values):
         """Tuning values of the handle by name (include/pixelsynth_hip_debug.h: ps_pixelcnn_set_tuning) -- which launch form the
         whole-grid pass takes from which size on, the look-ahead depths of the column launches, ...  None of them changes
         results; the parity tests use this to run every form inside one process."""
         for k, v in values.items():
-            _lib.check(_lib.lib().ps_pixelcnn_set_tuning(self.handle, k.encode(), int(v)), f"ps_pixelcnn_set_tuning({k})")
+            _lib.call("ps_pixelcnn_set_tuning", self.handle, k.encode(), int(v))
         return self
 
     def get_tuning(self, key):
         v = ctypes.c_int(0)
-        _lib.check(_lib.lib().ps_pixelcnn_get_tuning(self.handle, key.encode(), ctypes.cast(ctypes.byref(v), ctypes.c_void_p)),
-                   f"ps_pixelcnn_get_tuning({key})")
+        _lib.call("ps_pixelcnn_get_tuning", self.handle, key.encode(), v)
         return v.value
 
     # ---- which kernels carried the matrix work (include/pixelsynth_hip_debug.h; tests and bench.py, not the product path)
     @staticmethod
     def launch_kind_names():
-        L = _lib.lib()
-        return [L.ps_pixelcnn_launch_kind_name(k).decode() for k in range(L.ps_pixelcnn_launch_kinds())]
+        return [_lib.call("ps_pixelcnn_launch_kind_name", k).decode() for k in range(_lib.call("ps_pixelcnn_launch_kinds"))]
 
     def launch_counts(self):
         """{kernel: launches of this engine since its creation} (host counters)."""
         names = self.launch_kind_names()
         buf = (ctypes.c_longlong * len(names))()
-        _lib.check(_lib.lib().ps_pixelcnn_launch_counts(self.handle, ctypes.cast(buf, ctypes.c_void_p), len(names)), "ps_pixelcnn_launch_counts")
+        _lib.call("ps_pixelcnn_launch_counts", self.handle, buf, len(names))
         return dict(zip(names, (int(v) for v in buf)))
 
     def profile_begin(self):
-        _lib.check(_lib.lib().ps_pixelcnn_profile_begin(self.handle), "ps_pixelcnn_profile_begin")
+        _lib.call("ps_pixelcnn_profile_begin", self.handle)
 
     def profile_end(self):
         """Synchronises -> {kernel: (launches, summed ms)} of the launches since profile_begin (HIP events on the launches' own streams)."""
         names = self.launch_kind_names()
         n, ms = (ctypes.c_int * len(names))(), (ctypes.c_float * len(names))()
-        _lib.check(_lib.lib().ps_pixelcnn_profile_end(self.handle, len(names), ctypes.cast(n, ctypes.c_void_p), ctypes.cast(ms, ctypes.c_void_p)),
-                   "ps_pixelcnn_profile_end")
+        _lib.call("ps_pixelcnn_profile_end", self.handle, len(names), n, ms)
         return {k: (int(a), float(b)) for k, a, b in zip(names, n, ms)}
 
     def close(self):
         if getattr(self, "handle", None):
-            _lib.lib().ps_pixelcnn_destroy(self.handle)
+            _lib.call("ps_pixelcnn_destroy", self.handle)
             self.handle = None
 
     def __del__(self):
@@ -136,14 +132,19 @@ class PixelCNNEngine:
         if F_ > self.max_frames:
             raise ValueError(f"{F_} frames on an engine built for {self.max_frames}")
         codes = codes.reshape(F_, self.L).to(torch.int32).contiguous()
-        _lib.require_cuda(codes, mask_init, mask_undilated, mask_dilated)
-        mask_init, mask_undilated, mask_dilated = self._frame_masks(F_, mask_init, mask_undilated, mask_dilated)
+        masks = self._frame_masks(F_, mask_init, mask_undilated, mask_dilated)
         logits = torch.empty(F_, 512, self.H, self.W, dtype=torch.float32, device=codes.device)
-        rc = _lib.lib().ps_pixelcnn_forward_f32(self.handle, _lib.ptr(codes), _lib.ptr(mask_init),
-                                                _lib.ptr(mask_undilated), _lib.ptr(mask_dilated), F_,
-                                                _lib.ptr(logits), _lib.current_stream())
-        _lib.check(rc, "ps_pixelcnn_forward_f32")
+        _lib.call("ps_pixelcnn_forward_f32", self.handle, codes, *masks, F_, logits)
         return logits
+
+    def _ar_args(self, codes, order, region, mask_init, mask_undilated, mask_dilated, forced=None, uniforms=None):
+        """The frame arguments of an AR call checked (None: not one of the call's) -> (F, the three masks as the kernels index them)."""
+        F_ = codes.shape[0]
+        masks = self._frame_masks(F_, mask_init, mask_undilated, mask_dilated)
+        for name, t, dt in (("codes", codes, torch.int32), ("order", order, torch.int32), ("region", region, torch.uint8),
+                            ("forced", forced, torch.int32), ("uniforms", uniforms, torch.float32)):
+            self._frame_arg(F_, name, t, dt)
+        return F_, masks
 
     def ar_run(self, codes, order, region, mask_init, mask_undilated, mask_dilated, temperature=1.0, forced=None,
                uniforms=None, first_step=0, want_logits=False, waves=None):
@@ -151,37 +152,18 @@ class PixelCNNEngine:
         region (F,L) uint8 by location.  waves: optional wavefront schedule for these orders and this first_step,
         (cols device int32 (n,2), wave_start host int32 array) as from wavefronts() -- same results, far fewer
         dependent launches.  Returns out_logits (F,L,512) or None."""
-        F_ = codes.shape[0]
-        _lib.require_cuda(codes, order, region, mask_init, mask_undilated, mask_dilated, forced, uniforms)
-        mask_init, mask_undilated, mask_dilated = self._frame_masks(F_, mask_init, mask_undilated, mask_dilated)
-        for name, t, dt in (("codes", codes, torch.int32), ("order", order, torch.int32), ("region", region, torch.uint8),
-                            ("forced", forced, torch.int32), ("uniforms", uniforms, torch.float32)):
-            self._frame_arg(F_, name, t, dt)
+        F_, masks = self._ar_args(codes, order, region, mask_init, mask_undilated, mask_dilated, forced, uniforms)
         out = torch.empty(F_, self.L, 512, dtype=torch.float32, device=codes.device) if want_logits else None
-        head = (self.handle, _lib.ptr(codes), _lib.ptr(order), _lib.ptr(region), _lib.ptr(mask_init),
-                _lib.ptr(mask_undilated), _lib.ptr(mask_dilated), _lib.ptr(forced), _lib.ptr(uniforms),
-                float(temperature), F_, int(first_step))
+        head = (self.handle, codes, order, region, *masks, forced, uniforms, float(temperature), F_, int(first_step))
         from ..distributed import shared_device_turn
         with shared_device_turn():   # (a no-op but in the single-GPU dry run of several ranks)
             if waves is None or waves[0].shape[0] == 0:  # (nothing to walk: only the whole-grid pass runs)
-                rc = _lib.lib().ps_pixelcnn_ar_run(*head, _lib.ptr(out), _lib.current_stream())
-                _lib.check(rc, "ps_pixelcnn_ar_run")
+                _lib.call("ps_pixelcnn_ar_run", *head, out)
             else:
                 cols, wave_start = waves
-                _lib.require_cuda(cols)
                 assert cols.dtype == torch.int32 and wave_start.dtype == np.int32
-                rc = _lib.lib().ps_pixelcnn_ar_run_waves(*head, _lib.ptr(cols), _lib.ptr(wave_start), len(wave_start) - 1,
-                                                         _lib.ptr(out), _lib.current_stream())
-                _lib.check(rc, "ps_pixelcnn_ar_run_waves")
+                _lib.call("ps_pixelcnn_ar_run_waves", *head, cols, wave_start, len(wave_start) - 1, out)
         return out
-
-    def _ar_args(self, codes, order, region, mask_init, mask_undilated, mask_dilated):
-        F_ = codes.shape[0]
-        _lib.require_cuda(codes, order, region, mask_init, mask_undilated, mask_dilated)
-        masks = self._frame_masks(F_, mask_init, mask_undilated, mask_dilated)
-        for name, t, dt in (("codes", codes, torch.int32), ("order", order, torch.int32), ("region", region, torch.uint8)):
-            self._frame_arg(F_, name, t, dt)
-        return F_, masks
 
     def ar_prefix(self, codes, order, region, mask_init, mask_undilated, mask_dilated, first_step, frame_begin=0, frame_end=None,
                   first_steps=None, max_first_step=None):
@@ -189,51 +171,34 @@ class PixelCNNEngine:
         prefix.  Asynchronous on the current stream; disjoint frame ranges may go to different streams (ps_pixelcnn_ar_prefix).
         first_steps (F,) int32 device tensor + max_first_step: PER-FRAME prefixes (ps_pixelcnn_ar_prefix_frames) -- frame f's pass
         covers its positions [0, first_steps[f]), first_step <= first_steps[f] <= max_first_step."""
-        F_, (mi, mu, md) = self._ar_args(codes, order, region, mask_init, mask_undilated, mask_dilated)
-        if first_steps is not None:
-            _lib.require_cuda(first_steps)
-            assert first_steps.dtype == torch.int32 and first_steps.shape == (F_,) and first_steps.is_contiguous()
-            rc = _lib.lib().ps_pixelcnn_ar_prefix_frames(self.handle, _lib.ptr(codes), _lib.ptr(order), _lib.ptr(region), _lib.ptr(mi), _lib.ptr(mu),
-                                                         _lib.ptr(md), F_, _lib.ptr(first_steps), int(first_step), int(max_first_step), int(frame_begin),
-                                                         int(F_ if frame_end is None else frame_end), _lib.current_stream())
-            _lib.check(rc, "ps_pixelcnn_ar_prefix_frames")
+        F_, masks = self._ar_args(codes, order, region, mask_init, mask_undilated, mask_dilated)
+        frames = (int(frame_begin), int(F_ if frame_end is None else frame_end))
+        if first_steps is None:
+            _lib.call("ps_pixelcnn_ar_prefix", self.handle, codes, order, region, *masks, F_, int(first_step), *frames)
             return
-        rc = _lib.lib().ps_pixelcnn_ar_prefix(self.handle, _lib.ptr(codes), _lib.ptr(order), _lib.ptr(region), _lib.ptr(mi), _lib.ptr(mu),
-                                              _lib.ptr(md), F_, int(first_step), int(frame_begin), int(F_ if frame_end is None else frame_end),
-                                              _lib.current_stream())
-        _lib.check(rc, "ps_pixelcnn_ar_prefix")
+        assert first_steps.dtype == torch.int32 and first_steps.shape == (F_,) and first_steps.is_contiguous()
+        _lib.call("ps_pixelcnn_ar_prefix_frames", self.handle, codes, order, region, *masks, F_, first_steps, int(first_step),
+                  int(max_first_step), *frames)
 
     def ar_columns(self, codes, order, region, mask_init, mask_undilated, mask_dilated, waves, temperature=1.0, forced=None, uniforms=None,
                    first_step=0):
         """Second half of ar_run: the column launches of all frames, wavefront by wavefront (ps_pixelcnn_ar_columns); every frame's
         ar_prefix must have completed (stream order / events are the caller's)."""
-        F_, (mi, mu, md) = self._ar_args(codes, order, region, mask_init, mask_undilated, mask_dilated)
-        _lib.require_cuda(forced, uniforms)
-        self._frame_arg(F_, "forced", forced, torch.int32)
-        self._frame_arg(F_, "uniforms", uniforms, torch.float32)
+        F_, masks = self._ar_args(codes, order, region, mask_init, mask_undilated, mask_dilated, forced, uniforms)
         cols, wave_start = waves
-        _lib.require_cuda(cols)
         from ..distributed import shared_device_turn
         with shared_device_turn():
-            rc = _lib.lib().ps_pixelcnn_ar_columns(self.handle, _lib.ptr(codes), _lib.ptr(order), _lib.ptr(region), _lib.ptr(mi), _lib.ptr(mu),
-                                                   _lib.ptr(md), _lib.ptr(forced), _lib.ptr(uniforms), float(temperature), F_, int(first_step),
-                                                   _lib.ptr(cols), _lib.ptr(wave_start), len(wave_start) - 1, _lib.current_stream())
-            _lib.check(rc, "ps_pixelcnn_ar_columns")
+            _lib.call("ps_pixelcnn_ar_columns", self.handle, codes, order, region, *masks, forced, uniforms, float(temperature), F_,
+                      int(first_step), cols, wave_start, len(wave_start) - 1)
 
     def set_compute_units(self, n_cus):
         """Compute units the stream of this engine's column launches can use (0 = the whole device)."""
-        _lib.check(_lib.lib().ps_pixelcnn_set_compute_units(self.handle, int(n_cus)), "ps_pixelcnn_set_compute_units")
+        _lib.call("ps_pixelcnn_set_compute_units", self.handle, int(n_cus))
 
     def ar_step(self, codes, order, mask_init, mask_undilated, mask_dilated, step, first_step):
-        F_ = codes.shape[0]
-        mask_init, mask_undilated, mask_dilated = self._frame_masks(F_, mask_init, mask_undilated, mask_dilated)
-        self._frame_arg(F_, "codes", codes, torch.int32)
-        self._frame_arg(F_, "order", order, torch.int32)
+        F_, masks = self._ar_args(codes, order, None, mask_init, mask_undilated, mask_dilated)
         logits = torch.empty(F_, 512, dtype=torch.float32, device=codes.device)
-        rc = _lib.lib().ps_pixelcnn_ar_step(self.handle, _lib.ptr(codes), _lib.ptr(order), _lib.ptr(mask_init),
-                                            _lib.ptr(mask_undilated), _lib.ptr(mask_dilated), F_, int(step),
-                                            int(first_step), _lib.ptr(logits), _lib.current_stream())
-        _lib.check(rc, "ps_pixelcnn_ar_step")
+        _lib.call("ps_pixelcnn_ar_step", self.handle, codes, order, *masks, F_, int(step), int(first_step), logits)
         return logits
 
 
@@ -252,7 +217,7 @@ class CuRangeStream:
         self.first, self.n = int(first), int(n)
         self._raw = ctypes.c_void_p()
         with torch.cuda.device(device if device is not None else torch.cuda.current_device()):
-            _lib.check(_lib.lib().ps_stream_create_cu_range(self.first, self.n, ctypes.byref(self._raw)), "ps_stream_create_cu_range")
+            _lib.call("ps_stream_create_cu_range", self.first, self.n, ctypes.byref(self._raw))
             self.stream = torch.cuda.ExternalStream(self._raw.value)
 
     def close(self):
@@ -443,7 +408,6 @@ def wavefronts(order_host, H, W, first_step, device=None, max_cols=None, keep_ho
     max_cols: columns per wave (0 = the pure dependency levels; None = what a launch takes for this many frames).
     keep_host: a third value, the (n,2) columns as a numpy array of the caller's own (schedule surgery on the host).
     first_steps: (F,) int32 numpy array, a first walked position PER FRAME (ps_ar_wavefronts_frames; first_step = their minimum)."""
-    import ctypes
     order_host = np.ascontiguousarray(order_host, np.int32)
     F_, L = order_host.shape
     if max_cols is None:
@@ -546,7 +510,6 @@ class LaunchPipeline:
 
 
 def _wavefronts(order_host, F_, L, H, W, first_step, device, max_cols, keep_host=False, first_steps=None):
-    import ctypes
     nsteps = L - first_step
     n = F_ * nsteps
     if first_steps is not None:
@@ -564,12 +527,9 @@ def _wavefronts(order_host, F_, L, H, W, first_step, device, max_cols, keep_host
     wave_start = np.zeros(nsteps + (n + max_cols - 1) // max_cols + 2 if max_cols else nsteps + 1, np.int32)
     nw = ctypes.c_int32(0)
     if first_steps is not None:
-        rc = _lib.lib().ps_ar_wavefronts_frames(_lib.ptr(order_host), F_, H, W, _lib.ptr(first_steps), int(max_cols), _lib.ptr(cols),
-                                                _lib.ptr(wave_start), ctypes.cast(ctypes.byref(nw), ctypes.c_void_p))
+        _lib.call("ps_ar_wavefronts_frames", order_host, F_, H, W, first_steps, int(max_cols), cols, wave_start, nw)
     else:
-        rc = _lib.lib().ps_ar_wavefronts_capped(_lib.ptr(order_host), F_, H, W, int(first_step), int(max_cols), _lib.ptr(cols),
-                                                _lib.ptr(wave_start), ctypes.cast(ctypes.byref(nw), ctypes.c_void_p))
-    _lib.check(rc, "ps_ar_wavefronts_capped")
+        _lib.call("ps_ar_wavefronts_capped", order_host, F_, H, W, int(first_step), int(max_cols), cols, wave_start, nw)
     host = cols[:n].copy() if keep_host else None
     if device is not None:
         cols_t = stage[:n].to(device, non_blocking=True)

@@ -140,9 +140,8 @@ class LinearNoiseLayer(nn.Module):
                 noise = noise.contiguous()
                 scale = torch.empty(B, C, dtype=torch.float32, device=x.device)
                 shift = torch.empty_like(scale)
-                _lib.check(_lib.lib().ps_noise_affine_f32(noise.data_ptr(), ws[0].data_ptr(), ws[1].data_ptr(), self.bn.stored_mean.data_ptr(),
-                                                          self.bn.stored_var.data_ptr(), _ptr(pend), float(self.bn.eps), B, C, noise.size(1),
-                                                          scale.data_ptr(), shift.data_ptr(), _stream()), "ps_noise_affine_f32")
+                _lib.call("ps_noise_affine_f32", noise, ws[0], ws[1], self.bn.stored_mean, self.bn.stored_var, pend, float(self.bn.eps), B, C,
+                          noise.size(1), scale, shift)
                 return scale, shift
         scale, shift = self.affine(x, noise)
         if pend is not None:
@@ -185,14 +184,6 @@ def _is_nhwc_cuda(*ts):
 
 def _empty_nhwc(B, C, H, W, like):
     return torch.empty((B, C, H, W), dtype=like.dtype, device=like.device, memory_format=torch.channels_last)
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _ptr(t):
-    return None if t is None else t.data_ptr()
 
 
 def _plain_conv_weight(conv, x):
@@ -263,9 +254,8 @@ def conv1x1(conv, x):
             and conv.dilation == (1, 1) and conv.groups == 1 and _is_nhwc_cuda(x) and not torch.is_grad_enabled()):
         return None
     from .. import _lib
-    L = _lib.lib()
     Ci, Co = conv.in_channels, conv.out_channels
-    if not L.ps_conv1x1_takes(Ci, Co):
+    if not _lib.call("ps_conv1x1_takes", Ci, Co):
         return None
     weight = _plain_conv_weight(conv, x)
     if weight is None or weight.dtype != torch.float32 or not weight.is_cuda or weight.device != x.device:
@@ -279,7 +269,7 @@ def conv1x1(conv, x):
     y = _empty_nhwc(B, Co, H, W, x)
     if Co == 1:   # (channels_last of one channel is ambiguous to torch; the kernel writes (B, H, W, Co))
         y = torch.empty((B, H, W, Co), dtype=x.dtype, device=x.device).permute(0, 3, 1, 2)
-    _lib.check(L.ps_conv1x1_nhwc_f32(x.data_ptr(), cache[1].data_ptr(), B * H * W, Ci, Co, y.data_ptr(), _stream()), "ps_conv1x1_nhwc_f32")
+    _lib.call("ps_conv1x1_nhwc_f32", x, cache[1], B * H * W, Ci, Co, y)
     return y
 
 
@@ -332,7 +322,6 @@ def _thin_conv(conv, x, scale=None, shift=None):
     if weight is None:
         return None
     from .. import _lib
-    L = _lib.lib()
     key = (weight.data_ptr(), weight._version, str(weight.device))
     cache = conv.__dict__.get("_ps_thin_cache")
     if cache is None or cache[0] != key:
@@ -343,14 +332,11 @@ def _thin_conv(conv, x, scale=None, shift=None):
     if Co == 1:   # (channels_last of one channel is ambiguous to torch; the kernel writes (B, H, W, Co))
         y = torch.empty((B, H, W, Co), dtype=x.dtype, device=x.device).permute(0, 3, 1, 2)
     if thin_in and Co == 64 and W % 16 == 0:   # on the fp16 matrix pipe (split operands): 82 instead of 270 us per 16 views
-        _lib.check(L.ps_conv3x3_thin_in_f16x3_nhwc(x.data_ptr(), _ptr(scale), _ptr(shift), cache[1].data_ptr(), B, H, W, Co, y.data_ptr(),
-                                                   _overflow_flag(x.device).data_ptr(), _stream()), "ps_conv3x3_thin_in_f16x3_nhwc")
+        _lib.call("ps_conv3x3_thin_in_f16x3_nhwc", x, scale, shift, cache[1], B, H, W, Co, y, _overflow_flag(x.device))
     elif thin_in:
-        _lib.check(L.ps_conv3x3_thin_in_nhwc_f32(x.data_ptr(), _ptr(scale), _ptr(shift), cache[1].data_ptr(), B, H, W, Co, y.data_ptr(),
-                                                 _stream()), "ps_conv3x3_thin_in_nhwc_f32")
+        _lib.call("ps_conv3x3_thin_in_nhwc_f32", x, scale, shift, cache[1], B, H, W, Co, y)
     else:
-        _lib.check(L.ps_conv3x3_thin_out_nhwc_f32(x.data_ptr(), _ptr(scale), _ptr(shift), cache[1].data_ptr(), B, H, W, Ci, Co,
-                                                  y.data_ptr(), _stream()), "ps_conv3x3_thin_out_nhwc_f32")
+        _lib.call("ps_conv3x3_thin_out_nhwc_f32", x, scale, shift, cache[1], B, H, W, Ci, Co, y)
     return y
 
 
@@ -397,18 +383,15 @@ def _resample_sum(kind, a, b, bias=None, post=None):
     B, C, H, W = a.shape
     if not kind:
         out = torch.empty_like(a)
-        _lib.check(_lib.lib().ps_add_bias_nhwc_f32(a.data_ptr(), b.data_ptr(), _ptr(bias), B, H * W, C, out.data_ptr(), _stream()),
-                   "ps_add_bias_nhwc_f32")
+        _lib.call("ps_add_bias_nhwc_f32", a, b, bias, B, H * W, C, out)
     elif kind == "Up":
         out = _empty_nhwc(B, C, 2 * H, 2 * W, a)
-        _lib.check(_lib.lib().ps_upsample_add_nhwc_f32(a.data_ptr(), _ptr(b), _ptr(bias), B, H, W, C, out.data_ptr(), _stream()),
-                   "ps_upsample_add_nhwc_f32")
+        _lib.call("ps_upsample_add_nhwc_f32", a, b, bias, B, H, W, C, out)
     else:
         out = _empty_nhwc(B, C, H // 2, W // 2, a)
         if post is not None and not (_is_nhwc_cuda(post) and post.shape == out.shape):
             raise ValueError("_resample_sum: post must be a channels_last tensor of the pooled shape")
-        _lib.check(_lib.lib().ps_pool_add_post_nhwc_f32(a.data_ptr(), _ptr(b), _ptr(bias), _ptr(post), B, H, W, C, out.data_ptr(), _stream()),
-                   "ps_pool_add_post_nhwc_f32")
+        _lib.call("ps_pool_add_post_nhwc_f32", a, b, bias, post, B, H, W, C, out)
         return out
     if post is not None:
         raise ValueError("_resample_sum: post goes with 'Down' only")
@@ -454,8 +437,7 @@ class ResNet_Block(nn.Module):
             sc = scale.reshape(-1, C).expand(B, C).contiguous()
             sh = shift.reshape(-1, C).expand(B, C).contiguous()
             y = torch.empty_like(x)   # (preserves channels_last)
-            _lib.check(_lib.lib().ps_affine_relu_nhwc_f32(x.data_ptr(), sc.data_ptr(), sh.data_ptr(), B, x.size(2) * x.size(3), C,
-                                                          y.data_ptr(), _stream()), "ps_affine_relu_nhwc_f32")
+            _lib.call("ps_affine_relu_nhwc_f32", x, sc, sh, B, x.size(2) * x.size(3), C, y)
             return y
         return torch.clamp_min(torch.addcmul(-shift, x, scale), 0)
 
@@ -528,8 +510,7 @@ class ResNetDecoder(nn.Module):
             from .. import _lib
             B, _, H, W = x.shape
             h = _empty_nhwc(B, 4, H, W, x)          # cat + NCHW -> NHWC in one pass
-            _lib.check(_lib.lib().ps_cat_mask_nhwc_f32(x.data_ptr(), background_mask.data_ptr(), B, H, W, h.data_ptr(), _stream()),
-                       "ps_cat_mask_nhwc_f32")
+            _lib.call("ps_cat_mask_nhwc_f32", x, background_mask, B, H, W, h)
             _nhwc(self, h)                            # (the weights, once)
         else:
             h = x if background_mask is None else torch.cat((x, (~background_mask).unsqueeze(1).float()), 1)

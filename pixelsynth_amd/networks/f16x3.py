@@ -95,9 +95,8 @@ def pack3x3(weight, bias=None, s2d=False, d2s=False):
     top = float(wl.abs().max())
     if not (top == top and top < 6.0e4):
         raise ValueError("split-fp16 convolution: a weight fp16 cannot hold")
-    L = _lib.lib()
-    packed = torch.empty(L.ps_conv3x3_f16x3_packed_bytes(Cop, Ci), dtype=torch.uint8, device=weight.device)
-    _lib.check(L.ps_conv3x3_f16x3_pack(wl.data_ptr(), Cop, Ci, packed.data_ptr(), _lib.current_stream()), "ps_conv3x3_f16x3_pack")
+    packed = torch.empty(_lib.call("ps_conv3x3_f16x3_packed_bytes", Cop, Ci), dtype=torch.uint8, device=weight.device)
+    _lib.call("ps_conv3x3_f16x3_pack", wl, Cop, Ci, packed)
     if bias is not None:
         bias = torch.cat([bias, bias.new_zeros(Cop - Co)]).contiguous()
     return dict(packed=packed, Ci=Ci, Co=Cop, live=Co, bias=bias, s2d=s2d, d2s=d2s)
@@ -114,8 +113,6 @@ def conv3x3(x, p, scale=None, shift=None, bias=None, res=None):
     shape = (B, p["Co"] // 4, 2 * H, 2 * W) if p["d2s"] else (B, p["Co"], H, W)
     y = torch.empty(shape, dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
     bias = p["bias"] if bias is None else bias
-    ptr = lambda t: None if t is None else t.data_ptr()
-    _lib.check(_lib.lib().ps_conv3x3_f16x3_ex_nhwc(x.data_ptr(), ptr(scale), ptr(shift), p["packed"].data_ptr(), ptr(bias), ptr(res), B, H, W,
-                                                   C, p["Co"], p["live"], int(p["s2d"]), int(p["d2s"]), y.data_ptr(),
-                                                   flag(x.device).data_ptr(), _lib.current_stream()), "ps_conv3x3_f16x3_ex_nhwc")
+    _lib.call("ps_conv3x3_f16x3_ex_nhwc", x, scale, shift, p["packed"], bias, res, B, H, W, C, p["Co"], p["live"], int(p["s2d"]),
+              int(p["d2s"]), y, flag(x.device))
     return y

@@ -37,7 +37,6 @@ class DepthManipulator(nn.Module):
     @torch.no_grad()
     def project_zbuffer(self, depth, K, K_inv, RTinv_cam1, RT_cam2):
         """depth (B,1,w,h), cameras (B,4,4) -> (bilinear_sampler (B,2,w,h), projected depth (B,1,w,h))."""
-        _lib.require_cuda(depth, K, K_inv, RTinv_cam1, RT_cam2)
         bs, _, w, h = depth.size()
         if w != 256 or h != 256:   # the literals 128 / 255 of :66-90 only mean "the image" at 256 (the reference indexes out of bounds below it)
             raise ValueError(f"DepthManipulator.project_zbuffer: {w}x{h} input; the reference's pixel mapping is written for 256x256")
@@ -48,14 +47,9 @@ class DepthManipulator(nn.Module):
         zproj = torch.empty(bs, N, dtype=torch.float32, device=dev)
         ys, xs = torch.empty(bs, N, dtype=torch.int32, device=dev), torch.empty(bs, N, dtype=torch.int32, device=dev)
         flag = torch.empty(bs, N, dtype=torch.float32, device=dev)
-        L = _lib.lib()
-        _lib.check(L.ps_zbuffer_project_f32(_lib.ptr(depth), _lib.ptr(grid), _lib.ptr(K), _lib.ptr(K_inv), _lib.ptr(RTinv_cam1),
-                                            _lib.ptr(RT_cam2), bs, w, _lib.ptr(zproj), _lib.ptr(ys), _lib.ptr(xs), _lib.ptr(flag),
-                                            _lib.current_stream()), "ps_zbuffer_project_f32")
+        _lib.call("ps_zbuffer_project_f32", depth, grid, K, K_inv, RTinv_cam1, RT_cam2, bs, w, zproj, ys, xs, flag)
         order = zproj.sort(dim=1, descending=True, stable=True)[1].contiguous()      # (B,N) point at each sorted position (:68)
         out = torch.full((bs, 2, w, h), -2.0, device=dev, dtype=torch.float32)
         winner = torch.empty(bs, w, h, dtype=torch.int32, device=dev)
-        _lib.check(L.ps_zbuffer_scatter_sorted_f32(_lib.ptr(order), _lib.ptr(ys), _lib.ptr(xs), _lib.ptr(grid), _lib.ptr(flag), bs, N,
-                                                   w, h, _lib.ptr(out), _lib.ptr(winner), _lib.ptr(_lib.status_word(dev)),
-                                                   _lib.current_stream()), "ps_zbuffer_scatter_sorted_f32")
+        _lib.call("ps_zbuffer_scatter_sorted_f32", order, ys, xs, grid, flag, bs, N, w, h, out, winner, _lib.status_word(dev))
         return out, (-zproj).view(bs, 1, w, h)

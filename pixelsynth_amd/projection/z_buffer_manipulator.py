@@ -43,16 +43,12 @@ class PtsManipulator(nn.Module):
     # ------------------------------------------------------------------ a2
     def project_pts(self, pts3D, K, K_inv, RT_cam1, RTinv_cam1, RT_cam2, RTinv_cam2):
         """Reference :50-83.  pts3D (B,1,N) depth -> sampler (B,3,N)."""
-        _lib.require_cuda(pts3D, K, K_inv, RTinv_cam1, RT_cam2)
         B = pts3D.size(0)
         N = self.W * self.W
         assert pts3D.numel() == B * N, "project_pts expects one depth per grid point"
         depth = _f32c(pts3D)
         out = torch.empty(B, 3, N, dtype=torch.float32, device=depth.device)
-        rc = _lib.lib().ps_project_pts_f32(_lib.ptr(depth), _lib.ptr(_f32c(K)), _lib.ptr(_f32c(K_inv)),
-                                           _lib.ptr(_f32c(RTinv_cam1)), _lib.ptr(_f32c(RT_cam2)), B, self.W,
-                                           _lib.ptr(out), _lib.current_stream())
-        _lib.check(rc, "ps_project_pts_f32")
+        _lib.call("ps_project_pts_f32", depth, _f32c(K), _f32c(K_inv), _f32c(RTinv_cam1), _f32c(RT_cam2), B, self.W, out)
         return out
 
     # ------------------------------------------------------------------ a3
@@ -60,20 +56,15 @@ class PtsManipulator(nn.Module):
         """Reference :85-107 -> (features (B,C,W,W), background_mask (B,W,W) bool)."""
         bs, c, w, h = src.size()
         if len(pred_pts.size()) > 3 and w == self.W and h == self.W:
-            _lib.require_cuda(src, pred_pts, K, K_inv, RTinv_cam1, RT_cam2)
             sp = self.splatter
             S = self.W
             out = torch.empty(bs, c, S, S, dtype=torch.float32, device=src.device)
             bg = torch.empty(bs, S, S, dtype=torch.uint8, device=src.device)
             ws = splat_workspace(src.device, bs, S * S, S, sp.radius)
-            rc = _lib.lib().ps_project_splat_f32(
-                _lib.ptr(_f32c(pred_pts)), _lib.ptr(_f32c(src)), _lib.ptr(_f32c(K)), _lib.ptr(_f32c(K_inv)),
-                _lib.ptr(_f32c(RTinv_cam1)), _lib.ptr(_f32c(RT_cam2)), bs, c, S, float(sp.radius),
-                int(sp.points_per_pixel), float(sp._opt("tau", 1.0)), int(sp._opt("rad_pow", 2)),
-                ACCUMULATION[sp._opt("accumulation", "alphacomposite")],
-                int(sp._opt("background_smoothing_kernel_size", 13)), _lib.ptr(out), _lib.ptr(bg), _lib.ptr(ws),
-                ws.numel(), _lib.current_stream())
-            _lib.check(rc, "ps_project_splat_f32")
+            _lib.call("ps_project_splat_f32", _f32c(pred_pts), _f32c(src), _f32c(K), _f32c(K_inv), _f32c(RTinv_cam1), _f32c(RT_cam2), bs, c, S,
+                      float(sp.radius), int(sp.points_per_pixel), float(sp._opt("tau", 1.0)), int(sp._opt("rad_pow", 2)),
+                      ACCUMULATION[sp._opt("accumulation", "alphacomposite")], int(sp._opt("background_smoothing_kernel_size", 13)),
+                      out, bg, ws, ws.numel())
             return out, bg.view(torch.bool)    # (k_dilate writes 0 / 1: the same bytes are the boolean mask -- no conversion pass)
         if len(pred_pts.size()) > 3:
             pred_pts = pred_pts.view(bs, 1, -1)
@@ -113,7 +104,6 @@ class PtsManipulator(nn.Module):
     def project_pts_cumulative(self, pts3D, K, K_inv, RT_cam1, RTinv_cam1, RT_cam2, RTinv_cam2,
                                prior_point_cloud=None, last_background_mask=None, RTinv_cam3=None):
         """Reference :221-266 -> (sampler (B,3,NT), xy_proj (B,4,NT))."""
-        _lib.require_cuda(pts3D, K, K_inv, RTinv_cam1, RT_cam2)
         B = pts3D.size(0)
         depth = _f32c(pts3D).view(B, pts3D.numel() // B)
         n_new = depth.size(1)
@@ -128,9 +118,6 @@ class PtsManipulator(nn.Module):
         cloud = torch.empty(B, 4, NT, dtype=torch.float32, device=depth.device)
         prior = None if prior_point_cloud is None else _f32c(prior_point_cloud)
         rt3 = None if RTinv_cam3 is None else _f32c(RTinv_cam3)
-        rc = _lib.lib().ps_project_pts_cumulative_f32(
-            _lib.ptr(depth), _lib.ptr(new_index), _lib.ptr(prior), _lib.ptr(_f32c(K)), _lib.ptr(_f32c(K_inv)),
-            _lib.ptr(_f32c(RTinv_cam1)), _lib.ptr(_f32c(RT_cam2)), _lib.ptr(rt3), B, self.W, n_new, n_prior,
-            _lib.ptr(sampler), _lib.ptr(cloud), _lib.current_stream())
-        _lib.check(rc, "ps_project_pts_cumulative_f32")
+        _lib.call("ps_project_pts_cumulative_f32", depth, new_index, prior, _f32c(K), _f32c(K_inv), _f32c(RTinv_cam1), _f32c(RT_cam2), rt3,
+                  B, self.W, n_new, n_prior, sampler, cloud)
         return sampler, cloud

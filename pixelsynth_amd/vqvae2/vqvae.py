@@ -91,14 +91,13 @@ class _FastPath:
 
     def __init__(self, m, device):
         self.device = device
-        self.L = L = _lib.lib()
 
         def conv(c):
             return c.weight.detach().float(), c.bias.detach().float()
 
         def conv1(c):
             w, b = conv(c)
-            if not L.ps_conv1x1_takes(w.size(1), w.size(0)):
+            if not _lib.call("ps_conv1x1_takes", w.size(1), w.size(0)):
                 raise ValueError("VQ-VAE fast path: a %d -> %d 1 x 1 convolution" % (w.size(1), w.size(0)))
             return w.reshape(w.size(0), w.size(1)).contiguous(), b.contiguous()
 
@@ -164,8 +163,7 @@ class _FastPath:
         B, _, H, W = x.shape
         Co, Ci = w.shape
         y = torch.empty((B, Co, H, W), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
-        _lib.check(self.L.ps_conv1x1_ex_nhwc_f32(x.data_ptr(), ldx, w.data_ptr(), bias.data_ptr(), None if res is None else res.data_ptr(), flags,
-                                                 B * H * W, Ci, Co, y.data_ptr(), _lib.current_stream()), "ps_conv1x1_ex_nhwc_f32")
+        _lib.call("ps_conv1x1_ex_nhwc_f32", x, ldx, w, bias, res, flags, B * H * W, Ci, Co, y)
         return y
 
     def res(self, x, r):
@@ -180,8 +178,7 @@ class _FastPath:
         if self.ends:                                                  # 3 -> 64 at half size, written as the 2 x 2 blocks the next layer reads
             s = torch.empty(B, H // 4, W // 4, 4 * eb[0].out_channels, device=input.device)
             x = input.contiguous()
-            _lib.check(self.L.ps_vq_stem_s2d_f32(x.data_ptr(), self.stem_w.data_ptr(), self.stem_b.data_ptr(), B, H, W, s.data_ptr(),
-                                                 _lib.current_stream()), "ps_vq_stem_s2d_f32")
+            _lib.call("ps_vq_stem_s2d_f32", x, self.stem_w, self.stem_b, B, H, W, s)
             s = s.permute(0, 3, 1, 2)
         else:
             s = _s2d(F.conv2d(input, eb[0].weight, eb[0].bias, 2, 1))
@@ -210,8 +207,7 @@ class _FastPath:
         if self.ends:                                                  # ReLU, 64 -> 3 at twice the size: the image, NCHW
             B, _, Hh, Wh = h.shape
             img = torch.empty(B, 3, 2 * Hh, 2 * Wh, device=h.device)
-            _lib.check(self.L.ps_vq_head_f32(h.data_ptr(), self.head_w.data_ptr(), self.head_b.data_ptr(), B, Hh, Wh, img.data_ptr(),
-                                             _lib.current_stream()), "ps_vq_head_f32")
+            _lib.call("ps_vq_head_f32", h, self.head_w, self.head_b, B, Hh, Wh, img)
             return img
         return F.conv_transpose2d(F.relu(h), dc[6].weight, dc[6].bias, 2, 1).contiguous()
 
@@ -227,13 +223,10 @@ class Quantize(nn.Module):
 
     def nearest(self, z, layout, hw=1):
         """z: (N,dim) [layout 0] or (B,dim,HW) [layout 1], float32 CUDA -> int32 codes (N,)."""
-        _lib.require_cuda(z, self.embed)
         z = z.contiguous()
         n = z.numel() // self.dim
         idx = torch.empty(n, dtype=torch.int32, device=z.device)
-        rc = _lib.lib().ps_vq_nearest_f32(_lib.ptr(z), layout, _lib.ptr(self.embed.contiguous()), n, self.dim, self.n_embed, hw,
-                                          _lib.ptr(idx), None, _lib.current_stream())
-        _lib.check(rc, "ps_vq_nearest_f32")
+        _lib.call("ps_vq_nearest_f32", z, layout, self.embed.contiguous(), n, self.dim, self.n_embed, hw, idx, None)
         return idx
 
     def forward(self, input):
@@ -251,13 +244,10 @@ class Quantize(nn.Module):
 
     def embed_grid(self, codes):
         """codes (B,H,W) int -> (B,dim,H,W): embed_code + permute(0,3,1,2) in one gather kernel."""
-        _lib.require_cuda(codes, self.embed)
         B, H, W = codes.shape
         c32 = codes.to(torch.int32).contiguous()
         out = torch.empty(B, self.dim, H, W, dtype=torch.float32, device=codes.device)
-        rc = _lib.lib().ps_vq_embed_f32(_lib.ptr(c32), _lib.ptr(self.embed.contiguous()), B, H * W, self.dim, self.n_embed,
-                                        _lib.ptr(out), _lib.current_stream())
-        _lib.check(rc, "ps_vq_embed_f32")
+        _lib.call("ps_vq_embed_f32", c32, self.embed.contiguous(), B, H * W, self.dim, self.n_embed, out)
         return out
 
 

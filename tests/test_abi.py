@@ -52,6 +52,56 @@ def test_error_channel():
     assert L.ps_splat_workspace_bytes(1, 65536, 256, 4.0) > 65536 * 8
 
 
+def header_prototypes():
+    """{name: [parameter text]} of every prototype of the two headers (comments stripped)."""
+    protos = {}
+    for name in ("pixelsynth_hip.h", "pixelsynth_hip_debug.h"):
+        txt = open(os.path.join(ROOT, "include", name)).read()
+        txt = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", txt, flags=re.S))
+        for fn, params in re.findall(r"\b(ps_[a-z0-9_]+)\s*\(([^;{)]*)\)\s*;", txt):
+            protos[fn] = [p.strip() for p in params.split(",")] if params.strip() not in ("", "void") else []
+    return protos
+
+
+def test_bindings_match_the_header_prototypes():
+    """Every _PROTOS entry has as many arguments as its prototype, and the entries marked STREAM are exactly the prototypes that end
+    in `void *stream`: the ones call() appends the current stream to."""
+    protos = header_prototypes()
+    assert len(protos) == 69 and set(protos) == set(_lib._PROTOS)
+    for name, (_, args) in _lib._PROTOS.items():
+        assert len(args) == len(protos[name]), (name, len(args), protos[name])
+    ends_in_stream = {n for n, p in protos.items() if p and re.fullmatch(r"void\s*\*\s*stream", p[-1])}
+    assert len(ends_in_stream) == 42
+    assert {n for n, (_, args) in _lib._PROTOS.items() if args and args[-1] is _lib.STREAM} == ends_in_stream
+    assert all(a is not _lib.STREAM for _, args in _lib._PROTOS.values() for a in args[:-1])
+
+
+def test_call_refuses_host_tensors_before_touching_a_stream():
+    """A CPU tensor handed to an entry point that queues work is an error naming the function and the argument -- raised before a
+    stream is looked up, so it holds without a GPU; a wrong argument count is a TypeError naming the function."""
+    import torch
+    cpu = [torch.zeros(4, 4) for _ in range(5)]
+    with pytest.raises(RuntimeError, match=r"ps_project_pts_f32: args\[0\] is a CPU tensor.*no CPU fallback"):
+        _lib.call("ps_project_pts_f32", *cpu, 1, 16, torch.zeros(1, 3, 256))
+    with pytest.raises(TypeError, match="ps_project_pts_f32 takes 8 arguments besides the stream, got 7"):
+        _lib.call("ps_project_pts_f32", *cpu, 1, 16)
+    with pytest.raises(TypeError, match="ps_custom_order takes no stream"):
+        _lib.call("ps_custom_order", 3, 4, None, None, stream=0)
+
+
+def test_call_checks_status_and_returns_queries():
+    with pytest.raises(RuntimeError, match=r"ps_custom_order failed \(rc=-\d+\): .*null"):
+        _lib.call("ps_custom_order", 3, 4, None, None)
+    assert _lib.call("ps_conv1x1_takes", 3, 5) == 0                  # a query: 0 is an answer, not a failure
+    assert _lib.call("ps_conv1x1_takes", 64, 64) == 1
+    assert _lib.call("ps_abi_version") == 2
+    assert _lib.call("ps_splat_workspace_bytes", 0, 10, 16, 4.0) == 0
+    order = np.empty((16, 2), np.int32)
+    D = np.arange(16, dtype=np.int64).reshape(4, 4)
+    assert _lib.call("ps_custom_order", 4, 4, D, order) == 0          # host-only: numpy arrays as their data pointers
+    assert sorted(order[:, 0] * 4 + order[:, 1]) == list(range(16))
+
+
 def test_custom_order_matches_oracle():
     L = _lib.lib()
     for name, D in syn.distance_maps():

@@ -854,7 +854,6 @@ def test_prefix_pass_evaluates_only_what_is_read(F_, first):
     """The whole-grid pass over the observed prefix skips, stage by stage, the items nobody reads (k_prefix_starts): the
     device's (33, F) table of start ranks equals the numpy restatement (oracle/prefix_cone_oracle.py), and codes and
     logits are bit-identical to a run that evaluates the whole prefix at every stage (tuning value prefix_full)."""
-    import ctypes
     from oracle import prefix_cone_oracle as pc
     from pixelsynth_amd import _lib
     from pixelsynth_amd.lmconv.model import wavefronts
@@ -884,9 +883,7 @@ def test_prefix_pass_evaluates_only_what_is_read(F_, first):
     c_cone, l_cone = run()
     eng.set_tuning(prefix_cone_force=0)
     # the table the prefix pass just used
-    L = _lib.lib()
-    L.ps_pixelcnn_debug_cache.restype = ctypes.c_void_p
-    ptr = L.ps_pixelcnn_debug_cache(eng.handle, 5, 0)
+    ptr = _lib.call("ps_pixelcnn_debug_cache", eng.handle, 5, 0)
     assert ptr
     raw = type("Raw", (), {"__cuda_array_interface__": {"shape": (pc.N_EVAL, F_), "typestr": "<i4", "data": (ptr, False), "version": 2}})()
     torch.cuda.synchronize()
@@ -910,7 +907,6 @@ def test_prefix_cone_on_other_grids_and_random_orders(H, W):
     """k_prefix_starts on a square and a non-square grid with RANDOM generation orders (where the cone of a stage is far
     from a suffix of the prefix, so the start ranks give away a lot -- but never too little): device table == numpy
     restatement, codes and walked logits identical to the full prefix."""
-    import ctypes
     from oracle import prefix_cone_oracle as pc
     from pixelsynth_amd import _lib
     net = make_net(6)
@@ -936,9 +932,7 @@ def test_prefix_cone_on_other_grids_and_random_orders(H, W):
     eng.set_tuning(prefix_cone_force=1)
     c_cone, l_cone = run()
     eng.set_tuning(prefix_cone_force=0)
-    lib = _lib.lib()
-    lib.ps_pixelcnn_debug_cache.restype = ctypes.c_void_p
-    ptr = lib.ps_pixelcnn_debug_cache(eng.handle, 5, 0)
+    ptr = _lib.call("ps_pixelcnn_debug_cache", eng.handle, 5, 0)
     raw = type("Raw", (), {"__cuda_array_interface__": {"shape": (pc.N_EVAL, F_), "typestr": "<i4", "data": (ptr, False), "version": 2}})()
     torch.cuda.synchronize()
     got = torch.as_tensor(raw, device=DEV).clone().cpu().numpy()
