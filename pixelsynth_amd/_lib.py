@@ -96,6 +96,18 @@ _PROTOS = {
 }
 
 
+# libpixelsynth_percsim.so (include/pixelsynth_percsim.h): the PercSim passes, a library of their own beside this one
+PERCSIM_LIB_PATH = os.path.join(_HERE, "libpixelsynth_percsim.so")
+PERCSIM_PROTOS = {
+    "ps_percsim_last_error": (ctypes.c_char_p, []),
+    "ps_percsim_workspace_bytes": (c_size_t, [c_int] * 3),
+    "ps_percsim_input": (RC, [c_void_p] * 4 + [c_int, c_void_p] + [c_int] * 4 + [c_void_p, c_void_p, STREAM]),
+    "ps_percsim_tap": (RC, [c_void_p] + [c_int] * 5 + [c_void_p, c_void_p, c_size_t, STREAM]),
+    "ps_percsim_finish": (RC, [c_void_p, c_size_t] + [c_int] * 3 + [c_void_p, c_void_p, STREAM]),
+}
+_percsim = None
+
+
 def exported_symbols():
     """Names every entry point include/pixelsynth_hip.h and include/pixelsynth_hip_debug.h declare (used by the CPU load test)."""
     return sorted(_PROTOS)
@@ -121,9 +133,25 @@ def lib():
     return _lib
 
 
+def percsim_lib():
+    global _percsim
+    if _percsim is None:
+        lib()                          # (the runtime binding: see lib())
+        if not os.path.exists(PERCSIM_LIB_PATH):
+            raise RuntimeError(f"{PERCSIM_LIB_PATH} is missing: build it with `python -m pixelsynth_amd.build` "
+                               "(there is no CPU/PyTorch fallback for the HIP path)")
+        L = ctypes.CDLL(PERCSIM_LIB_PATH)
+        for name, (res, args) in PERCSIM_PROTOS.items():
+            fn = getattr(L, name)
+            fn.restype = c_int if res is RC else res
+            fn.argtypes = [c_void_p if a is STREAM else a for a in args]
+        _percsim = L
+    return _percsim
+
+
 def check(rc, what):
     if rc != 0:
-        msg = lib().ps_last_error()
+        msg = (percsim_lib().ps_percsim_last_error() if what in PERCSIM_PROTOS else lib().ps_last_error())
         raise RuntimeError(f"{what} failed (rc={rc}): {msg.decode() if msg else '?'}")
 
 
@@ -132,16 +160,16 @@ _POINTERS = (c_void_p, ctypes.c_char_p, ctypes.c_wchar_p)
 
 
 def call(name, *args, stream=None):
-    """The entry point `name` of _PROTOS on args: a torch tensor or numpy array goes as its data pointer, None as NULL, a ctypes
+    """The entry point `name` of _PROTOS (or PERCSIM_PROTOS) on args: a torch tensor or numpy array goes as its data pointer, None as NULL, a ctypes
     scalar or array (an out-parameter, a small host table) by reference; anything else (ints, floats, bytes, the engine's handle) as
     ctypes converts it.  An entry point that ends in a STREAM gets the current stream appended (or `stream`), and each of its tensor
     arguments must be a CUDA tensor on the current device: else RuntimeError, before anything is queued.  A nonzero RC raises
     RuntimeError (check); any other return value is handed back."""
-    res, types = _PROTOS[name]
+    res, types = _PROTOS[name] if name in _PROTOS else PERCSIM_PROTOS[name]
     queued = bool(types) and types[-1] is STREAM
     if len(args) != len(types) - queued:
         raise TypeError(f"{name} takes {len(types) - queued} arguments{' besides the stream' if queued else ''}, got {len(args)}")
-    fn = getattr(lib(), name)
+    fn = getattr(lib() if name in _PROTOS else percsim_lib(), name)
     conv, device = list(args), None
     for i, a in enumerate(args):
         if isinstance(a, torch.Tensor):

@@ -2,7 +2,8 @@
 
     python -m pixelsynth_amd.build [--force]
 
-One object per translation unit, linked into pixelsynth_amd/libpixelsynth_hip.so.  Both HIP units are built
+One object per translation unit, linked into pixelsynth_amd/libpixelsynth_hip.so; the PercSim passes (csrc/percsim.hip, declared in
+include/pixelsynth_percsim.h) into a library of their own next to it, libpixelsynth_percsim.so.  Both HIP units are built
 with -ffp-contract=off: splat.hip because its index paths must be bit-exact against the oracle, the lmconv*.hip units so
 that the post ops inlined into different kernels (whole-grid vs column step) round identically; the matrix
 products are explicit MFMA intrinsics and are not affected.
@@ -14,6 +15,8 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.environ.get("PS_HIP_LIB") or os.path.join(HERE, "libpixelsynth_hip.so")   # (PS_HIP_LIB: tuning builds, with PS_OBJ_SUFFIX)
+PERCSIM_LIB = os.path.join(HERE, "libpixelsynth_percsim.so")
+PERCSIM_UNITS = [("percsim.hip", ["-ffp-contract=off"])]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
 
@@ -42,13 +45,22 @@ if EXTRA:   # ps_build_info() (csrc/host_order.cpp) names them: a number measure
 def _deps():
     return [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")] + [
         os.path.join(os.path.dirname(HERE), "include", "pixelsynth_hip.h"),
-        os.path.join(os.path.dirname(HERE), "include", "pixelsynth_hip_debug.h")]
+        os.path.join(os.path.dirname(HERE), "include", "pixelsynth_hip_debug.h"),
+        os.path.join(os.path.dirname(HERE), "include", "pixelsynth_percsim.h")]
 
 
 def build(force=False, verbose=True):
+    """-> the path of libpixelsynth_hip.so; libpixelsynth_percsim.so is built beside it."""
+    _build(UNITS, LIB, force, verbose)
+    if not os.environ.get("PS_HIP_LIB"):
+        _build(PERCSIM_UNITS, PERCSIM_LIB, force, verbose)
+    return LIB
+
+
+def _build(units, lib, force, verbose):
     objs, todo = [], []
     dep_m = max(os.path.getmtime(d) for d in _deps())
-    for src, flags in UNITS:
+    for src, flags in units:
         sp = os.path.join(CSRC, src)
         if not os.path.exists(sp):
             continue
@@ -65,12 +77,12 @@ def build(force=False, verbose=True):
             subprocess.check_call(cmd)
         with ThreadPoolExecutor(max_workers=min(len(todo), max(1, (os.cpu_count() or 2) // 2))) as pool:
             list(pool.map(run, todo))
-    if force or not os.path.exists(LIB) or any(os.path.getmtime(o) > os.path.getmtime(LIB) for o in objs):
-        cmd = [HIPCC, "-shared", "-fPIC", f"--offload-arch={ARCH}", "-o", LIB] + objs
+    if force or not os.path.exists(lib) or any(os.path.getmtime(o) > os.path.getmtime(lib) for o in objs):
+        cmd = [HIPCC, "-shared", "-fPIC", f"--offload-arch={ARCH}", "-o", lib] + objs
         if verbose:
             print(" ".join(cmd), flush=True)
         subprocess.check_call(cmd)
-    return LIB
+    return lib
 
 
 if __name__ == "__main__":

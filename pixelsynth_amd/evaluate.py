@@ -1,12 +1,14 @@
-"""Score predicted views against ground truth: PSNR and SSIM on the HIP kernel (csrc/metrics.hip), the reference's
-calc_errors_quality.py without PercSim and FID (they need pretrained weights).
+"""Score predicted views against ground truth: PSNR and SSIM on the HIP kernel (csrc/metrics.hip) and, with --vgg16, PercSim (the
+VGG16 perceptual similarity, perceptual.py); the reference's calc_errors_quality.py without FID (it needs Inception weights).
 
-    python -m pixelsynth_amd.evaluate --pred DIR --gt DIR [--sampled DIR] [--max-img N] [--batch 64] [--json PATH]
+    python -m pixelsynth_amd.evaluate --pred DIR --gt DIR [--sampled DIR] [--max-img N] [--batch 64] [--json PATH] [--vgg16 PATH]
 
 Image i is <dir>/<i>.png in each directory.  Without --max-img, i runs from 0 as long as --pred has <i>.png; with it, every i < N must be
 there.  Images are read as RGB.  With --sampled, a pixel is "vis" where all channels of the ground truth equal the sampled image
 (calc_errors_quality.py:28-35), which adds PSNR_vis / PSNR_invis and SSIM_vis / SSIM_invis.  One line per metric, its mean over the
-images (PSNR clamped at 100 first, as the reference does).  --json writes the per-image rows and the means.
+images (PSNR clamped at 100 first, as the reference does).  --json writes the per-image rows and the means.  --vgg16 names VGG16
+weights (torchvision's vgg16-397923af.pth, or a PNet state dict; nothing is downloaded) and adds PercSim -- with --sampled also
+PercSim_invis and PercSim_vis, the images times the mask -- after the SSIM lines, means of the per-image values (no clamp).
 
 PNGs are decoded on a host thread pool (at most 16 threads), uploaded as pinned uint8 batches and scored on uint8 (the kernel converts
 x / 255, TF.to_tensor's values); the next batch decodes while the device scores this one, one synchronisation per batch.  Under
@@ -23,11 +25,13 @@ import torch
 
 from . import distributed as D
 from .image_metrics import COLUMNS, image_metrics
+from .perceptual import COLUMNS as PERCSIM_COLUMNS, perceptual_rows
 
 PSNR_CLAMP = 100.0
 # printed name -> column; the reference's names (calc_errors_quality.py:47-67) and their SSIM counterparts
 NAMES = {"PSNR": "psnr", "PSNR_invis": "psnr_invis", "PSNR_vis": "psnr_vis", "SSIM": "ssim", "SSIM_invis": "ssim_invis",
-         "SSIM_vis": "ssim_vis"}
+         "SSIM_vis": "ssim_vis", "PercSim": "percsim", "PercSim_invis": "percsim_invis", "PercSim_vis": "percsim_vis"}
+ALL_COLUMNS = COLUMNS + PERCSIM_COLUMNS     # the rows' columns with --vgg16
 
 
 def discover(pred, gt, sampled=None, max_img=None):
@@ -88,8 +92,9 @@ def _stage(decoded):
     return pred, gt, mask
 
 
-def score_files(items, device, batch=64, pool=None):
-    """-> (len(items), 6) float64 numpy rows (COLUMNS) of the (pred, gt, sampled) triples, in order."""
+def score_files(items, device, batch=64, pool=None, pnet=None):
+    """-> (len(items), 6) float64 numpy rows (COLUMNS) of the (pred, gt, sampled) triples, in order; with a PNet `pnet`
+    (len(items), 9) rows (ALL_COLUMNS)."""
     own = pool is None
     pool = pool or ThreadPoolExecutor(max_workers=_threads())
     try:
@@ -103,19 +108,24 @@ def score_files(items, device, batch=64, pool=None):
             pred, gt, mask = (None if t is None else t.to(device, non_blocking=True) for t in host)
             # (B, H, W, 3) storage read as (B, 3, H, W) through its strides: no copy
             out = image_metrics(gt.permute(0, 3, 1, 2), pred.permute(0, 3, 1, 2), mask)
+            if pnet is not None:
+                out = torch.cat([out, perceptual_rows(pnet, gt.permute(0, 3, 1, 2), pred.permute(0, 3, 1, 2), mask)], 1)
             rows.append(out.cpu().double().numpy())                               # the batch's one synchronisation
-        return np.concatenate(rows) if rows else np.zeros((0, 6))
+        return np.concatenate(rows) if rows else np.zeros((0, 6 if pnet is None else len(ALL_COLUMNS)))
     finally:
         if own:
             pool.shutdown()
 
 
-def summarize(rows, masked):
-    """-> {printed name: mean over images} in the reference's print order"""
+def summarize(rows, masked, percsim=False):
+    """-> {printed name: mean over images} in the reference's print order (utils/calc_errors.py:93-101); percsim: rows carry
+    ALL_COLUMNS"""
     names = ["PSNR", "PSNR_invis", "PSNR_vis", "SSIM", "SSIM_invis", "SSIM_vis"] if masked else ["PSNR", "SSIM"]
+    if percsim:
+        names += ["PercSim", "PercSim_invis", "PercSim_vis"] if masked else ["PercSim"]
     out = {}
     for name in names:
-        col = rows[:, COLUMNS.index(NAMES[name])].astype(np.float32)     # the reference averages float32 results
+        col = rows[:, ALL_COLUMNS.index(NAMES[name])].astype(np.float32)     # the reference averages float32 results
         if name.startswith("PSNR"):
             col = np.minimum(col, np.float32(PSNR_CLAMP))
         out[name] = float(np.mean([float(v) for v in col])) if len(col) else float("nan")
@@ -130,9 +140,12 @@ def main(argv=None):
     ap.add_argument("--max-img", type=int, help="score i < N (default: as long as --pred has <i>.png)")
     ap.add_argument("--batch", type=int, default=64, help="images per upload and launch")
     ap.add_argument("--json", help="write per-image rows and the means here")
+    ap.add_argument("--vgg16", help="VGG16 weights (vgg16-397923af.pth or a PNet state dict): adds PercSim")
     args = ap.parse_args(argv)
     if args.batch < 1:
         ap.error("--batch must be >= 1")
+    if args.vgg16 is not None and not os.path.isfile(args.vgg16):
+        ap.error(f"--vgg16 {args.vgg16}: no such file")
 
     rank, world = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1))
     local = 0 if os.environ.get("PS_DRYRUN_ONE_GPU") == "1" else int(os.environ.get("LOCAL_RANK", 0))
@@ -150,17 +163,23 @@ def main(argv=None):
         items = discover(args.pred, args.gt, args.sampled, args.max_img)
         n = len(items)
         mine = D.shard_views(n, rank, world)
-        local_rows = score_files([items[i] for i in mine], device, args.batch)
-        rows = D.gather_rows(local_rows.T, n).T                                    # (n, 6), image order
+        pnet = None
+        if args.vgg16 is not None:
+            from .networks.pretrained_networks import PNet
+            pnet = PNet(use_gpu=True, weights=args.vgg16)
+        local_rows = score_files([items[i] for i in mine], device, args.batch, pnet=pnet)
+        rows = D.gather_rows(local_rows.T, n).T                                    # (n, 6) -- 9 with --vgg16 --, image order
         masked = args.sampled is not None
-        means = summarize(rows, masked)
+        means = summarize(rows, masked, pnet is not None)
         if rank == 0:
             for name, v in means.items():
                 print("%s \t %0.5f" % (name, v))
             if args.json:
                 cols = COLUMNS if masked else ("psnr", "ssim")
+                if pnet is not None:
+                    cols = cols + (PERCSIM_COLUMNS if masked else ("percsim",))
                 doc = {"n": n, "pred": args.pred, "gt": args.gt, "sampled": args.sampled, "psnr_clamp": PSNR_CLAMP, "means": means,
-                       "rows": [dict(index=i, **{c: float(rows[i, COLUMNS.index(c)]) for c in cols}) for i in range(n)]}
+                       "rows": [dict(index=i, **{c: float(rows[i, ALL_COLUMNS.index(c)]) for c in cols}) for i in range(n)]}
                 with open(args.json, "w") as fh:
                     json.dump(doc, fh, indent=1)
     finally:

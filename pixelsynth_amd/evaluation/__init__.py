@@ -1,16 +1,19 @@
-"""Quality of rendered views (the reference's evaluation/, calc_errors_quality.py): PSNR and SSIM on the HIP kernel, overall and split
-into the pixels the splat covered ("vis") and the outpainted ones ("invis").  PercSim (VGG / AlexNet weights), FID (Inception weights)
-and the homography consistency score (OpenCV and the reference's point files) are not provided."""
+"""Quality of rendered views (the reference's evaluation/, calc_errors_quality.py): PSNR and SSIM on the HIP kernel, and PercSim (the
+VGG16 perceptual similarity: perceptual.py, networks/pretrained_networks.PNet) when the caller passes a PNet, overall and split into the
+pixels the splat covered ("vis") and the outpainted ones ("invis").  FID (Inception weights, pytorch_fid), LPIPS and the homography
+consistency score (OpenCV and the reference's point files) are not provided."""
 from ..image_metrics import COLUMNS, image_metrics
+from ..perceptual import COLUMNS as PERCSIM_COLUMNS, perceptual_rows
 
-__all__ = ["score_views", "COLUMNS"]
+__all__ = ["score_views", "COLUMNS", "PERCSIM_COLUMNS"]
 
 
-def score_views(pred, gt, background_mask=None):
+def score_views(pred, gt, background_mask=None, pnet=None):
     """pred, gt (B, 3, H, W) frames in the model's [-1, 1] space (mapped by 0.5 x + 0.5, as base_model.py:97-99 does before
     scoring); background_mask (B, H, W) bool, True where no point was splatted (outpaint_views / synthesize_views) -- "vis" is
     ~background_mask, "invis" the outpainted region.  -> dict of (B,) f32 tensors: psnr, ssim, and with a mask the vis / invis
-    columns as well."""
+    columns as well; with a PNet `pnet` also percsim (and with a mask percsim_vis / percsim_invis), the masked variants scoring the
+    images times the mask as calc_errors_quality.py does."""
     a, b = pred * 0.5 + 0.5, gt * 0.5 + 0.5
     mask = None
     if background_mask is not None:
@@ -19,4 +22,9 @@ def score_views(pred, gt, background_mask=None):
         mask = (~background_mask.bool()).unsqueeze(1)
     rows = image_metrics(a, b, mask)
     keep = COLUMNS if mask is not None else ("psnr", "ssim")
-    return {k: rows[:, COLUMNS.index(k)] for k in keep}
+    out = {k: rows[:, COLUMNS.index(k)] for k in keep}
+    if pnet is not None:
+        prow = perceptual_rows(pnet, a, b, mask)
+        for k in PERCSIM_COLUMNS if mask is not None else ("percsim",):
+            out[k] = prow[:, PERCSIM_COLUMNS.index(k)]
+    return out

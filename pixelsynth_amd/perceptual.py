@@ -1,0 +1,166 @@
+"""PercSim of image pairs on the ROCm device: the binding of csrc/percsim.hip around the split-fp16 convolutions, for a PNet
+(networks/pretrained_networks.py).
+
+perceptual_rows(pnet, img1, img2, mask=None) -> (B, 3) f32 tensor, columns COLUMNS.  img1, img2 (B, 3, H, W), float32 in [0, 1] or
+uint8 (converted in the kernel as x / 255, TF.to_tensor's values), any strides (NCHW or channels-last storage, read in place); mask
+(B, 1, H, W): "vis" scores img * m, "invis" img * (1 - m), as the reference's calc_errors_quality.py does; without a mask those columns
+are NaN.  The three variants share one network pass.  Everything is checked before the first launch; a CPU tensor is an error (no CPU
+fallback).  H and W multiples of 256 run on the HIP path, any other size through the torch formula on the device.
+
+A network pass: the input pass writes 2P standardised images (B, H, W, 4) (the P first are in0 of the pairs, the next P their in1);
+conv1_1 (ps_conv3x3_thin_in_f16x3_nhwc, no bias), conv1_2 (act shift = -bias of conv1_1, its own bias on the way out), then per tap
+ps_percsim_tap on the layer's pre-ReLU output -- the cosine partial sums and, for the first four, the max-pooled input of the next slice,
+whose convolutions apply the ReLU on the way in -- and ps_percsim_finish.  Passes are cut so that one activation map stays near 1 GiB;
+a pass is a guarded scope (networks.f16x3.checked).
+"""
+import ctypes
+
+import torch
+
+from . import _lib
+from .networks import f16x3
+
+COLUMNS = ("percsim", "percsim_vis", "percsim_invis")
+_DTYPES = {torch.float32: 0, torch.uint8: 1}             # PS_DTYPE_F32, PS_DTYPE_U8
+PLAIN, VIS, INVIS, RAW = 0, 1, 2, 3                       # PS_PERCSIM_*
+_LEVELS = ((0, 1), (2, 3), (4, 5, 6), (7, 8, 9), (10, 11, 12))    # the convolutions before each tap
+_MAP_BYTES = 1 << 30                                      # one activation map of a pass at most (the 64-channel maps at full size)
+
+
+def pairs_per_pass(H, W):
+    return max(1, min(65535, _MAP_BYTES // (2 * H * W * 64 * 4)))
+
+
+def _nhwc(N, C, H, W, dev):
+    return torch.empty((N, C, H, W), dtype=torch.float32, device=dev, memory_format=torch.channels_last)
+
+
+def _network(layers, x, P, H, W):
+    """The pass over x (2P, 4, H, W) channels_last (the input pass's output) -> (layers (P, 5), total (P)) f32."""
+    dev, N = x.device, 2 * P
+    ones = torch.ones(N * 512, dtype=torch.float32, device=dev)
+    zeros = torch.zeros(N * 512, dtype=torch.float32, device=dev)
+    relu = lambda C: (ones[:N * C].view(N, C), zeros[:N * C].view(N, C))     # act(x) = max(x * 1 - 0, 0)
+    nbytes = _lib.call("ps_percsim_workspace_bytes", P, H, W)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    h = None
+    for level, convs in enumerate(_LEVELS):
+        for i in convs:
+            if i == 0:
+                h = _nhwc(N, 64, H, W, dev)
+                _lib.call("ps_conv3x3_thin_in_f16x3_nhwc", x, None, None, layers["w0"], N, H, W, 64, h, f16x3.flag(dev))
+            elif i == 1:       # conv1_1's bias enters as the act's shift: max(y + b, 0)
+                h = f16x3.conv3x3(h, layers["packed"][0], ones[:N * 64].view(N, 64), (-layers["b0"]).expand(N, 64).contiguous())
+            else:
+                p = layers["packed"][i - 1]
+                h = f16x3.conv3x3(h, p, *relu(p["Ci"]))
+        C, Hl, Wl = h.shape[1:]
+        pooled = _nhwc(N, C, Hl // 2, Wl // 2, dev) if level < 4 else None
+        _lib.call("ps_percsim_tap", h, P, H, W, level, C, pooled, ws, nbytes)
+        h = pooled
+    per_layer = torch.empty(P, 5, dtype=torch.float32, device=dev)
+    total = torch.empty(P, dtype=torch.float32, device=dev)
+    _lib.call("ps_percsim_finish", ws, nbytes, P, H, W, per_layer, total)
+    return per_layer, total
+
+
+def _strides(t):
+    return (ctypes.c_int64 * 4)(*t.stride())
+
+
+def _passes(pnet, img1, img2, mask, modes):
+    """Network passes over the pairs (img1, img2) in each mode of `modes` (one row block per mode) -> (total (len(modes), B),
+    layers (len(modes), B, 5)), on the HIP path.  Inside the caller's guarded scope."""
+    B, _, H, W = img1.shape
+    dev = img1.device
+    layers = pnet.hip_layers(dev)
+    V = len(modes)
+    per = max(1, pairs_per_pass(H, W) // V)
+    total = torch.empty(V, B, dtype=torch.float32, device=dev)
+    per_layer = torch.empty(V, B, 5, dtype=torch.float32, device=dev)
+    for b0 in range(0, B, per):
+        b1 = min(B, b0 + per)
+        n, P = b1 - b0, (b1 - b0) * V
+        x = torch.empty((2 * P, H, W, 4), dtype=torch.float32, device=dev)
+        a, b = img1[b0:b1], img2[b0:b1]
+        m = None if mask is None else mask[b0:b1]
+        for v, mode in enumerate(modes):
+            _lib.call("ps_percsim_input", a, _strides(a), b, _strides(b), _DTYPES[img1.dtype], m if mode in (VIS, INVIS) else None,
+                      mode, n, H, W, x[v * n:(v + 1) * n], x[P + v * n:P + (v + 1) * n])
+        pl, tot = _network(layers, x.permute(0, 3, 1, 2), P, H, W)
+        total[:, b0:b1] = tot.view(V, n)
+        per_layer[:, b0:b1] = pl.view(V, n, 5)
+    return total, per_layer
+
+
+def pnet_pairs(pnet, in0, in1):
+    """PNet.forward's HIP path: in0, in1 (N, 3, H, W) fp32 in [-1, 1] on the device (pnet.hip_takes) -> (total (N,), layers (N, 5)).
+    A guarded scope: its fp32 rerun goes through pnet.torch_forward."""
+    def run():
+        if f16x3.forced_mode() == "fp32":
+            tot, pl = pnet.torch_forward(in0, in1, retPerLayer=True)
+            return tot, torch.stack(pl, 1)
+        with torch.cuda.device(in0.device):
+            tot, pl = _passes(pnet, in0, in1, None, (RAW,))
+        return tot[0], pl[0]
+    return f16x3.checked(in0.device, run)
+
+
+def _check(pnet, img1, img2, mask):
+    if not hasattr(pnet, "hip_takes") or not hasattr(pnet, "torch_forward"):
+        raise TypeError("pnet must be a networks.pretrained_networks.PNet")
+    for name, t in (("img1", img1), ("img2", img2)):
+        if not torch.is_tensor(t):
+            raise TypeError(f"{name} must be a tensor")
+        if t.dim() != 4:
+            raise ValueError(f"{name} must be (B, 3, H, W), got shape {tuple(t.shape)}")
+    if img1.shape != img2.shape:
+        raise ValueError(f"img1 and img2 differ in shape: {tuple(img1.shape)} vs {tuple(img2.shape)}")
+    B, C, H, W = img1.shape
+    if C != 3:
+        raise ValueError(f"C must be 3, got {C}")
+    if B < 1 or H < 1 or W < 1:
+        raise ValueError(f"empty image batch {tuple(img1.shape)}")
+    if img1.dtype != img2.dtype or img1.dtype not in _DTYPES:
+        raise TypeError(f"img1 and img2 must both be float32 or both uint8, got {img1.dtype} and {img2.dtype}")
+    if mask is not None:
+        if not torch.is_tensor(mask) or tuple(mask.shape) != (B, 1, H, W):
+            raise ValueError(f"mask must be (B, 1, H, W) = {(B, 1, H, W)}, got {tuple(getattr(mask, 'shape', ()))}")
+        if not (mask.dtype.is_floating_point or mask.dtype == torch.bool):
+            raise TypeError(f"mask must be floating point or bool, got {mask.dtype}")
+    _lib.require_cuda(img1, img2, mask)
+    devs = {t.device for t in (img1, img2, mask) if t is not None}
+    if len(devs) != 1:
+        raise ValueError(f"img1, img2 and mask must be on one device, got {sorted(map(str, devs))}")
+
+
+def _torch_rows(pnet, img1, img2, mask):
+    """The same rows through pnet.torch_forward: the images converted with the input pass's fp32 operations, in its order."""
+    a, b = ((t.float() / 255.0 if t.dtype == torch.uint8 else t) for t in (img1, img2))
+    out = torch.full((a.size(0), 3), float("nan"), dtype=torch.float32, device=a.device)
+    out[:, 0] = pnet.torch_forward(a * 2 - 1, b * 2 - 1)
+    if mask is not None:
+        for col, m in ((1, mask), (2, 1 - mask)):
+            out[:, col] = pnet.torch_forward(a * m * 2 - 1, b * m * 2 - 1)
+    return out
+
+
+def perceptual_rows(pnet, img1, img2, mask=None):
+    _check(pnet, img1, img2, mask)
+    B, _, H, W = img1.shape
+    dev = img1.device
+    if mask is not None:
+        mask = mask.to(torch.float32).contiguous()
+    probe = torch.empty((1, 3, H, W), dtype=torch.float32, device=dev)   # what the HIP path takes (no data is read)
+    modes = (PLAIN,) if mask is None else (PLAIN, VIS, INVIS)
+
+    def run():
+        if not pnet.hip_takes(probe, probe):
+            return _torch_rows(pnet, img1, img2, mask)
+        with torch.cuda.device(dev):
+            total, _ = _passes(pnet, img1, img2, mask, modes)
+        out = torch.full((B, 3), float("nan"), dtype=torch.float32, device=dev)
+        out[:, :len(modes)] = total.t()
+        return out
+    with torch.no_grad():
+        return f16x3.checked(dev, run)

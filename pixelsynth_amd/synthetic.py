@@ -365,3 +365,20 @@ def metric_mask(kind, seed, B, H, W):
     yy, xx = np.meshgrid(np.arange(H), np.arange(W), indexing="ij")
     m = {"empty": np.zeros((H, W), bool), "full": np.ones((H, W), bool), "ragged": (xx + (yy // 3) % 11) >= (W * 3) // 5}[kind]
     return np.ascontiguousarray(np.broadcast_to(m.astype(np.float32), (B, 1, H, W)))
+
+
+def vgg16_state_dict(seed=0):
+    """VGG16 weights in torchvision's format (features.{0, 2, 5, ..., 28}.weight / .bias, float32) for PercSim's network
+    (networks/pretrained_networks.py): He-normal weights, std sqrt(2 / (9 Ci)), and N(0, 0.01^2) biases.  Of the order of real VGG16
+    weights (1e-2), so that the low halves of the split-fp16 operands fall into fp16's subnormal range as they do there."""
+    rs = np.random.RandomState(seed)
+    cfg = (64, 64, "M", 128, 128, "M", 256, 256, 256, "M", 512, 512, 512, "M", 512, 512, 512)
+    out, ci, i = {}, 3, 0
+    for v in cfg:
+        if v == "M":
+            i += 1
+            continue
+        out[f"features.{i}.weight"] = (rs.randn(v, ci, 3, 3) * math.sqrt(2.0 / (9 * ci))).astype(np.float32)
+        out[f"features.{i}.bias"] = (rs.randn(v) * 0.01).astype(np.float32)
+        ci, i = v, i + 2
+    return out
