@@ -107,6 +107,16 @@ PERCSIM_PROTOS = {
 }
 _percsim = None
 
+# libpixelsynth_consistency.so (include/pixelsynth_consistency.h): the homography consistency score, a library of its own as well
+CONSISTENCY_LIB_PATH = os.path.join(_HERE, "libpixelsynth_consistency.so")
+CONSISTENCY_PROTOS = {
+    "ps_consistency_last_error": (ctypes.c_char_p, []),
+    "ps_consistency_workspace_bytes": (c_size_t, [c_int] * 3),
+    "ps_consistency": (RC, [c_void_p] * 4 + [c_int, c_void_p, c_void_p, c_int, c_void_p] + [c_int] * 4 + [c_void_p, c_void_p, c_void_p,
+                                                                                                         c_size_t, STREAM]),
+}
+_consistency = None
+
 
 def exported_symbols():
     """Names every entry point include/pixelsynth_hip.h and include/pixelsynth_hip_debug.h declare (used by the CPU load test)."""
@@ -149,9 +159,36 @@ def percsim_lib():
     return _percsim
 
 
+def consistency_lib():
+    global _consistency
+    if _consistency is None:
+        lib()                          # (the runtime binding: see lib())
+        if not os.path.exists(CONSISTENCY_LIB_PATH):
+            raise RuntimeError(f"{CONSISTENCY_LIB_PATH} is missing: build it with `python -m pixelsynth_amd.build` "
+                               "(there is no CPU/PyTorch fallback for the HIP path)")
+        L = ctypes.CDLL(CONSISTENCY_LIB_PATH)
+        for name, (res, args) in CONSISTENCY_PROTOS.items():
+            fn = getattr(L, name)
+            fn.restype = c_int if res is RC else res
+            fn.argtypes = [c_void_p if a is STREAM else a for a in args]
+        _consistency = L
+    return _consistency
+
+
+def _library_of(what):
+    """-> (the loaded library, the name of its last-error function) of the entry point `what`; libpixelsynth_hip.so for any other
+    label (callers of check() name their calls freely)"""
+    if what in PERCSIM_PROTOS:
+        return percsim_lib(), "ps_percsim_last_error"
+    if what in CONSISTENCY_PROTOS:
+        return consistency_lib(), "ps_consistency_last_error"
+    return lib(), "ps_last_error"
+
+
 def check(rc, what):
     if rc != 0:
-        msg = (percsim_lib().ps_percsim_last_error() if what in PERCSIM_PROTOS else lib().ps_last_error())
+        L, last = _library_of(what)
+        msg = getattr(L, last)()
         raise RuntimeError(f"{what} failed (rc={rc}): {msg.decode() if msg else '?'}")
 
 
@@ -160,16 +197,18 @@ _POINTERS = (c_void_p, ctypes.c_char_p, ctypes.c_wchar_p)
 
 
 def call(name, *args, stream=None):
-    """The entry point `name` of _PROTOS (or PERCSIM_PROTOS) on args: a torch tensor or numpy array goes as its data pointer, None as NULL, a ctypes
-    scalar or array (an out-parameter, a small host table) by reference; anything else (ints, floats, bytes, the engine's handle) as
-    ctypes converts it.  An entry point that ends in a STREAM gets the current stream appended (or `stream`), and each of its tensor
-    arguments must be a CUDA tensor on the current device: else RuntimeError, before anything is queued.  A nonzero RC raises
+    """The entry point `name` of _PROTOS (or PERCSIM_PROTOS, CONSISTENCY_PROTOS) on args: a torch tensor or numpy array goes as its data
+    pointer, None as NULL, a ctypes scalar or array (an out-parameter, a small host table) by reference; anything else (ints, floats,
+    bytes, the engine's handle) as ctypes converts it.  An entry point that ends in a STREAM gets the current stream appended (or
+    `stream`), and each of its tensor arguments must be a CUDA tensor on the current device: else RuntimeError, before anything is
+    queued.  A nonzero RC raises
     RuntimeError (check); any other return value is handed back."""
-    res, types = _PROTOS[name] if name in _PROTOS else PERCSIM_PROTOS[name]
+    table = _PROTOS if name in _PROTOS else PERCSIM_PROTOS if name in PERCSIM_PROTOS else CONSISTENCY_PROTOS
+    res, types = table[name]
     queued = bool(types) and types[-1] is STREAM
     if len(args) != len(types) - queued:
         raise TypeError(f"{name} takes {len(types) - queued} arguments{' besides the stream' if queued else ''}, got {len(args)}")
-    fn = getattr(lib() if name in _PROTOS else percsim_lib(), name)
+    fn = getattr(_library_of(name)[0], name)
     conv, device = list(args), None
     for i, a in enumerate(args):
         if isinstance(a, torch.Tensor):

@@ -3,7 +3,8 @@
     python -m pixelsynth_amd.build [--force]
 
 One object per translation unit, linked into pixelsynth_amd/libpixelsynth_hip.so; the PercSim passes (csrc/percsim.hip, declared in
-include/pixelsynth_percsim.h) into a library of their own next to it, libpixelsynth_percsim.so.  Both HIP units are built
+include/pixelsynth_percsim.h) into a library of their own next to it, libpixelsynth_percsim.so, and the homography consistency score
+(csrc/consistency.hip, include/pixelsynth_consistency.h) into libpixelsynth_consistency.so.  The HIP units are built
 with -ffp-contract=off: splat.hip because its index paths must be bit-exact against the oracle, the lmconv*.hip units so
 that the post ops inlined into different kernels (whole-grid vs column step) round identically; the matrix
 products are explicit MFMA intrinsics and are not affected.
@@ -17,6 +18,8 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.environ.get("PS_HIP_LIB") or os.path.join(HERE, "libpixelsynth_hip.so")   # (PS_HIP_LIB: tuning builds, with PS_OBJ_SUFFIX)
 PERCSIM_LIB = os.path.join(HERE, "libpixelsynth_percsim.so")
 PERCSIM_UNITS = [("percsim.hip", ["-ffp-contract=off"])]
+CONSISTENCY_LIB = os.path.join(HERE, "libpixelsynth_consistency.so")
+CONSISTENCY_UNITS = [("consistency.hip", ["-ffp-contract=off"])]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
 
@@ -46,14 +49,16 @@ def _deps():
     return [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")] + [
         os.path.join(os.path.dirname(HERE), "include", "pixelsynth_hip.h"),
         os.path.join(os.path.dirname(HERE), "include", "pixelsynth_hip_debug.h"),
-        os.path.join(os.path.dirname(HERE), "include", "pixelsynth_percsim.h")]
+        os.path.join(os.path.dirname(HERE), "include", "pixelsynth_percsim.h"),
+        os.path.join(os.path.dirname(HERE), "include", "pixelsynth_consistency.h")]
 
 
 def build(force=False, verbose=True):
-    """-> the path of libpixelsynth_hip.so; libpixelsynth_percsim.so is built beside it."""
+    """-> the path of libpixelsynth_hip.so; libpixelsynth_percsim.so and libpixelsynth_consistency.so are built beside it."""
     _build(UNITS, LIB, force, verbose)
     if not os.environ.get("PS_HIP_LIB"):
         _build(PERCSIM_UNITS, PERCSIM_LIB, force, verbose)
+        _build(CONSISTENCY_UNITS, CONSISTENCY_LIB, force, verbose)
     return LIB
 
 

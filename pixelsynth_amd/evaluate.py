@@ -14,6 +14,15 @@ PNGs are decoded on a host thread pool (at most 16 threads), uploaded as pinned 
 x / 255, TF.to_tensor's values); the next batch decodes while the device scores this one, one synchronisation per batch.  Under
 torch.distributed.run the images are dealt with distributed.shard_views and the rows come back to every rank through one all-gather
 (distributed.gather_rows); rank 0 prints and writes.  PS_DRYRUN_ONE_GPU=1 runs every rank on cuda:0 over gloo.
+
+    python -m pixelsynth_amd.evaluate --consistency DIR --masks DIR --points DIR --directions FILE.npy [--vgg16 PATH] [--max-img N]
+                                      [--batch B] [--json PATH]
+
+scores the homography consistency of view pairs as calc_errors_consistency_homography.py does (consistency.py, csrc/consistency.hip):
+item i (i < len(directions), or < N) has DIR/%04d/output_image_<d>_0001.png and _0002.png, d = consistency.MAPPING[directions[i]],
+--masks DIR/%04d/mask1.png and mask2.png, --points DIR/reproj1_<i>.npy and reproj2_<i>.npy, frames of 256 x 256.  Prints PSNR_vis
+-- with --vgg16 PercSim_vis first -- the mean over items of 0.5 (dir0 + dir1), PSNR clamped at 100 per direction.  The same decode
+pool, pinned uploads and sharding as above.
 """
 import argparse
 import json
@@ -25,6 +34,7 @@ import torch
 
 from . import distributed as D
 from .image_metrics import COLUMNS, image_metrics
+from . import consistency as CS
 from .perceptual import COLUMNS as PERCSIM_COLUMNS, perceptual_rows
 
 PSNR_CLAMP = 100.0
@@ -134,31 +144,40 @@ def summarize(rows, masked, percsim=False):
 
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
-    ap.add_argument("--pred", required=True, help="directory of predicted <i>.png")
-    ap.add_argument("--gt", required=True, help="directory of ground-truth <i>.png")
+    ap.add_argument("--pred", help="directory of predicted <i>.png")
+    ap.add_argument("--gt", help="directory of ground-truth <i>.png")
     ap.add_argument("--sampled", help="directory of the sampled images: adds the vis / invis split")
     ap.add_argument("--max-img", type=int, help="score i < N (default: as long as --pred has <i>.png)")
     ap.add_argument("--batch", type=int, default=64, help="images per upload and launch")
     ap.add_argument("--json", help="write per-image rows and the means here")
     ap.add_argument("--vgg16", help="VGG16 weights (vgg16-397923af.pth or a PNet state dict): adds PercSim")
+    ap.add_argument("--consistency", help="homography consistency mode: directory of the view pairs <%%04d>/output_image_<d>_000{1,2}.png")
+    ap.add_argument("--masks", help="with --consistency: directory of <%%04d>/mask1.png, mask2.png")
+    ap.add_argument("--points", help="with --consistency: directory of reproj1_<i>.npy, reproj2_<i>.npy")
+    ap.add_argument("--directions", help="with --consistency: .npy of each item's direction index into consistency.MAPPING")
     args = ap.parse_args(argv)
+    if args.consistency is None:
+        missing = [o for o, v in (("--pred", args.pred), ("--gt", args.gt)) if v is None]
+        if missing:
+            ap.error("the following arguments are required: " + ", ".join(missing))
+        stray = [o for o, v in (("--masks", args.masks), ("--points", args.points), ("--directions", args.directions)) if v is not None]
+        if stray:
+            ap.error(f"{', '.join(stray)} go with --consistency")
+    else:
+        missing = [o for o, v in (("--masks", args.masks), ("--points", args.points), ("--directions", args.directions)) if v is None]
+        if missing:
+            ap.error("--consistency requires " + ", ".join(missing))
+        stray = [o for o, v in (("--pred", args.pred), ("--gt", args.gt), ("--sampled", args.sampled)) if v is not None]
+        if stray:
+            ap.error(f"{', '.join(stray)} do not go with --consistency")
     if args.batch < 1:
         ap.error("--batch must be >= 1")
     if args.vgg16 is not None and not os.path.isfile(args.vgg16):
         ap.error(f"--vgg16 {args.vgg16}: no such file")
+    if args.consistency is not None:
+        return _consistency_main(args)
 
-    rank, world = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1))
-    local = 0 if os.environ.get("PS_DRYRUN_ONE_GPU") == "1" else int(os.environ.get("LOCAL_RANK", 0))
-    if not torch.cuda.is_available():
-        raise SystemExit("pixelsynth_amd.evaluate needs the ROCm device (there is no CPU fallback)")
-    torch.cuda.set_device(local)
-    device = torch.device("cuda", local)
-    if world > 1:
-        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-        if os.environ.get("PS_DRYRUN_ONE_GPU") == "1":
-            torch.distributed.init_process_group("gloo")
-        else:
-            torch.distributed.init_process_group("nccl", device_id=device)
+    rank, world, device = _setup()
     try:
         items = discover(args.pred, args.gt, args.sampled, args.max_img)
         n = len(items)
@@ -180,6 +199,144 @@ def main(argv=None):
                     cols = cols + (PERCSIM_COLUMNS if masked else ("percsim",))
                 doc = {"n": n, "pred": args.pred, "gt": args.gt, "sampled": args.sampled, "psnr_clamp": PSNR_CLAMP, "means": means,
                        "rows": [dict(index=i, **{c: float(rows[i, ALL_COLUMNS.index(c)]) for c in cols}) for i in range(n)]}
+                with open(args.json, "w") as fh:
+                    json.dump(doc, fh, indent=1)
+    finally:
+        if world > 1:
+            torch.distributed.destroy_process_group()
+    return 0
+
+
+def _setup():
+    """-> (rank, world size, device): the device of this rank, and the process group when there is more than one rank"""
+    rank, world = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1))
+    local = 0 if os.environ.get("PS_DRYRUN_ONE_GPU") == "1" else int(os.environ.get("LOCAL_RANK", 0))
+    if not torch.cuda.is_available():
+        raise SystemExit("pixelsynth_amd.evaluate needs the ROCm device (there is no CPU fallback)")
+    torch.cuda.set_device(local)
+    device = torch.device("cuda", local)
+    if world > 1:
+        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+        if os.environ.get("PS_DRYRUN_ONE_GPU") == "1":
+            torch.distributed.init_process_group("gloo")
+        else:
+            torch.distributed.init_process_group("nccl", device_id=device)
+    return rank, world, device
+
+
+# ---- the homography consistency mode (calc_errors_consistency_homography.py)
+CONSISTENCY_SIZE = 256                       # the reference's 255 literals and (256, 256, 1) reshapes
+
+
+def consistency_discover(views, masks, points, directions, max_img=None):
+    """-> list of (index, view1, view2, mask1, mask2, reproj1, reproj2) paths for i < len(directions) (or < max_img).  Raises
+    FileNotFoundError naming the first missing file, ValueError for a direction outside consistency.MAPPING."""
+    dirs = np.load(directions)
+    if dirs.ndim != 1:
+        raise ValueError(f"{directions}: a 1-D array of direction indices expected, got shape {dirs.shape}")
+    n = len(dirs) if max_img is None else int(max_img)
+    if n < 0:
+        raise ValueError(f"--max-img must be >= 0, got {n}")
+    if n > len(dirs):
+        raise ValueError(f"--max-img {n}: {directions} holds {len(dirs)} directions")
+    out = []
+    for i in range(n):
+        d = int(dirs[i])
+        if not 0 <= d < len(CS.MAPPING):
+            raise ValueError(f"{directions}: item {i}: direction {d} outside 0 .. {len(CS.MAPPING) - 1}")
+        item = (i, os.path.join(views, "%04d" % i, "output_image_%s_0001.png" % CS.MAPPING[d]),
+                os.path.join(views, "%04d" % i, "output_image_%s_0002.png" % CS.MAPPING[d]),
+                os.path.join(masks, "%04d" % i, "mask1.png"), os.path.join(masks, "%04d" % i, "mask2.png"),
+                os.path.join(points, "reproj1_%d.npy" % i), os.path.join(points, "reproj2_%d.npy" % i))
+        for p in item[1:]:
+            if not os.path.exists(p):
+                raise FileNotFoundError(f"item {i}: {p} is missing")
+        out.append(item)
+    return out
+
+
+def _read_gray(path):
+    """ImageOps.grayscale(Image.open(path)) as (H, W) uint8: PIL's integer L conversion"""
+    from PIL import Image, ImageOps
+    with Image.open(path) as im:
+        return np.asarray(ImageOps.grayscale(im), dtype=np.uint8)
+
+
+def _decode_item(item):
+    """-> (view1, view2 (H, W, 3) u8, mask1, mask2 (H, W) u8, reproj1, reproj2)"""
+    i, v1, v2, m1, m2, p1, p2 = item
+    arrs = (_read_rgb(v1), _read_rgb(v2), _read_gray(m1), _read_gray(m2))
+    S = CONSISTENCY_SIZE
+    for path, a in zip((v1, v2, m1, m2), arrs):
+        if a.shape[:2] != (S, S):
+            raise ValueError(f"item {i}: {path} is {a.shape[1]} x {a.shape[0]}; the consistency score takes {S} x {S} frames")
+    pts = []
+    for path in (p1, p2):
+        p = np.load(path)
+        if p.ndim != 2 or p.shape[1] < 2 or p.dtype.kind not in "iuf":
+            raise ValueError(f"item {i}: {path} holds a {p.dtype} array of shape {p.shape}; (n, >= 2) real numbers expected")
+        pts.append(p)
+    return arrs + tuple(pts)
+
+
+def consistency_files(items, device, batch=64, pool=None, pnet=None):
+    """-> (len(items), 3) float64 rows (consistency.COLUMNS[:3]), or (len(items), 6) with a PNet, in order"""
+    own = pool is None
+    pool = pool or ThreadPoolExecutor(max_workers=_threads())
+    k = 3 if pnet is None else 6
+    try:
+        chunks = [items[i:i + batch] for i in range(0, len(items), batch)]
+        submit = lambda ch: [pool.submit(_decode_item, it) for it in ch]
+        rows = []
+        pending = submit(chunks[0]) if chunks else None
+        for c in range(len(chunks)):
+            dec = [f.result() for f in pending]
+            pending = submit(chunks[c + 1]) if c + 1 < len(chunks) else None     # decodes while the device scores this batch
+            labels = [it[0] for it in chunks[c]]
+            H12, H21 = CS.fit_points([d[4] for d in dec], [d[5] for d in dec], labels)
+            host = [torch.from_numpy(np.stack([d[j] for d in dec])).pin_memory() for j in range(4)]
+            v1, v2, m1, m2 = (t.to(device, non_blocking=True) for t in host)
+            out = CS.consistency_rows(v1.permute(0, 3, 1, 2), v2.permute(0, 3, 1, 2), m1[:, None], m2[:, None], H12, H21, pnet=pnet)
+            rows.append(out.cpu().double().numpy())                               # the batch's one synchronisation
+        return np.concatenate(rows) if rows else np.zeros((0, k))
+    finally:
+        if own:
+            pool.shutdown()
+
+
+def consistency_summarize(rows, percsim=False):
+    """-> {printed name: mean over items} in the reference's METRICS order (PercSim_vis, PSNR_vis): per item
+    (dir0 + dir1) * 0.5 of the fp32 per-direction values in fp64, then np.mean (:103-109)"""
+    out = {}
+    for name, c0 in ((("PercSim_vis", 3),) if percsim else ()) + (("PSNR_vis", 0),):
+        d0, d1 = rows[:, c0].astype(np.float32), rows[:, c0 + 1].astype(np.float32)
+        per = [(float(a) + float(b)) * .5 for a, b in zip(d0, d1)]
+        out[name] = float(np.mean(per)) if per else float("nan")
+    return out
+
+
+def _consistency_main(args):
+    rank, world, device = _setup()
+    try:
+        items = consistency_discover(args.consistency, args.masks, args.points, args.directions, args.max_img)
+        n = len(items)
+        mine = D.shard_views(n, rank, world)
+        pnet = None
+        if args.vgg16 is not None:
+            from .networks.pretrained_networks import PNet
+            pnet = PNet(use_gpu=True, weights=args.vgg16)
+        local_rows = consistency_files([items[i] for i in mine], device, args.batch, pnet=pnet)
+        k = 3 if pnet is None else 6
+        rows = D.gather_rows(local_rows.reshape(-1, k).T, n).T                     # (n, k), item order
+        means = consistency_summarize(rows, pnet is not None)
+        if rank == 0:
+            for name, v in means.items():
+                print("%s \t %0.5f" % (name, v))
+            if args.json:
+                cols = CS.COLUMNS[:k]
+                doc = {"n": n, "consistency": args.consistency, "masks": args.masks, "points": args.points,
+                       "directions": args.directions, "psnr_clamp": PSNR_CLAMP, "means": means,
+                       "rows": [dict(index=i, **{c: float(rows[i, j]) for j, c in enumerate(cols)}) for i in range(n)]}
                 with open(args.json, "w") as fh:
                     json.dump(doc, fh, indent=1)
     finally:

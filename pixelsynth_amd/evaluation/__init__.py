@@ -1,11 +1,13 @@
 """Quality of rendered views (the reference's evaluation/, calc_errors_quality.py): PSNR and SSIM on the HIP kernel, and PercSim (the
 VGG16 perceptual similarity: perceptual.py, networks/pretrained_networks.PNet) when the caller passes a PNet, overall and split into the
-pixels the splat covered ("vis") and the outpainted ones ("invis").  FID (Inception weights, pytorch_fid), LPIPS and the homography
-consistency score (OpenCV and the reference's point files) are not provided."""
+pixels the splat covered ("vis") and the outpainted ones ("invis").  The homography consistency score of view pairs
+(calc_errors_consistency_homography.py: PSNR_vis and PercSim_vis of each view warped into the other's frame) is consistency_rows
+(consistency.py).  FID (Inception weights, pytorch_fid) and LPIPS are not provided."""
+from ..consistency import COLUMNS as CONSISTENCY_COLUMNS, consistency_rows
 from ..image_metrics import COLUMNS, image_metrics
 from ..perceptual import COLUMNS as PERCSIM_COLUMNS, perceptual_rows
 
-__all__ = ["score_views", "COLUMNS", "PERCSIM_COLUMNS"]
+__all__ = ["score_views", "consistency_rows", "COLUMNS", "PERCSIM_COLUMNS", "CONSISTENCY_COLUMNS"]
 
 
 def score_views(pred, gt, background_mask=None, pnet=None):
