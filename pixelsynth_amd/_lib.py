@@ -117,6 +117,19 @@ CONSISTENCY_PROTOS = {
 }
 _consistency = None
 
+# libpixelsynth_fid.so (include/pixelsynth_fid.h): the passes of the FID network, a library of its own as well
+FID_LIB_PATH = os.path.join(_HERE, "libpixelsynth_fid.so")
+FID_PROTOS = {
+    "ps_fid_last_error": (ctypes.c_char_p, []),
+    "ps_fid_input": (RC, [c_void_p, c_void_p] + [c_int] * 4 + [c_void_p, STREAM]),
+    "ps_fid_conv_takes": (c_int, [c_int] * 7),
+    "ps_fid_conv_co_tile": (c_int, [c_int]),
+    "ps_fid_conv_packed_floats": (c_size_t, [c_int] * 4),
+    "ps_fid_conv": (RC, [c_void_p, c_int, c_void_p, c_size_t, c_void_p] + [c_int] * 10 + [c_void_p, c_int, c_int, STREAM]),
+    "ps_fid_pool": (RC, [c_void_p] + [c_int] * 6 + [c_void_p, c_int, c_int, STREAM]),
+}
+_fid = None
+
 
 def exported_symbols():
     """Names every entry point include/pixelsynth_hip.h and include/pixelsynth_hip_debug.h declare (used by the CPU load test)."""
@@ -175,6 +188,22 @@ def consistency_lib():
     return _consistency
 
 
+def fid_lib():
+    global _fid
+    if _fid is None:
+        lib()                          # (the runtime binding: see lib())
+        if not os.path.exists(FID_LIB_PATH):
+            raise RuntimeError(f"{FID_LIB_PATH} is missing: build it with `python -m pixelsynth_amd.build` "
+                               "(there is no CPU/PyTorch fallback for the HIP path)")
+        L = ctypes.CDLL(FID_LIB_PATH)
+        for name, (res, args) in FID_PROTOS.items():
+            fn = getattr(L, name)
+            fn.restype = c_int if res is RC else res
+            fn.argtypes = [c_void_p if a is STREAM else a for a in args]
+        _fid = L
+    return _fid
+
+
 def _library_of(what):
     """-> (the loaded library, the name of its last-error function) of the entry point `what`; libpixelsynth_hip.so for any other
     label (callers of check() name their calls freely)"""
@@ -182,6 +211,8 @@ def _library_of(what):
         return percsim_lib(), "ps_percsim_last_error"
     if what in CONSISTENCY_PROTOS:
         return consistency_lib(), "ps_consistency_last_error"
+    if what in FID_PROTOS:
+        return fid_lib(), "ps_fid_last_error"
     return lib(), "ps_last_error"
 
 
@@ -197,13 +228,13 @@ _POINTERS = (c_void_p, ctypes.c_char_p, ctypes.c_wchar_p)
 
 
 def call(name, *args, stream=None):
-    """The entry point `name` of _PROTOS (or PERCSIM_PROTOS, CONSISTENCY_PROTOS) on args: a torch tensor or numpy array goes as its data
+    """The entry point `name` of _PROTOS (or PERCSIM_PROTOS, CONSISTENCY_PROTOS, FID_PROTOS) on args: a torch tensor or numpy array goes as its data
     pointer, None as NULL, a ctypes scalar or array (an out-parameter, a small host table) by reference; anything else (ints, floats,
     bytes, the engine's handle) as ctypes converts it.  An entry point that ends in a STREAM gets the current stream appended (or
     `stream`), and each of its tensor arguments must be a CUDA tensor on the current device: else RuntimeError, before anything is
     queued.  A nonzero RC raises
     RuntimeError (check); any other return value is handed back."""
-    table = _PROTOS if name in _PROTOS else PERCSIM_PROTOS if name in PERCSIM_PROTOS else CONSISTENCY_PROTOS
+    table = next((t for t in (_PROTOS, PERCSIM_PROTOS, CONSISTENCY_PROTOS) if name in t), FID_PROTOS)
     res, types = table[name]
     queued = bool(types) and types[-1] is STREAM
     if len(args) != len(types) - queued:

@@ -4,7 +4,8 @@
 
 One object per translation unit, linked into pixelsynth_amd/libpixelsynth_hip.so; the PercSim passes (csrc/percsim.hip, declared in
 include/pixelsynth_percsim.h) into a library of their own next to it, libpixelsynth_percsim.so, and the homography consistency score
-(csrc/consistency.hip, include/pixelsynth_consistency.h) into libpixelsynth_consistency.so.  The HIP units are built
+(csrc/consistency.hip, include/pixelsynth_consistency.h) into libpixelsynth_consistency.so, and the passes of the FID network
+(csrc/fid.hip, include/pixelsynth_fid.h) into libpixelsynth_fid.so.  The HIP units are built
 with -ffp-contract=off: splat.hip because its index paths must be bit-exact against the oracle, the lmconv*.hip units so
 that the post ops inlined into different kernels (whole-grid vs column step) round identically; the matrix
 products are explicit MFMA intrinsics and are not affected.
@@ -20,6 +21,8 @@ PERCSIM_LIB = os.path.join(HERE, "libpixelsynth_percsim.so")
 PERCSIM_UNITS = [("percsim.hip", ["-ffp-contract=off"])]
 CONSISTENCY_LIB = os.path.join(HERE, "libpixelsynth_consistency.so")
 CONSISTENCY_UNITS = [("consistency.hip", ["-ffp-contract=off"])]
+FID_LIB = os.path.join(HERE, "libpixelsynth_fid.so")
+FID_UNITS = [("fid.hip", ["-ffp-contract=off"])]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
 
@@ -50,15 +53,18 @@ def _deps():
         os.path.join(os.path.dirname(HERE), "include", "pixelsynth_hip.h"),
         os.path.join(os.path.dirname(HERE), "include", "pixelsynth_hip_debug.h"),
         os.path.join(os.path.dirname(HERE), "include", "pixelsynth_percsim.h"),
-        os.path.join(os.path.dirname(HERE), "include", "pixelsynth_consistency.h")]
+        os.path.join(os.path.dirname(HERE), "include", "pixelsynth_consistency.h"),
+        os.path.join(os.path.dirname(HERE), "include", "pixelsynth_fid.h")]
 
 
 def build(force=False, verbose=True):
-    """-> the path of libpixelsynth_hip.so; libpixelsynth_percsim.so and libpixelsynth_consistency.so are built beside it."""
+    """-> the path of libpixelsynth_hip.so; libpixelsynth_percsim.so, libpixelsynth_consistency.so and libpixelsynth_fid.so are built
+    beside it."""
     _build(UNITS, LIB, force, verbose)
     if not os.environ.get("PS_HIP_LIB"):
         _build(PERCSIM_UNITS, PERCSIM_LIB, force, verbose)
         _build(CONSISTENCY_UNITS, CONSISTENCY_LIB, force, verbose)
+        _build(FID_UNITS, FID_LIB, force, verbose)
     return LIB
 
 

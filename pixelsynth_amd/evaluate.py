@@ -1,7 +1,9 @@
 """Score predicted views against ground truth: PSNR and SSIM on the HIP kernel (csrc/metrics.hip) and, with --vgg16, PercSim (the
-VGG16 perceptual similarity, perceptual.py); the reference's calc_errors_quality.py without FID (it needs Inception weights).
+VGG16 perceptual similarity, perceptual.py) and, with --inception, FID (the Fréchet distance of Inception-v3 features, fid.py,
+csrc/fid.hip); the reference's calc_errors_quality.py.
 
     python -m pixelsynth_amd.evaluate --pred DIR --gt DIR [--sampled DIR] [--max-img N] [--batch 64] [--json PATH] [--vgg16 PATH]
+                                      [--inception PATH]
 
 Image i is <dir>/<i>.png in each directory.  Without --max-img, i runs from 0 as long as --pred has <i>.png; with it, every i < N must be
 there.  Images are read as RGB.  With --sampled, a pixel is "vis" where all channels of the ground truth equal the sampled image
@@ -9,6 +11,10 @@ there.  Images are read as RGB.  With --sampled, a pixel is "vis" where all chan
 images (PSNR clamped at 100 first, as the reference does).  --json writes the per-image rows and the means.  --vgg16 names VGG16
 weights (torchvision's vgg16-397923af.pth, or a PNet state dict; nothing is downloaded) and adds PercSim -- with --sampled also
 PercSim_invis and PercSim_vis, the images times the mask -- after the SSIM lines, means of the per-image values (no clamp).
+--inception names Inception-v3 weights (pytorch_fid's pt_inception-2015-12-05-*.pth, or any state dict with torchvision's Inception3
+keys; nothing is downloaded) and adds the line FID after the means: the Fréchet distance between the 2048-feature statistics of the
+--pred images and of the --gt images (what `python -m pytorch_fid PRED GT` scores), the images the other metrics read, decoded once.
+Under torch.distributed.run the feature rows travel with the metric rows and rank 0 does the statistics.
 
 PNGs are decoded on a host thread pool (at most 16 threads), uploaded as pinned uint8 batches and scored on uint8 (the kernel converts
 x / 255, TF.to_tensor's values); the next batch decodes while the device scores this one, one synchronisation per batch.  Under
@@ -36,6 +42,7 @@ from . import distributed as D
 from .image_metrics import COLUMNS, image_metrics
 from . import consistency as CS
 from .perceptual import COLUMNS as PERCSIM_COLUMNS, perceptual_rows
+from . import fid as FID
 
 PSNR_CLAMP = 100.0
 # printed name -> column; the reference's names (calc_errors_quality.py:47-67) and their SSIM counterparts
@@ -102,15 +109,16 @@ def _stage(decoded):
     return pred, gt, mask
 
 
-def score_files(items, device, batch=64, pool=None, pnet=None):
+def score_files(items, device, batch=64, pool=None, pnet=None, inception=None):
     """-> (len(items), 6) float64 numpy rows (COLUMNS) of the (pred, gt, sampled) triples, in order; with a PNet `pnet`
-    (len(items), 9) rows (ALL_COLUMNS)."""
+    (len(items), 9) rows (ALL_COLUMNS).  With a FIDInception `inception`: -> (those rows, (len(items), 2 * 2048) float64 feature rows,
+    the --pred image's features then the --gt image's)."""
     own = pool is None
     pool = pool or ThreadPoolExecutor(max_workers=_threads())
     try:
         chunks = [items[i:i + batch] for i in range(0, len(items), batch)]
         submit = lambda ch: [pool.submit(_decode, it) for it in ch]
-        rows = []
+        rows, feats = [], []
         pending = submit(chunks[0]) if chunks else None
         for k in range(len(chunks)):
             host = _stage([f.result() for f in pending])
@@ -120,8 +128,17 @@ def score_files(items, device, batch=64, pool=None, pnet=None):
             out = image_metrics(gt.permute(0, 3, 1, 2), pred.permute(0, 3, 1, 2), mask)
             if pnet is not None:
                 out = torch.cat([out, perceptual_rows(pnet, gt.permute(0, 3, 1, 2), pred.permute(0, 3, 1, 2), mask)], 1)
-            rows.append(out.cpu().double().numpy())                               # the batch's one synchronisation
-        return np.concatenate(rows) if rows else np.zeros((0, 6 if pnet is None else len(ALL_COLUMNS)))
+            if inception is not None:
+                both = FID.inception_features(inception, torch.cat([pred, gt]).permute(0, 3, 1, 2))
+                out = torch.cat([out, both[:len(pred)], both[len(pred):]], 1)
+            out = out.cpu().double().numpy()                                      # the batch's one synchronisation
+            rows.append(out[:, :out.shape[1] - (0 if inception is None else 2 * FID.I.DIMS)])
+            feats.append(out[:, rows[-1].shape[1]:])
+        k = 6 if pnet is None else len(ALL_COLUMNS)
+        rows = np.concatenate(rows) if rows else np.zeros((0, k))
+        if inception is None:
+            return rows
+        return rows, (np.concatenate(feats) if feats else np.zeros((0, 2 * FID.I.DIMS)))
     finally:
         if own:
             pool.shutdown()
@@ -151,6 +168,8 @@ def main(argv=None):
     ap.add_argument("--batch", type=int, default=64, help="images per upload and launch")
     ap.add_argument("--json", help="write per-image rows and the means here")
     ap.add_argument("--vgg16", help="VGG16 weights (vgg16-397923af.pth or a PNet state dict): adds PercSim")
+    ap.add_argument("--inception", help="Inception-v3 weights (pt_inception-2015-12-05-*.pth or a state dict with torchvision's keys): "
+                                        "adds FID of --pred against --gt")
     ap.add_argument("--consistency", help="homography consistency mode: directory of the view pairs <%%04d>/output_image_<d>_000{1,2}.png")
     ap.add_argument("--masks", help="with --consistency: directory of <%%04d>/mask1.png, mask2.png")
     ap.add_argument("--points", help="with --consistency: directory of reproj1_<i>.npy, reproj2_<i>.npy")
@@ -167,13 +186,16 @@ def main(argv=None):
         missing = [o for o, v in (("--masks", args.masks), ("--points", args.points), ("--directions", args.directions)) if v is None]
         if missing:
             ap.error("--consistency requires " + ", ".join(missing))
-        stray = [o for o, v in (("--pred", args.pred), ("--gt", args.gt), ("--sampled", args.sampled)) if v is not None]
+        stray = [o for o, v in (("--pred", args.pred), ("--gt", args.gt), ("--sampled", args.sampled), ("--inception", args.inception))
+                 if v is not None]
         if stray:
             ap.error(f"{', '.join(stray)} do not go with --consistency")
     if args.batch < 1:
         ap.error("--batch must be >= 1")
     if args.vgg16 is not None and not os.path.isfile(args.vgg16):
         ap.error(f"--vgg16 {args.vgg16}: no such file")
+    if args.inception is not None and not os.path.isfile(args.inception):
+        ap.error(f"--inception {args.inception}: no such file")
     if args.consistency is not None:
         return _consistency_main(args)
 
@@ -181,15 +203,26 @@ def main(argv=None):
     try:
         items = discover(args.pred, args.gt, args.sampled, args.max_img)
         n = len(items)
+        if args.inception is not None and n < 2:
+            raise SystemExit(f"--inception: FID needs two images at least, found {n}")
         mine = D.shard_views(n, rank, world)
         pnet = None
         if args.vgg16 is not None:
             from .networks.pretrained_networks import PNet
             pnet = PNet(use_gpu=True, weights=args.vgg16)
-        local_rows = score_files([items[i] for i in mine], device, args.batch, pnet=pnet)
+        net = None
+        if args.inception is not None:
+            from .networks.inception import FIDInception
+            net = FIDInception(weights=args.inception, use_gpu=True)
+        local_rows = score_files([items[i] for i in mine], device, args.batch, pnet=pnet, inception=net)
+        if net is not None:      # the feature rows travel with the metric rows: float64 blocks, fp32 features pass unchanged
+            local_rows = np.concatenate(local_rows, 1)
         rows = D.gather_rows(local_rows.T, n).T                                    # (n, 6) -- 9 with --vgg16 --, image order
         masked = args.sampled is not None
         means = summarize(rows, masked, pnet is not None)
+        if net is not None and rank == 0:
+            feats = rows[:, -2 * FID.I.DIMS:]
+            means["FID"] = FID.fid_of_rows(feats[:, :FID.I.DIMS], feats[:, FID.I.DIMS:])
         if rank == 0:
             for name, v in means.items():
                 print("%s \t %0.5f" % (name, v))
@@ -198,6 +231,7 @@ def main(argv=None):
                 if pnet is not None:
                     cols = cols + (PERCSIM_COLUMNS if masked else ("percsim",))
                 doc = {"n": n, "pred": args.pred, "gt": args.gt, "sampled": args.sampled, "psnr_clamp": PSNR_CLAMP, "means": means,
+                       **({"fid": means["FID"]} if net is not None else {}),
                        "rows": [dict(index=i, **{c: float(rows[i, ALL_COLUMNS.index(c)]) for c in cols}) for i in range(n)]}
                 with open(args.json, "w") as fh:
                     json.dump(doc, fh, indent=1)

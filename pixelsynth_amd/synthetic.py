@@ -382,3 +382,20 @@ def vgg16_state_dict(seed=0):
         out[f"features.{i}.bias"] = (rs.randn(v) * 0.01).astype(np.float32)
         ci, i = v, i + 2
     return out
+
+
+def inception_state_dict(seed=0):
+    """Inception-v3 trunk weights with torchvision's keys (<name>.conv.weight, <name>.bn.{weight, bias, running_mean, running_var},
+    float32) for the FID network (networks/inception.py): He-normal weights, std sqrt(2 / (KH KW Ci)), gamma U(0.5, 1.5), beta and
+    running means N(0, 0.05^2), running variances U(0.5, 1.5) -- folding the BatchNorm is exercised, and the activations keep their scale
+    to the last block."""
+    from .networks.inception import conv_specs
+    rs = np.random.RandomState(seed)
+    out = {}
+    for name, (ci, co, (kh, kw), _, _) in conv_specs().items():
+        out[name + ".conv.weight"] = (rs.randn(co, ci, kh, kw) * math.sqrt(2.0 / (kh * kw * ci))).astype(np.float32)
+        out[name + ".bn.weight"] = (0.5 + rs.rand(co)).astype(np.float32)
+        out[name + ".bn.bias"] = (rs.randn(co) * 0.05).astype(np.float32)
+        out[name + ".bn.running_mean"] = (rs.randn(co) * 0.05).astype(np.float32)
+        out[name + ".bn.running_var"] = (0.5 + rs.rand(co)).astype(np.float32)
+    return out
