@@ -130,6 +130,17 @@ FID_PROTOS = {
 }
 _fid = None
 
+# libpixelsynth_scene.so (include/pixelsynth_scene.h): the batched chained-scene step over ragged clouds, a library of its own as well
+SCENE_LIB_PATH = os.path.join(_HERE, "libpixelsynth_scene.so")
+SCENE_PROTOS = {
+    "ps_scene_last_error": (ctypes.c_char_p, []),
+    "ps_scene_state_bytes": (c_size_t, [c_int] * 3),
+    "ps_scene_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_double]),
+    "ps_scene_step_f32": (RC, [c_void_p] * 13 + [c_int] * 6 + [c_double, c_int, c_float, c_int, c_int, c_int, c_void_p, c_void_p,
+                                                                c_void_p, c_size_t, STREAM]),
+}
+_scene = None
+
 
 def exported_symbols():
     """Names every entry point include/pixelsynth_hip.h and include/pixelsynth_hip_debug.h declare (used by the CPU load test)."""
@@ -204,6 +215,22 @@ def fid_lib():
     return _fid
 
 
+def scene_lib():
+    global _scene
+    if _scene is None:
+        lib()                          # (the runtime binding: see lib())
+        if not os.path.exists(SCENE_LIB_PATH):
+            raise RuntimeError(f"{SCENE_LIB_PATH} is missing: build it with `python -m pixelsynth_amd.build` "
+                               "(there is no CPU/PyTorch fallback for the HIP path)")
+        L = ctypes.CDLL(SCENE_LIB_PATH)
+        for name, (res, args) in SCENE_PROTOS.items():
+            fn = getattr(L, name)
+            fn.restype = c_int if res is RC else res
+            fn.argtypes = [c_void_p if a is STREAM else a for a in args]
+        _scene = L
+    return _scene
+
+
 def _library_of(what):
     """-> (the loaded library, the name of its last-error function) of the entry point `what`; libpixelsynth_hip.so for any other
     label (callers of check() name their calls freely)"""
@@ -213,6 +240,8 @@ def _library_of(what):
         return consistency_lib(), "ps_consistency_last_error"
     if what in FID_PROTOS:
         return fid_lib(), "ps_fid_last_error"
+    if what in SCENE_PROTOS:
+        return scene_lib(), "ps_scene_last_error"
     return lib(), "ps_last_error"
 
 
@@ -228,13 +257,13 @@ _POINTERS = (c_void_p, ctypes.c_char_p, ctypes.c_wchar_p)
 
 
 def call(name, *args, stream=None):
-    """The entry point `name` of _PROTOS (or PERCSIM_PROTOS, CONSISTENCY_PROTOS, FID_PROTOS) on args: a torch tensor or numpy array goes as its data
+    """The entry point `name` of _PROTOS (or PERCSIM_PROTOS, CONSISTENCY_PROTOS, FID_PROTOS, SCENE_PROTOS) on args: a torch tensor or numpy array goes as its data
     pointer, None as NULL, a ctypes scalar or array (an out-parameter, a small host table) by reference; anything else (ints, floats,
     bytes, the engine's handle) as ctypes converts it.  An entry point that ends in a STREAM gets the current stream appended (or
     `stream`), and each of its tensor arguments must be a CUDA tensor on the current device: else RuntimeError, before anything is
     queued.  A nonzero RC raises
     RuntimeError (check); any other return value is handed back."""
-    table = next((t for t in (_PROTOS, PERCSIM_PROTOS, CONSISTENCY_PROTOS) if name in t), FID_PROTOS)
+    table = next((t for t in (_PROTOS, PERCSIM_PROTOS, CONSISTENCY_PROTOS, SCENE_PROTOS) if name in t), FID_PROTOS)
     res, types = table[name]
     queued = bool(types) and types[-1] is STREAM
     if len(args) != len(types) - queued:

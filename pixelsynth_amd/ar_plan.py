@@ -51,6 +51,7 @@ class ARPlan:
         # the schedule of per-frame prefixes (cols on the device, wave_start on the host) and first_steps on the device: where
         # build_ar_plan made them, None otherwise
         self.waves_frames = self.first_steps_dev = None
+        self.background_counts = None    # build_ar_plan(count_background=True): set pixels of every mask (it has them on the host)
         self._waves = None
 
     @property
@@ -81,11 +82,12 @@ class ARPlan:
                 if t is not None]
 
 
-def build_ar_plan(background_mask, G=32, device=None):
+def build_ar_plan(background_mask, G=32, device=None, count_background=False):
     """background_mask (B,S,S) bool/uint8 tensor (device or host) -> ARPlan on `device`.
     One device->host copy of the mask (the reference does four, z_buffermodel.py:662-669), the integer work (pooling,
     distance transforms, generation order) in C++ on the host (csrc/host_order.cpp), the orders back up, and the three
-    kernel masks built from them on the device (ps_order_masks_f32) -- nothing bigger than the orders crosses PCIe."""
+    kernel masks built from them on the device (ps_order_masks_f32) -- nothing bigger than the orders crosses PCIe.
+    count_background: also keep every mask's number of set pixels (plan.background_counts), for PtsManipulator.forward_scene_step."""
     device = device or (background_mask.device if background_mask.is_cuda else torch.device("cuda", torch.cuda.current_device()))
     B, S, _ = background_mask.shape
     L = G * G
@@ -106,6 +108,8 @@ def build_ar_plan(background_mask, G=32, device=None):
         masks = [torch.empty(B, 9, L, dtype=torch.float32, device=device) for _ in range(3)]
         _lib.call("ps_order_masks_f32", d_order, B, G, G, *masks, _lib.status_word(device))
         plan = ARPlan(d_order, d_region, *masks, order_loc.copy(), region, (G, G))   # (the staging buffers are reused by the next plan)
+        if count_background:   # set pixels per mask: what a batched chained scene's next frame adds to every cloud
+            plan.background_counts = np.count_nonzero(np.asarray(bg).reshape(B, -1), axis=1).tolist()
         if PER_FRAME_PREFIX and int(plan.first_steps.max()) > plan.first_step:
             fs_t = _pinned("first_steps", (B,), torch.int32)
             fs_t.numpy()[:] = plan.first_steps

@@ -5,7 +5,8 @@
 One object per translation unit, linked into pixelsynth_amd/libpixelsynth_hip.so; the PercSim passes (csrc/percsim.hip, declared in
 include/pixelsynth_percsim.h) into a library of their own next to it, libpixelsynth_percsim.so, and the homography consistency score
 (csrc/consistency.hip, include/pixelsynth_consistency.h) into libpixelsynth_consistency.so, and the passes of the FID network
-(csrc/fid.hip, include/pixelsynth_fid.h) into libpixelsynth_fid.so.  The HIP units are built
+(csrc/fid.hip, include/pixelsynth_fid.h) into libpixelsynth_fid.so, and the batched chained-scene step (csrc/scene.hip, which includes
+csrc/splat.hip for its kernels; include/pixelsynth_scene.h) into libpixelsynth_scene.so.  The HIP units are built
 with -ffp-contract=off: splat.hip because its index paths must be bit-exact against the oracle, the lmconv*.hip units so
 that the post ops inlined into different kernels (whole-grid vs column step) round identically; the matrix
 products are explicit MFMA intrinsics and are not affected.
@@ -23,6 +24,8 @@ CONSISTENCY_LIB = os.path.join(HERE, "libpixelsynth_consistency.so")
 CONSISTENCY_UNITS = [("consistency.hip", ["-ffp-contract=off"])]
 FID_LIB = os.path.join(HERE, "libpixelsynth_fid.so")
 FID_UNITS = [("fid.hip", ["-ffp-contract=off"])]
+SCENE_LIB = os.path.join(HERE, "libpixelsynth_scene.so")
+SCENE_UNITS = [("scene.hip", ["-ffp-contract=off"])]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
 
@@ -50,6 +53,8 @@ if EXTRA:   # ps_build_info() (csrc/host_order.cpp) names them: a number measure
 
 def _deps():
     return [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")] + [
+        os.path.join(CSRC, "splat.hip"),    # (scene.hip includes it)
+        os.path.join(os.path.dirname(HERE), "include", "pixelsynth_scene.h"),
         os.path.join(os.path.dirname(HERE), "include", "pixelsynth_hip.h"),
         os.path.join(os.path.dirname(HERE), "include", "pixelsynth_hip_debug.h"),
         os.path.join(os.path.dirname(HERE), "include", "pixelsynth_percsim.h"),
@@ -58,13 +63,14 @@ def _deps():
 
 
 def build(force=False, verbose=True):
-    """-> the path of libpixelsynth_hip.so; libpixelsynth_percsim.so, libpixelsynth_consistency.so and libpixelsynth_fid.so are built
-    beside it."""
+    """-> the path of libpixelsynth_hip.so; libpixelsynth_percsim.so, libpixelsynth_consistency.so, libpixelsynth_fid.so and
+    libpixelsynth_scene.so are built beside it."""
     _build(UNITS, LIB, force, verbose)
     if not os.environ.get("PS_HIP_LIB"):
         _build(PERCSIM_UNITS, PERCSIM_LIB, force, verbose)
         _build(CONSISTENCY_UNITS, CONSISTENCY_LIB, force, verbose)
         _build(FID_UNITS, FID_LIB, force, verbose)
+        _build(SCENE_UNITS, SCENE_LIB, force, verbose)
     return LIB
 
 

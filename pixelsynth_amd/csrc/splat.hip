@@ -180,22 +180,30 @@ __device__ __forceinline__ uint32_t point_bbox(const float *p, int S, float hw)
 constexpr int LDS_TILES = 4096;
 constexpr int MAX_TPP = 9;  // tiles per point kept in LDS ranks (larger footprints take the direct path)
 
+// RAGGED (the batched chained scenes, csrc/scene.hip): cloud b holds counts[b] <= N points in rows of N; the points at or past
+// counts[b] do not exist for binning -- no bbox, no key.  Everything behind the binning (k_scan, the sorts, k_composite, the dilation)
+// only ever sees point indices that were binned, and takes N as the row length alone.  Calls without counts instantiate RAGGED = false:
+// the kernels they ran before.
+template <bool RAGGED>
 __global__ __launch_bounds__(256) void k_bin_count(const float *__restrict__ pts, int N, int S,
                                                    float hw, int tilesX, int NT,
                                                    uint32_t *__restrict__ bbox,
-                                                   uint32_t *__restrict__ tile_count)
+                                                   uint32_t *__restrict__ tile_count,
+                                                   const int32_t *__restrict__ counts)
 {
     __shared__ uint32_t cnt[LDS_TILES];
     const int b = blockIdx.y;
     const int n = blockIdx.x * 256 + threadIdx.x;
+    const int Nrow = N;                          // row length of pts / bbox
+    if (RAGGED) N = min(N, max(counts[b], 0));   // points cloud b has
     const bool agg = NT <= LDS_TILES;
     if (agg) {
         for (int t = threadIdx.x; t < NT; t += 256) cnt[t] = 0;
         __syncthreads();
     }
     if (n < N) {
-        const uint32_t bb = point_bbox(pts + ((size_t)b * N + n) * 3, S, hw);
-        bbox[(size_t)b * N + n] = bb;
+        const uint32_t bb = point_bbox(pts + ((size_t)b * Nrow + n) * 3, S, hw);
+        bbox[(size_t)b * Nrow + n] = bb;
         if (bb != CULLED) {
             const int tx0 = bb & 255, ty0 = (bb >> 8) & 255, tx1 = (bb >> 16) & 255, ty1 = bb >> 24;
             for (int ty = ty0; ty <= ty1; ++ty)
@@ -242,18 +250,20 @@ __global__ __launch_bounds__(1024) void k_scan(uint32_t *__restrict__ counters, 
     if (t == 1023) c[NT] = base + part[1023];
 }
 
+template <bool RAGGED>
 __global__ __launch_bounds__(256) void k_bin_fill(const float *__restrict__ pts, int N, int tilesX,
                                                   int NT, const uint32_t *__restrict__ bbox,
                                                   const uint32_t *__restrict__ tile_off,
                                                   uint32_t *__restrict__ tile_cursor,
-                                                  uint64_t *__restrict__ keys)
+                                                  uint64_t *__restrict__ keys,
+                                                  const int32_t *__restrict__ counts)
 {
     __shared__ uint32_t cnt[LDS_TILES];       // per-tile count of this workgroup, then its base in the tile's list
     __shared__ uint16_t rank[256][MAX_TPP];   // rank of each (point, tile) inside the workgroup's share
     const int b = blockIdx.y;
     const int n = blockIdx.x * 256 + threadIdx.x;
     uint32_t bb = CULLED;
-    if (n < N) bb = bbox[(size_t)b * N + n];
+    if (n < (RAGGED ? min(N, max(counts[b], 0)) : N)) bb = bbox[(size_t)b * N + n];
     const int tx0 = bb & 255, ty0 = (bb >> 8) & 255, tx1 = (bb >> 16) & 255, ty1 = bb >> 24;
     const bool live = bb != CULLED;
     // same-footprint decision for the whole workgroup (uniform branch): LDS aggregation or the direct path
@@ -800,8 +810,11 @@ void launch_composite(bool debug, bool recip, dim3 grid, hipStream_t st, const u
 int splat_core(const float *pts, const float *feat, int B, int N, int C, int S, double radius_px,
                int K, float tau, int rad_pow, int accumulation, int bg_ksize, float *out_feat,
                uint8_t *out_bg, int32_t *out_idx, float *out_zbuf, float *out_dist, char *ws,
-               const SplatPlan &p, hipStream_t st, bool counters_cleared = false)
+               const SplatPlan &p, hipStream_t st, bool counters_cleared = false, const int32_t *counts = nullptr,
+               int n_max = 0)
 {
+    // counts (device, (B) int32): ragged clouds -- cloud b holds counts[b] <= N points in rows of N, n_max the largest of them
+    // (the host's bookkeeping: the binning grids cover n_max points per cloud).  Without counts: what this function always launched.
     uint32_t *bbox = (uint32_t *)(ws + p.off_bbox);
     uint32_t *tile_off = (uint32_t *)(ws + p.off_count);
     uint32_t *cursor = (uint32_t *)(ws + p.off_cursor);
@@ -821,10 +834,12 @@ int splat_core(const float *pts, const float *feat, int B, int N, int C, int S, 
     // counters (count + cursor + worklist are adjacent) start from zero every call
     // (the fused project + splat call has them cleared by its projection kernel)
     if (!counters_cleared) PS_HIP_CHECK(hipMemsetAsync(ws + p.off_count, 0, p.off_bg0 - p.off_count, st));
-    const dim3 gpt((N + 255) / 256, B);
-    hipLaunchKernelGGL(k_bin_count, gpt, dim3(256), 0, st, pts, N, S, p.hw, p.tilesX, p.NT, bbox, tile_off);
+    const dim3 gpt(((counts ? n_max : N) + 255) / 256, B);
+    if (counts) hipLaunchKernelGGL(k_bin_count<true>, gpt, dim3(256), 0, st, pts, N, S, p.hw, p.tilesX, p.NT, bbox, tile_off, counts);
+    else hipLaunchKernelGGL(k_bin_count<false>, gpt, dim3(256), 0, st, pts, N, S, p.hw, p.tilesX, p.NT, bbox, tile_off, counts);
     hipLaunchKernelGGL(k_scan, dim3(B), dim3(1024), 0, st, tile_off, p.NT, (uint32_t)((size_t)N * p.max_tiles_pp));
-    hipLaunchKernelGGL(k_bin_fill, gpt, dim3(256), 0, st, pts, N, p.tilesX, p.NT, bbox, tile_off, cursor, keys);
+    if (counts) hipLaunchKernelGGL(k_bin_fill<true>, gpt, dim3(256), 0, st, pts, N, p.tilesX, p.NT, bbox, tile_off, cursor, keys, counts);
+    else hipLaunchKernelGGL(k_bin_fill<false>, gpt, dim3(256), 0, st, pts, N, p.tilesX, p.NT, bbox, tile_off, cursor, keys, counts);
     hipLaunchKernelGGL(k_sort_small, dim3(p.NT, B), dim3(64), 0, st, keys, tile_off, p.NT, work);
     hipLaunchKernelGGL(k_sort_big, dim3(128), dim3(1024), 0, st, keys, tile_off, work);
     const dim3 gc(p.NT, B, (C + CG - 1) / CG);
@@ -868,6 +883,8 @@ int check_splat_args(int B, int N, int C, int S, double radius_px, int K, int ac
 
 }  // namespace
 
+// csrc/scene.hip includes this unit for its kernels and host core, without the C ABI of libpixelsynth_hip.so
+#ifndef PS_SPLAT_KERNELS_ONLY
 extern "C" {
 
 size_t ps_splat_workspace_bytes(int B, int N, int S, double radius_px)
@@ -1104,3 +1121,4 @@ int ps_read_status(int32_t *status, void *stream)
 }
 
 }  // extern "C"
+#endif  // PS_SPLAT_KERNELS_ONLY

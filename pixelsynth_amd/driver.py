@@ -5,6 +5,8 @@ create_vid.py for what this repository builds.
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \
            -m pixelsynth_amd.driver --trajectory circle --frames 64 --out results/         (C4: views sharded over 8 GPUs)
     python -m pixelsynth_amd.driver --scene R L --num-split 4 --out results/             (chained, as the reference's gen_scene)
+    python -m pixelsynth_amd.driver --scene R L --image-dir imgs/ --batch 16 --out results/   (many chained scenes, 16 at a time)
+    python -m pixelsynth_amd.driver --pairs directions.npy --image-dir imgs/ --out views/  (gen_two_imgs: what evaluate --consistency scores)
 
 One source image (a PNG, or the synthetic RealEstate10K-shaped sample), the demo cameras of process_demo_data
 (demo.py:36-96), target poses from ZbufferModelPts.get_rt_from_rot (directions 'R','L','U','D',... in `--frames`
@@ -18,9 +20,17 @@ from the previous generated frame on top of the accumulated point cloud; images 
 the reference's save_scene / save_video layout (demo.py:100-164).  A chain does not shard: with several ranks, rank r
 renders its own chain for direction list r (replicas).
 
-The depth regressor, the refinement decoder and trained weights are not part of this repository: depth
-is synthetic unless --depth-npy is given, weights are random-init unless --pixelcnn / --vqvae state dicts are given,
-and the saved image is the un-refined composite (reprojected features where visible, decoded sample elsewhere).
+Several source images (--image A B ..., or --image-dir) are several INDEPENDENT scenes: with --scene they run through the batched
+chained path in groups of --batch (forward_scene with B > 1: ragged clouds kept on the device) and are dealt over the ranks with
+distributed.shard_views -- no collective, every rank writes its own scenes, scene i to <out>/<%04d>/scene/ and <out>/<%04d>/video/.
+--pairs DIRECTIONS.npy (a 1-D array of direction indices into R L U D UL UR DR DL, one per image) runs gen_two_imgs the same way and
+writes the layout of the reference's eval_consistency.py:122-149 under <out>/<%04d>/: input_image_.png,
+output_image_<d>_0001.png, output_image_<d>_0002.png -- the views `python -m pixelsynth_amd.evaluate --consistency` lists.
+
+The depth regressor (networks.Unet) and the refinement decoder (networks.get_decoder) are part of the package, and ZbufferModelPts
+builds them from the reference's options (norm_G, refine_model_type); THIS driver builds the model without them and ships no trained
+weights: depth is synthetic unless --depth-npy is given, weights are random-init unless --pixelcnn / --vqvae state
+dicts are given, and the saved image is the un-refined composite (reprojected features where visible, decoded sample elsewhere).
 """
 import argparse
 import os
@@ -111,6 +121,93 @@ def scene_outputs_to_disk(outputs, directions, num_split, out_dir):
     return n
 
 
+MAPPING = ("R", "L", "U", "D", "UL", "UR", "DR", "DL")     # gen_two_imgs: index -> direction (eval_consistency.py:101)
+IMAGE_SUFFIXES = (".png", ".jpg", ".jpeg")
+
+
+def source_images(image, image_dir):
+    """--image / --image-dir -> the list of source paths, scene i = entry i (a directory's images in sorted order)."""
+    paths = list(image or [])
+    if image_dir:
+        if paths:
+            raise ValueError("--image and --image-dir exclude each other")
+        paths = sorted(os.path.join(image_dir, f) for f in os.listdir(image_dir) if f.lower().endswith(IMAGE_SUFFIXES))
+        if not paths:
+            raise ValueError(f"--image-dir {image_dir}: no {' / '.join(IMAGE_SUFFIXES)} image")
+    return paths
+
+
+def load_directions(path, n_scenes):
+    """--pairs DIRECTIONS.npy -> one direction index per scene (the file evaluate --consistency reads with --directions)."""
+    dirs = np.load(path)
+    if dirs.ndim != 1:
+        raise ValueError(f"{path}: a 1-D array of direction indices expected, got shape {dirs.shape}")
+    if len(dirs) < n_scenes:
+        raise ValueError(f"{path} holds {len(dirs)} directions for {n_scenes} source images")
+    dirs = [int(d) for d in dirs[:n_scenes]]
+    for i, d in enumerate(dirs):
+        if not 0 <= d < len(MAPPING):
+            raise ValueError(f"{path}: item {i}: direction {d} outside 0 .. {len(MAPPING) - 1}")
+    return dirs
+
+
+def scene_groups(n_scenes, batch, rank, world):
+    """The scenes of rank `rank`, dealt by distributed.shard_views, in groups of at most `batch` -> list of lists of scene indices.
+    Over the ranks every scene appears exactly once."""
+    if batch < 1:
+        raise ValueError(f"--batch must be >= 1, got {batch}")
+    mine = D.shard_views(n_scenes, rank, world)
+    return [mine[s:s + batch] for s in range(0, len(mine), batch)]
+
+
+def scene_dir(out_dir, index):
+    return os.path.join(out_dir, "%04d" % index)
+
+
+def scenes_to_disk(outputs, group, directions, num_split, out_dir):
+    """The outputs of a batched forward_scene (gen_scene) -> scene_outputs_to_disk's layout inside <out>/<%04d>/ for every scene of
+    `group` (slice b = scene group[b]).  -> video frames written per scene."""
+    n = 0
+    for b, index in enumerate(group):
+        one = {k: v[b:b + 1] for k, v in outputs.items() if k.startswith("PredImg_")}
+        n = scene_outputs_to_disk(one, directions, num_split, scene_dir(out_dir, index))
+    return n
+
+
+def pairs_to_disk(outputs, group, direction_ids, out_dir):
+    """The outputs of a batched forward_scene (gen_two_imgs) -> eval_consistency.py:122-149 under <out>/<%04d>/ for every scene of
+    `group`: the input and the views 1 and 2 of the scene's own direction."""
+    for b, (index, d) in enumerate(zip(group, direction_ids)):
+        name, folder = MAPPING[d], scene_dir(out_dir, index)
+        os.makedirs(folder, exist_ok=True)
+        save_png(os.path.join(folder, "input_image_.png"), outputs["InputImg"][b])
+        for i in (1, 2):
+            save_png(os.path.join(folder, "output_image_%s_%04d.png" % (name, i)), outputs[f"PredImg_{name}_{i}"][b])
+
+
+@torch.no_grad()
+def run_scenes(model, imgs, cam, groups, out_dir, directions=None, num_split=None, pair_directions=None):
+    """Independent chained scenes in batches: imgs {scene index: (1,3,S,S)}, cam the (1,4,4) demo cameras every scene starts from,
+    groups from scene_groups.  pair_directions {scene index: direction index}: gen_two_imgs and the --pairs layout; otherwise
+    gen_scene over `directions` and the per-scene scene/ + video/ layout.  -> scenes written."""
+    done = 0
+    for group in groups:
+        B = len(group)
+        batch = {"images": [torch.cat([imgs[i] for i in group])], "depth_fn": syn.depth_from_image,
+                 "cameras": [{k: v.expand(B, 4, 4).contiguous() for k, v in cam.items()}]}
+        if pair_directions is not None:
+            ids = [pair_directions[i] for i in group]
+            batch["direction"] = torch.tensor(ids)
+        _, outputs = model(batch)
+        model.outpaint2.engine(32, 32, B).check()
+        if pair_directions is not None:
+            pairs_to_disk(outputs, group, ids, out_dir)
+        else:
+            scenes_to_disk(outputs, group, directions, num_split, out_dir)
+        done += B
+    return done
+
+
 _SIDE = {}
 
 
@@ -193,18 +290,31 @@ def load_image(path, S=256):
 
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
-    ap.add_argument("--image", help="source PNG/JPEG (default: the synthetic sample)")
+    ap.add_argument("--image", nargs="+", metavar="PATH", help="source PNG/JPEG (default: the synthetic sample); several: one scene each "
+                                                                 "(with --scene or --pairs)")
+    ap.add_argument("--image-dir", help="a directory of source images, one scene each, in sorted order (with --scene or --pairs)")
+    ap.add_argument("--pairs", metavar="DIRECTIONS.npy", help="gen_two_imgs: per image the direction index of this 1-D array; writes "
+                                                             "<out>/<%%04d>/{input_image_,output_image_<d>_0001,output_image_<d>_0002}.png")
     ap.add_argument("--depth-npy", help="(S,S) float32 depth in [min_z, max_z] (default: synthetic smooth depth)")
     ap.add_argument("--trajectory", default="circle", help="circle | R | L | U | D | UL | UR | DL | DR")
     ap.add_argument("--scene", nargs="+", metavar="DIR", help="chained mode: directions of forward_scene, e.g. R L C")
     ap.add_argument("--num-split", type=int, default=4, help="--scene: views per direction (num_split)")
     ap.add_argument("--sequential", action="store_true", help="--scene: sequential_outpainting")
     ap.add_argument("--frames", type=int, default=64)
-    ap.add_argument("--batch", type=int, default=16, help="views rendered together per rank")
+    ap.add_argument("--batch", type=int, default=16, help="views (or, with several images, chained scenes) rendered together per rank")
     ap.add_argument("--out", default="results")
     ap.add_argument("--pixelcnn", help="state_dict of the reference's OurPixelCNN (torch.save)")
     ap.add_argument("--vqvae", help="state_dict of the reference's VQVAETop (torch.save)")
     args = ap.parse_args(argv)
+    sources = source_images(args.image, args.image_dir)
+    many = args.image_dir is not None or len(sources) > 1 or args.pairs is not None
+    if many and not (args.scene or args.pairs):
+        ap.error("several source images are several chained scenes: give --scene DIR ... or --pairs DIRECTIONS.npy")
+    if args.scene and args.pairs:
+        ap.error("--scene and --pairs exclude each other")
+    if args.pairs and not sources:
+        ap.error("--pairs needs --image ... or --image-dir")
+    pair_ids = load_directions(args.pairs, len(sources)) if args.pairs else None
 
     rank, world = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1))
     local = int(os.environ.get("LOCAL_RANK", 0))
@@ -224,7 +334,23 @@ def main(argv=None):
             torch.distributed.init_process_group("nccl", device_id=device)
     model = build_model(device, args.pixelcnn, args.vqvae)
     t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
-    img = (load_image(args.image) if args.image else torch.from_numpy(syn.image(1000, 1, 3, 256))).to(device)
+    if many:     # independent scenes: dealt over the ranks, no collective, every rank writes its own
+        groups = scene_groups(len(sources), args.batch, rank, world)
+        imgs = {i: load_image(sources[i]).to(device) for g in groups for i in g}
+        cam = {k: t(v) for k, v in syn.demo_cameras(1).items()}
+        model.opt.num_samples = 1
+        if args.pairs:
+            model.opt.model_setting, model.opt.num_split = "gen_two_imgs", 2      # (gen_two_imgs renders views 2, 1, 0 whatever num_split says)
+            n = run_scenes(model, imgs, cam, groups, args.out, pair_directions=dict(enumerate(pair_ids)))
+        else:
+            model.opt.directions, model.opt.num_split, model.opt.sequential_outpainting = list(args.scene), args.num_split, args.sequential
+            n = run_scenes(model, imgs, cam, groups, args.out, directions=list(args.scene), num_split=args.num_split)
+        print(f"rank {rank}: {n} of {len(sources)} scenes ({'pairs' if args.pairs else 'chained ' + ' '.join(args.scene)}) in groups of "
+              f"{args.batch} -> {args.out}/%04d/")
+        if world > 1:
+            torch.distributed.destroy_process_group()
+        return
+    img = (load_image(sources[0]) if sources else torch.from_numpy(syn.image(1000, 1, 3, 256))).to(device)
     depth = t(np.load(args.depth_npy)[None, None].astype(np.float32)) if args.depth_npy else t(syn.depth_smooth(2000, 1, 256, 1.0, 100.0))
     cam = {k: t(v) for k, v in syn.demo_cameras(1).items()}
     if args.scene:

@@ -4,12 +4,15 @@ models/projection/z_buffer_manipulator.py:PtsManipulator (same constructor and m
 project_pts / project_pts_cumulative run in csrc/splat.hip:k_project through the C ABI
 (ps_project_pts_f32, ps_project_pts_cumulative_f32); forward_justpts uses the fused
 ps_project_splat_f32 so the (B,N,3) cloud never leaves the scratch buffer.
+
+forward_scene_step advances B independent chained scenes by one frame on a SceneState -- per-scene clouds of different lengths that
+stay on the device between frames (csrc/scene.hip through ps_scene_step_f32, include/pixelsynth_scene.h).
 """
 import torch
 import torch.nn as nn
 
 from .. import _lib
-from ..layers.z_buffer_layers import ACCUMULATION, RasterizePointsXYsBlending, splat_workspace
+from ..layers.z_buffer_layers import _WS, ACCUMULATION, RasterizePointsXYsBlending, splat_workspace
 
 EPS = 1e-2
 
@@ -24,6 +27,55 @@ def get_splatter(name, depth_values, opt=None, size=256, C=64, points_per_pixel=
 
 def _f32c(t):
     return t if (t.dtype == torch.float32 and t.is_contiguous()) else t.float().contiguous()
+
+
+class SceneState:
+    """The accumulated point clouds of B independent chained scenes (include/pixelsynth_scene.h): a ping-pong pair of homogeneous
+    clouds (B,4,cap) and of their features (B,C,cap), the per-scene counts on the device (count (B) int32) and on the host (counts: the
+    bookkeeping every step is checked against before anything is enqueued).  Logical point i of scene b is column i: the last frame's
+    new points first, in row-major order of its mask, then the older cloud in its order (reference :248-266)."""
+
+    def __init__(self, B, C, cap, device):
+        self.B, self.C, self.cap = int(B), int(C), int(cap)
+        if self.B <= 0 or self.C <= 0 or self.cap <= 0:
+            raise ValueError(f"SceneState: B, C, cap must be positive (got {B}, {C}, {cap})")
+        self._cloud = torch.empty(2, self.B, 4, self.cap, dtype=torch.float32, device=device)
+        self._feat = torch.empty(2, self.B, self.C, self.cap, dtype=torch.float32, device=device)
+        self.count = torch.zeros(self.B, dtype=torch.int32, device=device)
+        self.counts = [0] * self.B
+        self._cur = 0
+        assert self.nbytes == _lib.call("ps_scene_state_bytes", self.B, self.C, self.cap)
+
+    @property
+    def nbytes(self):
+        return sum(t.numel() * t.element_size() for t in (self._cloud, self._feat, self.count))
+
+    @property
+    def cloud(self):
+        """(B,4,cap); scene b's points are cloud[b, :, :counts[b]]."""
+        return self._cloud[self._cur]
+
+    @property
+    def feats(self):
+        """(B,C,cap); scene b's features are feats[b, :, :counts[b]]."""
+        return self._feat[self._cur]
+
+    def reset(self):
+        """Forget every scene's cloud (the next step is a first frame)."""
+        self.counts = [0] * self.B
+        self.count.zero_()
+
+    def grown(self, cap):
+        """A state of capacity `cap` >= this one's with the same contents (a copy on the device)."""
+        if cap < max(self.counts):
+            raise ValueError(f"SceneState.grown: cap {cap} < the {max(self.counts)} points a scene already holds")
+        st = SceneState(self.B, self.C, cap, self.count.device)
+        n = min(self.cap, cap)
+        st._cloud[0, :, :, :n] = self.cloud[:, :, :n]
+        st._feat[0, :, :, :n] = self.feats[:, :, :n]
+        st.count.copy_(self.count)
+        st.counts = list(self.counts)
+        return st
 
 
 class PtsManipulator(nn.Module):
@@ -121,3 +173,52 @@ class PtsManipulator(nn.Module):
         _lib.call("ps_project_pts_cumulative_f32", depth, new_index, prior, _f32c(K), _f32c(K_inv), _f32c(RTinv_cam1), _f32c(RT_cam2), rt3,
                   B, self.W, n_new, n_prior, sampler, cloud)
         return sampler, cloud
+
+    # ------------------------------------------------------------------ a5 / a4 / a6, B scenes with ragged clouds
+    def forward_scene_step(self, state, src, pred_pts, K, K_inv, RT_cam1, RTinv_cam1, RT_cam2, RTinv_cam2,
+                           last_background_mask=None, RTinv_cam3=None, new_counts=None):
+        """forward_justpts_cumulative for B independent scenes at once, on the state the scenes keep on the device:
+        src (B,C,W,W) and pred_pts (B,1,W,W) of the frame rendered FROM, cameras (B,4,4); last_background_mask (B,W,W) bool and
+        RTinv_cam3 of the previously rendered frame, both None for the first frame of the chains (every pixel a point, as
+        forward_justpts; the state starts over).  -> (features (B,C,W,W), background_mask (B,W,W) bool); scene b's cloud and
+        features are state.cloud[b, :, :state.counts[b]] and state.feats[b, :, :state.counts[b]] -- bit for bit what
+        forward_justpts_cumulative returns for scene b alone.
+        new_counts: the number of set pixels of every scene's mask where the caller already has them on the host (the AR plan
+        reads the mask back: ARPlan.background_counts); otherwise they are read here (one copy of B integers).
+        A step after which a scene would hold more than state.cap points raises before anything is enqueued and names the scene;
+        the state is untouched."""
+        sp, S = self.splatter, self.W
+        B, C = src.shape[:2]
+        if (B, C) != (state.B, state.C) or tuple(src.shape[2:]) != (S, S) or pred_pts.numel() != B * S * S:
+            raise ValueError(f"forward_scene_step: src {tuple(src.shape)} / pred_pts {tuple(pred_pts.shape)} do not fit a state of "
+                             f"{state.B} scenes with {state.C} features at W = {S}")
+        first = last_background_mask is None
+        if first:
+            new_counts, prior = [S * S] * B, [0] * B
+            mask = rt3 = None
+        else:
+            if RTinv_cam3 is None or min(state.counts) <= 0:
+                raise ValueError("forward_scene_step: a chained frame needs RTinv_cam3 and a state that holds a first frame")
+            mask = last_background_mask.reshape(B, S, S)
+            mask = (mask if mask.dtype in (torch.bool, torch.uint8) else mask != 0).contiguous()
+            if new_counts is None:
+                new_counts = mask.view(B, -1).sum(1, dtype=torch.int32).tolist()
+            prior, rt3 = state.counts, _f32c(RTinv_cam3)
+        nxt = [int(p) + int(n) for p, n in zip(prior, new_counts)]
+        over = [b for b in range(B) if nxt[b] > state.cap]
+        if over:
+            b = over[0]
+            raise RuntimeError(f"forward_scene_step: scene {b} would hold {nxt[b]} points ({prior[b]} + {int(new_counts[b])} new), the "
+                               f"state was created with cap = {state.cap}" + (f" (also scenes {over[1:]})" if over[1:] else ""))
+        out = torch.empty(B, C, S, S, dtype=torch.float32, device=src.device)
+        bg = torch.empty(B, S, S, dtype=torch.uint8, device=src.device)
+        nbytes = _lib.call("ps_scene_workspace_bytes", B, state.cap, S, float(sp.radius))
+        ws = _WS.get(src.device, nbytes)
+        cur, other = state._cur, 1 - state._cur
+        _lib.call("ps_scene_step_f32", _f32c(pred_pts), _f32c(src), mask, state._cloud[cur], state._feat[cur], state._cloud[other],
+                  state._feat[other], state.count, _f32c(K), _f32c(K_inv), _f32c(RTinv_cam1), _f32c(RT_cam2), rt3, B, C, S, state.cap,
+                  max(prior), max(nxt), float(sp.radius), int(sp.points_per_pixel), float(sp._opt("tau", 1.0)), int(sp._opt("rad_pow", 2)),
+                  ACCUMULATION[sp._opt("accumulation", "alphacomposite")], int(sp._opt("background_smoothing_kernel_size", 13)),
+                  out, bg, ws, ws.numel())
+        state._cur, state.counts = other, nxt
+        return out, bg.view(torch.bool)

@@ -52,6 +52,8 @@ class _SceneState:
         self.out_RTinv = None         # inverse pose of the last rendered frame
         self.numerator = None
         self.direction = None
+        self.scenes = None            # B > 1: the projection.SceneState of the batch (ragged clouds kept on the device) in place of
+        self.new_counts = None        # cloud / feats, and the set pixels of every scene's `background` where the AR plan counted them
 
 
 class _PipeBuffers:
@@ -615,39 +617,104 @@ class ZbufferModelPts(nn.Module):
         that were background last time are new, a5), outpainting, state hand-over (:476-522 / :540-582)."""
         depth = self._scene_depth(st.img, batch)
         fs = st.img if getattr(self.opt, "use_rgb_features", True) else self.encoder(st.img)
-        gen_fs, background_mask, cloud, feats = self.pts_transformer.forward_justpts_cumulative(
-            fs, depth, K, K_inv, in_RT, in_RTinv, out_RT, out_RTinv, st.cloud, st.feats, st.background, st.out_RTinv)
+        B = st.img.shape[0]
+        cloud = feats = plan = uniforms = None
+        if B == 1:
+            gen_fs, background_mask, cloud, feats = self.pts_transformer.forward_justpts_cumulative(
+                fs, depth, K, K_inv, in_RT, in_RTinv, out_RT, out_RTinv, st.cloud, st.feats, st.background, st.out_RTinv)
+        else:
+            gen_fs, background_mask = self._scene_step_batched(st, fs, depth, K, K_inv, in_RT, in_RTinv, out_RT, out_RTinv)
+            # a scene is the same picture alone or in a batch: every scene gets the draws of a B = 1 run (candidate i: the (1, L)
+            # draw of manual_seed(i)), never row b of a (B, L) draw
+            L = self.obs[1] * self.obs[2]
+            uniforms = torch.rand(1, L, generator=torch.Generator(device="cpu").manual_seed(0)).expand(1, B, L).to(gen_fs.device)
         if not getattr(self.opt, "no_outpainting", False):
-            plan = build_ar_plan(background_mask, self.obs[1])
-            gen_img = self.get_best_sample(plan, self.vqvae.encode_codes(gen_fs), background_mask, gen_fs, netD, input_img)
+            plan = build_ar_plan(background_mask, self.obs[1], count_background=B > 1)
+            gen_img = self.get_best_sample(plan, self.vqvae.encode_codes(gen_fs), background_mask, gen_fs, netD, input_img,
+                                           uniforms=uniforms)
         else:
             gen_img = self._project_checked(gen_fs)
         st.img, st.cloud, st.feats, st.background, st.out_RTinv = gen_img, cloud, feats, background_mask, out_RTinv
+        st.new_counts = None if plan is None else plan.background_counts
         return gen_img, gen_fs, depth, background_mask
+
+    SCENE_CAP_FRAMES = 2   # frames' worth of points (W * W each) a batched chain's state starts with; it doubles when a frame needs more
+
+    def _scene_step_batched(self, st, fs, depth, K, K_inv, in_RT, in_RTinv, out_RT, out_RTinv):
+        """The reprojection + splat of one frame of B > 1 chained scenes on their SceneState (PtsManipulator.forward_scene_step): the
+        clouds stay on the device, every scene with its own length.  The host knows every scene's next count before the launch (the AR
+        plan of the last frame counted its mask), so the state grows here, ahead of the step, and the step itself never overflows."""
+        pm = self.pts_transformer
+        B, C, W = fs.shape[0], fs.shape[1], pm.W
+        if st.scenes is None:
+            from .projection.z_buffer_manipulator import SceneState
+            cap = int(getattr(self.opt, "scene_cap", 0) or self.SCENE_CAP_FRAMES * W * W)
+            st.scenes = SceneState(B, C, max(cap, W * W), fs.device)
+        new_counts = None
+        if st.background is not None:
+            new_counts = st.new_counts
+            if new_counts is None:      # (no_outpainting: no plan has read the mask)
+                new_counts = st.background.reshape(B, -1).sum(1, dtype=torch.int32).tolist()
+            need = max(p + int(n) for p, n in zip(st.scenes.counts, new_counts))
+            if need > st.scenes.cap:
+                st.scenes = st.scenes.grown(max(need, 2 * st.scenes.cap))
+        return pm.forward_scene_step(st.scenes, fs, depth, K, K_inv, in_RT, in_RTinv, out_RT, out_RTinv, st.background, st.out_RTinv,
+                                     new_counts=new_counts)
 
     @torch.no_grad()
     def forward_scene(self, batch, netD=None):
         """z_buffermodel.py:420-584 (model_setting gen_scene / gen_two_imgs): per direction, first the far end of the
         sweep (unless sequential_outpainting), then the views in between, every frame rendered from the previous
-        one on top of the accumulated point cloud.  B = 1, as in the reference (a5 needs equal counts per image).
-        -> (None, outputs) with the reference's keys PredImg_<dir>_<i>, FeaturesImg_..., PredDepthImg_..., ForegroundImg_..."""
+        one on top of the accumulated point cloud.
+        B = 1 runs as the reference does (a5 with boolean gathers, which need equal counts per image).  B > 1 -- images (B,3,S,S),
+        cameras (B,4,4), for gen_two_imgs a (B,) "direction" -- advances B INDEPENDENT scenes one frame per step together, their
+        clouds of different lengths kept on the device (_scene_step_batched); poses are built per scene and stacked, and slice b of
+        every output equals the B = 1 run of scene b.  With per-scene directions (gen_two_imgs) a value is stored under the key of
+        every direction in the batch: slice b is scene b's under ITS direction's keys.
+        -> (None, outputs) with the reference's keys PredImg_<dir>_<i>, FeaturesImg_..., PredDepthImg_..., ForegroundImg_...
+        (ForegroundImg_* (B,1,S,S))."""
         dev = next(self.parameters()).device   # (the renderer itself refuses anything but the GPU)
         input_img = batch["images"][0].to(dev)
         cam = {k: v.to(dev) for k, v in batch["cameras"][0].items() if torch.is_tensor(v)}
         K, K_inv, input_RT, input_RTinv = cam["K"], cam["Kinv"], cam["P"], cam["Pinv"]
         two = self.opt.model_setting == 'gen_two_imgs'
-        directions = [self.mapping[int(batch["direction"])]] if two else list(self.opt.directions)
+        B = input_img.shape[0]
+        if B == 1:
+            directions = [self.mapping[int(batch["direction"])]] if two else list(self.opt.directions)
+        else:
+            if max(int(getattr(self.opt, "num_samples", 1)), 1) > 1:
+                raise NotImplementedError("forward_scene with B > 1 renders one sample per frame (num_samples ranks candidates over the "
+                                          "whole batch): use num_samples = 1 or B = 1")
+            if any(v.shape[0] != B for v in (K, K_inv, input_RT, input_RTinv)):
+                raise ValueError(f"forward_scene: {B} images need (B,4,4) cameras")
+            if two:   # one sweep, every scene in its own direction
+                per_scene = [self.mapping[int(d)] for d in torch.as_tensor(batch["direction"]).reshape(-1).tolist()]
+                if len(per_scene) != B:
+                    raise ValueError(f"forward_scene: {B} images need a (B,) direction, got {len(per_scene)}")
+                directions = [tuple(per_scene)]
+            else:
+                directions = list(self.opt.directions)
         sequential = bool(getattr(self.opt, "sequential_outpainting", False))
         outputs = {"InputImg": input_img}
         st = _SceneState(input_img)
 
         def pose_of(direction, numerator, denom):
-            return self.get_rt_from_rot(direction, input_RT, numerator, denom)
+            if B == 1:
+                return self.get_rt_from_rot(direction, input_RT, numerator, denom)
+            # per scene, as a B = 1 run builds them (a (1,4,4) inverse each), then stacked
+            per = direction if isinstance(direction, tuple) else (direction,) * B
+            pairs = [self.get_rt_from_rot(d, input_RT[b:b + 1], numerator, denom) for b, d in enumerate(per)]
+            return torch.cat([p[0] for p in pairs]), torch.cat([p[1] for p in pairs])
+
+        def put(kind, direction, tag, value):
+            for d in (dict.fromkeys(direction) if isinstance(direction, tuple) else (direction,)):
+                outputs[f"{kind}_{d}_{tag}"] = value
 
         def summary(direction, tag, gen_fs, depth, background_mask):
-            outputs[f"FeaturesImg_{direction}_{tag}"] = gen_fs
-            outputs[f"PredDepthImg_{direction}_{tag}"] = depth
-            outputs[f"ForegroundImg_{direction}_{tag}"] = (~background_mask).repeat(input_img.shape[0], 1, 1, 1).float()
+            put("FeaturesImg", direction, tag, gen_fs)
+            put("PredDepthImg", direction, tag, depth)
+            # (B = 1: the reference's repeat(B, 1, 1, 1); its B x B result for a batch is not kept -- (B,1,S,S))
+            put("ForegroundImg", direction, tag, ((~background_mask).repeat(B, 1, 1, 1) if B == 1 else (~background_mask).unsqueeze(1)).float())
 
         for direction in directions:
             base = int(self.opt.num_split)
@@ -672,7 +739,7 @@ class ZbufferModelPts(nn.Module):
                 gen_img, gen_fs, depth, bgm = self._scene_frame(st, batch, K, K_inv, in_RT, in_RTinv, out_RT, out_RTinv,
                                                                 netD, input_img)
                 st.numerator, st.direction = num_split, direction
-                outputs[f"PredImg_{direction}_{num_split}"] = gen_img
+                put("PredImg", direction, num_split, gen_img)
                 summary(direction, num_split, gen_fs, depth, bgm)
                 todo = range(num_split - 1, -1, -1)
             else:
@@ -685,8 +752,8 @@ class ZbufferModelPts(nn.Module):
                 out_RTinv, out_RT = pose_of(direction, i, num_split)
                 gen_img, gen_fs, depth, bgm = self._scene_frame(st, batch, K, K_inv, in_RT, in_RTinv, out_RT, out_RTinv,
                                                                 netD, input_img)
-                outputs[f"PredImg_{direction}_{i}"] = gen_img
-                outputs[f"FeaturesImg_{direction}_{i}"] = gen_fs
+                put("PredImg", direction, i, gen_img)
+                put("FeaturesImg", direction, i, gen_fs)
                 if sequential and i == num_split:
                     summary(direction, num_split, gen_fs, depth, bgm)
                     st.direction = direction
