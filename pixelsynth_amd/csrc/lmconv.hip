@@ -150,6 +150,7 @@ const TuningEntry tuning_table[] = {
     {"wg_ti_out", &Tuning::wg_ti_out, 1, 2}, {"wg_ti_in", &Tuning::wg_ti_in, 2, 4}, {"wg_ti_dil", &Tuning::wg_ti_dil, 2, 4},
     {"item_sort", &Tuning::item_sort, 0, 2}, {"gemm_ws", &Tuning::gemm_ws, 0, 7},
     {"prefix_full", &Tuning::prefix_full, 0, 1}, {"prefix_cone_force", &Tuning::prefix_cone_force, 0, 1},
+    {"prefix_exact", &Tuning::prefix_exact, 0, 1}, {"prefix_compact", &Tuning::prefix_compact, 0, 1},
     {"tp_ahead", &Tuning::tp_ahead, 0, NST - 2}, {"col_ahead", &Tuning::col_ahead, 0, NST - 4},
     {"tp_min_cols", &Tuning::tp_min_cols, 1, 1 << 30}, {"tp_xcds", &Tuning::tp_xcds, -1, 7}, {"tp_fill", &Tuning::tp_fill, 0, 1},
     {"tp_affine", &Tuning::tp_affine, 0, 1}, {"tp_dequeue", &Tuning::tp_dequeue, 0, 1}, {"tp_ct8_xcds", &Tuning::tp_ct8_xcds, 0, 4}, {"tp_ct8_cols", &Tuning::tp_ct8_cols, 0, 1024},
@@ -499,6 +500,10 @@ int ps_pixelcnn_create(const float *const *params, int n_params, int H, int W, i
     if ((rc = dev_alloc(h, &h->perm_sorted, 2 * locs))) return fail_out(rc);
     if ((rc = dev_alloc(h, &h->perm_cnt, (size_t)2 * 512 * max_frames))) return fail_out(rc);
     if ((rc = dev_alloc(h, &h->perm_tsum, (size_t)2 * max_frames))) return fail_out(rc);
+    // the exact cone and the stages' own item lists (lmconv_grid.hip): 33 x 128 B and 32 x 8 KB per frame of a 32 x 32 grid (34 MB at 128 frames)
+    if ((rc = dev_alloc(h, &h->pbits, (size_t)N_EVAL * max_frames * ((h->L + 31) / 32)))) return fail_out(rc);
+    if ((rc = dev_alloc(h, &h->cperm, (size_t)(N_EVAL - 1) * locs))) return fail_out(rc);
+    if ((rc = dev_alloc(h, &h->cperm_cnt, (size_t)(N_EVAL - 1) * max_frames))) return fail_out(rc);
     if ((rc = dev_alloc(h, &h->taps, locs))) return fail_out(rc);
     if ((rc = dev_alloc(h, &h->nbr_tp, (size_t)2 * NST * 2 * TP_COL_CAP * NBR_LD))) return fail_out(rc);
     if ((rc = dev_alloc(h, &h->cnt_tp, 2 * tp_cnt_index(NST, 0)))) return fail_out(rc);
@@ -809,6 +814,10 @@ void *ps_pixelcnn_debug_cache(ps_pixelcnn *h, int what, int idx)
     if (what == 8) return h->done_col; // tuning: the latency form's `done` counters [NST][CNT_PAD] (dword 1 of a row: look-ahead waits that had to wait)
     if (what == 3) return h->nbr_tp;   // neighbour slots of the last throughput launch [NST][2][1024][160]
     if (what == 5) return h->pstart;   // (33, F) int32 of the last AR run's prefix pass: first rank evaluated per stage and frame
+    // the same pass's exact cone and the stages' own item lists -- idx 0: (33, F, ceil(L / 32)) uint32 bit sets by rank; 1: (32, maxF) int32
+    // entries per (product stage, share), a frame range's shares from its first frame on; 2: (32, maxF * L) int2 the lists, share s of a
+    // range at (f0 * L + s * frames per share * npre); 3: (2, maxF * L) int2 the sorted lists they were taken from
+    if (what == 10) return idx == 0 ? (void *)h->pbits : idx == 1 ? (void *)h->cperm_cnt : idx == 2 ? (void *)h->cperm : idx == 3 ? (void *)h->permq : nullptr;
 #ifdef PS_WG_TRACE_BUILD
     if (what == 6 || what == 7 || what == 9) return wg_trace_symbol(what);   // (lmconv_grid.hip)
 #endif

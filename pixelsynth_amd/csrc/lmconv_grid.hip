@@ -34,6 +34,14 @@ struct ItemMap {
     const int2 *permq;     // the same list as (item, location) pairs: one load instead of the chain position -> item -> order -> location
     const int32_t *end;    // (F) or null: frame f's prefix ends at rank end[f] <= npre (per-frame prefixes: the ranks from there on are
                            // its columns'); only with an order
+    const uint32_t *bits;  // (F, bw) or null: the EXACT set of ranks evaluated at this stage, one bit per rank (k_prefix_sets); takes the
+    int bw;                // place of `start` (a subset of its suffix, already cut at the frame's end); bw = 32-bit words per frame
+    // the stage's own item list (k_perm_compact): the entries of `permq` that are evaluated at this stage, share by share (a share = the
+    // frames of one XCD, or all of them: cparts = 8 / 1), in the order permq has them; share s starts at cq[s * cshare] and holds
+    // ccnt[s] entries.  Read by k_gemm_ws; every other kernel walks permq / the items and asks item_wanted.
+    const int2 *cq;
+    const int32_t *ccnt;
+    int cshare, cparts;
 };
 // item at position `pos` of the products' item list, -1 past its end
 __device__ __forceinline__ int item_at(const ItemMap &m, int pos, int nitems)
@@ -51,8 +59,9 @@ __device__ __forceinline__ void item_loc(const ItemMap &m, int item, int L, int 
 // is the item evaluated at this stage?
 __device__ __forceinline__ bool item_wanted(const ItemMap &m, int item)
 {
-    if (!m.start && !m.end) return true;
+    if (!m.start && !m.end && !m.bits) return true;
     const int fl = item / m.npre, r = item - fl * m.npre;
+    if (m.bits) return (m.bits[(size_t)(m.f0 + fl) * m.bw + (r >> 5)] >> (r & 31)) & 1u;   // (no bit at or behind the frame's end)
     return (!m.start || r >= m.start[m.f0 + fl]) && (!m.end || r < m.end[m.f0 + fl]);
 }
 
@@ -860,9 +869,32 @@ __global__ __launch_bounds__(WS_THREADS) void k_gemm_ws(GemmArgs a, PostArgs pa)
     __shared__ int sItem[MI], sLoc[MI];
     const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, i = lane & 15, kk = lane >> 4;
     const int xcd = blockIdx.x & (N_XCD - 1), tb = blockIdx.x >> 3;
-    const int y = xcd * a.tpx + tb;              // contiguous item ranges per XCD, as in k_gemm
-    if (tb >= a.tpx || y >= a.ny) return;
-    const int item0 = y * MI, ntaps = a.slot_first[a.nslots];
+    // The stage's own item list (k_perm_compact): only the evaluated items, so every tile that runs is full of them (the last of a
+    // share apart).  The grid is sized for ALL items -- the host does not know the counts -- and a workgroup past its share's live
+    // tiles leaves on one scalar load.  Shares of the XCDs: workgroup (xcd, tb) is tile tb of share xcd; one share: its live tiles
+    // are dealt to the XCDs in contiguous ranges, as the items are below.
+    int item0, iend;
+    const int2 *list = a.items.permq;
+    if (a.items.cq) {
+        list = a.items.cq;
+        if (a.items.cparts > 1) {
+            const int n = a.items.ccnt[xcd];
+            if (tb * MI >= n) return;
+            item0 = xcd * a.items.cshare + tb * MI;
+            iend = xcd * a.items.cshare + n;
+        } else {
+            const int n = a.items.ccnt[0], nt = (n + MI - 1) / MI, tl = (nt + N_XCD - 1) / N_XCD, yl = xcd * tl + tb;
+            if (tb >= tl || yl >= nt) return;
+            item0 = yl * MI;
+            iend = n;
+        }
+    } else {
+        const int y = xcd * a.tpx + tb;          // contiguous item ranges per XCD, as in k_gemm
+        if (tb >= a.tpx || y >= a.ny) return;
+        item0 = y * MI;
+        iend = a.nitems;
+    }
+    const int ntaps = a.slot_first[a.nslots];
     const f32x4 zero = {0.0f, 0.0f, 0.0f, 0.0f};
     {   // ---- set-up: rows and mask values of every (tap, item): lane = item, wave w does taps w, w + 4, w + 8.
         // Where the items were sorted, k_perm_scatter left (item, location | tap set << 12 | fractional-masks flag << 21) pairs: ONE load
@@ -872,9 +904,9 @@ __global__ __launch_bounds__(WS_THREADS) void k_gemm_ws(GemmArgs a, PostArgs pa)
         const int pos = item0 + lane;
         int item = -1, q = 0, pat = 0x1ff;
         bool frac = true;
-        if (pos < a.nitems) {
-            if (a.items.permq) {
-                const int2 v = a.items.permq[pos];
+        if (pos < iend) {
+            if (list) {
+                const int2 v = list[pos];
                 item = v.x; q = v.y & 4095; pat = (v.y >> 12) & 0x1ff; frac = (v.y >> 21) & 1;
             } else {
                 int fq;
@@ -882,7 +914,7 @@ __global__ __launch_bounds__(WS_THREADS) void k_gemm_ws(GemmArgs a, PostArgs pa)
                 item_loc(a.items, item, a.L, fq, q);
             }
         }
-        const bool valid = item >= 0 && item_wanted(a.items, item);
+        const bool valid = item >= 0 && (a.items.cq || item_wanted(a.items, item));   // (the stage's own list holds evaluated items only)
         const int f = a.items.f0 + (item >= 0 ? item / a.items.npre : 0), r = q / a.W, c = q - r * a.W;
         if (wave == 0) { sItem[lane] = valid ? item : -1; sLoc[lane] = valid ? f * a.L + q : 0; }
         for (int t = wave; t < ntaps; t += WS_WAVES) {
@@ -1133,6 +1165,106 @@ __global__ __launch_bounds__(1024) void k_prefix_starts(StartsArgs a)
 }
 
 // ------------------------------------------------------------------------------------------
+// The same cone as EXACT sets (tune.prefix_exact).  The suffix form evaluates every rank from the smallest one anybody reads; with the
+// whole-grid pass the largest phase of a step, the ranks inside that suffix that nobody reads (11-12 % of the items of PixelSynth's
+// orders) are worth leaving out too.  One workgroup per frame walks the stages backwards exactly as k_prefix_starts does, with one bit
+// per rank in LDS instead of one number: the set a stage evaluates, the ranks those read through their open taps one stage earlier
+// (plus themselves, for the residual input), and so on; everything is cut at the frame's own end.  The numpy restatement is
+// exact_need_sets (oracle/prefix_cone_oracle.py).  bits[(stage id * F + f) * bw + w], stage ids as above.
+// A thread owns ranks t, t + 1024, ... and keeps the ranks of their open, in-grid, in-prefix neighbours in registers (two per dword,
+// 0xFFFF = none), so a step of the walk is LDS traffic only.  K = ranks per thread: 1 for grids of up to 1024 locations, 2, 4.
+// ------------------------------------------------------------------------------------------
+constexpr int SETS_W = STARTS_MAXL / 32;
+template <int K>
+__global__ __launch_bounds__(1024) void k_prefix_sets(StartsArgs a, uint32_t *bits, int bw)
+{
+    __shared__ unsigned short rank[STARTS_MAXL];   // by location
+    __shared__ uint32_t need[NNODE][SETS_W];       // ranks of node n's activations that somebody reads
+    __shared__ uint32_t needX[NGATED][SETS_W];     // the same for the output of conv_input inside gated block g
+    __shared__ uint32_t col[2][SETS_W];            // what the COLUMNS (ranks >= npre) read through dilation-1 / dilation-2 taps
+    const int f = a.f0 + blockIdx.x, t = threadIdx.x, L = a.L, npre = a.pend ? a.pend[f] : a.npre;
+    const int32_t *ord = a.order + (size_t)f * L;
+    for (int r = t; r < L; r += 1024) rank[ord[r]] = (unsigned short)r;
+    for (int w = t; w < NNODE * SETS_W; w += 1024) (&need[0][0])[w] = 0u;
+    for (int w = t; w < NGATED * SETS_W; w += 1024) (&needX[0][0])[w] = 0u;
+    for (int w = t; w < 2 * SETS_W; w += 1024) (&col[0][0])[w] = 0u;
+    __syncthreads();
+    auto set_bit = [](uint32_t *s, int r) { atomicOr(&s[r >> 5], 1u << (r & 31)); };
+    uint32_t nb[2][K][4];
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        const int r = t + 1024 * k;
+#pragma unroll
+        for (int kind = 0; kind < 2; ++kind)
+#pragma unroll
+            for (int n = 0; n < 4; ++n) nb[kind][k][n] = 0xFFFFFFFFu;
+        if (r >= L) continue;
+        const int q = ord[r], y = q / a.W, x = q - y * a.W;
+#pragma unroll
+        for (int n = 0; n < 8; ++n) {
+            const int tap = n < 4 ? n : n + 1, dy = tap / 3 - 1, dx = tap % 3 - 1;
+#pragma unroll
+            for (int kind = 0; kind < 2; ++kind) {
+                const float *mask = kind == 0 ? a.mask_und : a.mask_dil;
+                const int yy = y + (kind + 1) * dy, xx = x + (kind + 1) * dx;
+                if (mask[((size_t)f * 9 + tap) * L + q] == 0.0f || yy < 0 || yy >= a.H || xx < 0 || xx >= a.W) continue;
+                const int nr = rank[yy * a.W + xx];
+                if (nr >= npre) continue;                       // (a column's activations are the column steps' business)
+                if (r >= npre) set_bit(col[kind], nr);
+                else nb[kind][k][n >> 1] = (n & 1) ? (nb[kind][k][n >> 1] & 0x0000FFFFu) | (uint32_t)nr << 16 : (nb[kind][k][n >> 1] & 0xFFFF0000u) | (uint32_t)nr;
+            }
+        }
+    }
+    __syncthreads();
+    // dst |= the prefix ranks of `src` and the prefix ranks they read through the open taps of mask kind `kind` (src != dst)
+    auto reads = [&](const uint32_t *src, uint32_t *dst, int kind) {
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            const int r = t + 1024 * k;
+            if (r >= npre || !((src[r >> 5] >> (r & 31)) & 1u)) continue;
+            set_bit(dst, r);
+#pragma unroll
+            for (int n = 0; n < 8; ++n) {
+                const uint32_t pair = kind == 0 ? nb[0][k][n >> 1] : nb[1][k][n >> 1];
+                const int nr = (int)((n & 1) ? pair >> 16 : pair & 0xFFFFu);
+                if (nr != 0xFFFF) set_bit(dst, nr);
+            }
+        }
+        __syncthreads();
+    };
+    auto join = [&](uint32_t *dst, const uint32_t *src) {      // dst |= src
+        for (int w = t; w < bw; w += 1024) dst[w] |= src[w];
+        __syncthreads();
+    };
+    auto emit = [&](int stage, const uint32_t *src) {
+        for (int w = t; w < bw; w += 1024) bits[((size_t)stage * a.F + f) * bw + w] = src[w];
+    };
+    for (int g = 0; g < NGATED; ++g) { join(needX[g], col[0]); join(need[a.g_in[g]], col[0]); }
+    for (int d = 0; d < 4; ++d) join(need[a.d_in[d]], col[1]);
+    const int kind[18] = {0, 0, 1, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};
+    const int idx[18] = {0, 1, 0, 2, 3, 1, 4, 5, 6, 7, 2, 8, 9, 10, 3, 11, 12, 13};
+    for (int e = 17; e >= 0; --e) {
+        if (kind[e] == 0) {
+            const int g = idx[e];
+            const uint32_t *so = need[a.g_out[g]];               // conv_out + gate
+            emit(15 + g, so);
+            reads(so, needX[g], 0);                              //   reads conv_input's output at its open taps
+            join(need[a.g_in[g]], so);                           //   and the residual input at the same location
+            const uint32_t *si = needX[g];                       // conv_input (+ nin_skip)
+            emit(1 + g, si);
+            reads(si, need[a.g_in[g]], 0);
+            if (a.g_skip[g] >= 0) join(need[a.g_skip[g]], si);
+        } else {
+            const int d = idx[e];
+            const uint32_t *sd = need[a.d_out[d]];
+            emit(29 + d, sd);
+            reads(sd, need[a.d_in[d]], 1);
+        }
+    }
+    emit(0, need[0]);   // u_init + norm_init
+}
+
+// ------------------------------------------------------------------------------------------
 // Items grouped by their set of open taps (round 5).  A tile of the products computes a tap for all its items as soon as ONE of
 // them has it open; a location has 4.7 of its 9 taps open on average (of every adjacent pair exactly one precedes the other), a
 // tile of 16 consecutive ranks of a frame 7.1 of 9, a tile of 32 already 8.1 -- a third of the MFMA work of the pass multiplied
@@ -1296,6 +1428,54 @@ __global__ __launch_bounds__(1024) void k_perm_scatter(PermArgs a)
         a.perm[kind][pos] = fl * a.npre + r;
         a.permq[kind][pos] = int2{fl * a.npre + r, q | pat << 12 | (int)(v & 1u) << 21};   // (item, location | tap set | fractional masks)
     }
+}
+
+// ------------------------------------------------------------------------------------------
+// The stages' own item lists.  The sorted list holds every position of the prefix, and since the sort the ranks a stage skips sit at
+// the head of every (tap set, frame) run -- spread through tiles that run anyway, at the full price of a workgroup (its set-up, its
+// chunks and barriers, its post op do not depend on how many of its 64 items are evaluated).  So every (stage, share) gets a list of
+// its evaluated entries alone: grid (32 product stages, shares), a workgroup walks its share's run of `permq` in order and keeps what
+// item_wanted keeps -- order inside a share unchanged (tap sets heaviest first, frame, rank), shares kept apart (an XCD's tiles read
+// its own frames' rows only).  out[(stage - 1) * stride + share * share_len ...], cnt[(stage - 1) * cnt_stride + share].
+// ------------------------------------------------------------------------------------------
+struct CompactArgs {
+    ItemMap items;              // npre, f0, end of the pass
+    const int2 *permq[2];       // the sorted lists (dilation 1 / dilation 2)
+    const int32_t *start;       // (N_EVAL, F) or null
+    const uint32_t *bits;       // (N_EVAL, F, bw) or null
+    int F, bw, nitems, share_len;
+    int2 *out;
+    size_t stride;
+    int32_t *cnt;
+    int cnt_stride;
+};
+__global__ __launch_bounds__(1024) void k_perm_compact(CompactArgs a)
+{
+    __shared__ int wsum[16];
+    const int stage = 1 + blockIdx.x, share = blockIdx.y, t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    ItemMap m = a.items;
+    m.start = a.start ? a.start + (size_t)stage * a.F : nullptr;
+    m.bits = a.bits ? a.bits + (size_t)stage * a.F * a.bw : nullptr;
+    m.bw = a.bw;
+    const int2 *in = a.permq[stage >= 1 + 2 * NGATED ? 1 : 0];
+    const int base = share * a.share_len, end = min(base + a.share_len, a.nitems);
+    int2 *out = a.out + (size_t)(stage - 1) * a.stride + base;
+    int kept = 0;
+    for (int p0 = base; p0 < end; p0 += 1024) {
+        const int p = p0 + t;
+        int2 v = int2{-1, 0};
+        if (p < end) v = in[p];
+        const bool w = v.x >= 0 && item_wanted(m, v.x);
+        const unsigned long long b = __ballot(w);
+        if (lane == 0) wsum[wave] = __popcll(b);
+        __syncthreads();
+        int before = 0, total = 0;
+        for (int k = 0; k < 16; ++k) { before += k < wave ? wsum[k] : 0; total += wsum[k]; }
+        if (w) out[kept + before + __popcll(b & ((1ull << lane) - 1ull))] = v;
+        kept += total;
+        __syncthreads();
+    }
+    if (t == 0) a.cnt[(size_t)(stage - 1) * a.cnt_stride + share] = kept;
 }
 
 struct UinitArgs {
@@ -1474,15 +1654,21 @@ void run_grid(ps_pixelcnn *h, int F, const int32_t *codes, const Masks &m, float
     // (with out_logits the caller also gets the logits of the prefix locations: every item is needed then.  tune.prefix_cone_force
     // keeps the elimination on for the parity test, which compares the logits of the WALKED locations only.)
     const bool cone = order && (!logits || h->tune.prefix_cone_force) && h->L <= STARTS_MAXL && !h->tune.prefix_full;
+    const bool exact = cone && h->tune.prefix_exact;    // the cone as exact sets (k_prefix_sets) instead of one start rank per stage
+    const int bw = (h->L + 31) / 32;
     if (cone) {
         StartsArgs sa{order, m.und, m.dil, h->H, h->W, h->L, npre, F, {}, {}, {}, {}, {}, h->pstart, f0, pend};
         for (int g = 0; g < NGATED; ++g) { sa.g_in[g] = h->gated[g].node_in; sa.g_out[g] = h->gated[g].node_out; sa.g_skip[g] = h->gated[g].node_skip; }
         for (int d = 0; d < 4; ++d) { sa.d_in[d] = h->dil[d].node_in; sa.d_out[d] = h->dil[d].node_out; }
         hipLaunchKernelGGL(k_prefix_starts, dim3(nf), dim3(1024), 0, st, sa);
+        if (exact && h->L <= 1024) hipLaunchKernelGGL(k_prefix_sets<1>, dim3(nf), dim3(1024), 0, st, sa, h->pbits, bw);
+        else if (exact && h->L <= 2048) hipLaunchKernelGGL(k_prefix_sets<2>, dim3(nf), dim3(1024), 0, st, sa, h->pbits, bw);
+        else if (exact) hipLaunchKernelGGL(k_prefix_sets<4>, dim3(nf), dim3(1024), 0, st, sa, h->pbits, bw);
     }
     // the products' item lists, grouped by open-tap set (one per mask kind); the frame range's own part of the scratch
     const int32_t *perm[2] = {nullptr, nullptr};
     const int2 *permq[2] = {nullptr, nullptr};
+    int cparts = 0, cshare = 0;                         // shares of the stages' own lists (0: there are none)
     if (h->tune.item_sort && h->L <= STARTS_MAXL && all_items.npre >= 2 && nf <= 2048) {
         PermArgs pa{};
         pa.order = order; pa.mask[0] = m.und; pa.mask[1] = m.dil;
@@ -1501,15 +1687,31 @@ void run_grid(ps_pixelcnn *h, int F, const int32_t *codes, const Masks &m, float
         hipLaunchKernelGGL(k_perm_sort, dim3(nf, 2), dim3(1024), 0, st, pa);
         hipLaunchKernelGGL(k_perm_scan, dim3((pa.nparts * PERM_KEYS * ((nf + pa.nparts - 1) / pa.nparts) + 1023) / 1024, 2), dim3(1024), 0, st, pa);
         hipLaunchKernelGGL(k_perm_scatter, dim3(nf, 2), dim3(1024), 0, st, pa);
+        if (cone && h->tune.prefix_compact) {   // the stages' own lists of evaluated items, for k_gemm_ws
+            cparts = pa.nparts;
+            cshare = cparts > 1 ? (nf / cparts) * all_items.npre : nitems;
+            CompactArgs ca{all_items, {permq[0], permq[1]}, exact ? nullptr : h->pstart, exact ? h->pbits : nullptr, F, bw, nitems, cshare,
+                           h->cperm + (size_t)f0 * h->L, locs, h->cperm_cnt + f0, h->maxF};
+            hipLaunchKernelGGL(k_perm_compact, dim3(N_EVAL - 1, cparts), dim3(1024), 0, st, ca);
+        }
     }
     float *const part = h->partial + (size_t)4 * f0 * h->L * (2 * NF);
     ItemMap items = all_items;
-    auto at_stage = [&](int stage_id) { items.start = cone ? h->pstart + (size_t)stage_id * F : nullptr; };
+    auto at_stage = [&](int stage_id) {
+        items.start = cone && !exact ? h->pstart + (size_t)stage_id * F : nullptr;
+        items.bits = exact ? h->pbits + (size_t)stage_id * F * bw : nullptr;
+        items.bw = bw;
+        items.cq = cparts && stage_id >= 1 ? h->cperm + (size_t)(stage_id - 1) * h->maxF * h->L + (size_t)f0 * h->L : nullptr;
+        items.ccnt = cparts && stage_id >= 1 ? h->cperm_cnt + (size_t)(stage_id - 1) * h->maxF + f0 : nullptr;
+        items.cshare = cshare;
+        items.cparts = cparts;
+    };
     // -> 0: raw slots in `partial`, 1: slots summed by the kernel, 2: the post op `post` done by the kernel as well
     auto gemm = [&](GemmArgs &a, const float *mask, const float *sum_bias = nullptr, const PostArgs *post = nullptr) {
         a.items = items;
         a.items.perm = mask == m.und ? perm[0] : mask == m.dil ? perm[1] : nullptr;
         a.items.permq = mask == m.und ? permq[0] : mask == m.dil ? permq[1] : nullptr;
+        if (!a.items.permq) { a.items.cq = nullptr; a.items.ccnt = nullptr; }   // (nin_out: no sorted list, no list of its own)
         a.H = h->H; a.W = h->W; a.L = h->L; a.nitems = nitems;
         a.mask = mask; a.mask_fstride = (size_t)9 * h->L; a.tiles_per_block = 1;
         a.partial = h->partial + (size_t)4 * f0 * h->L * (2 * NF);   // (the frame range's own part of the scratch: passes over disjoint ranges may run side by side)

@@ -95,6 +95,9 @@ struct Tuning {
     int item_sort = 2;           // whole-grid products: items grouped by their set of open taps (round 5).  0 = natural (frame, rank)
                                  // order, 1 = one sort over all frames, 2 = one per XCD share of the frames (the rows of a frame stay in one L2)
     int prefix_full = 0;         // 1: the prefix pass evaluates every item (no dependency-cone elimination)
+    int prefix_exact = 1;        // the cone as exact sets of ranks (k_prefix_sets) instead of one start rank per stage and frame: 11-12 % fewer items
+    int prefix_compact = 1;      // k_gemm_ws walks a list of the stage's evaluated items alone (k_perm_compact): the skipped ranks no longer sit
+                                 // inside tiles that run anyway (bit-identical, like prefix_exact: which items share a tile changes no bit)
     int prefix_cone_force = 0;   // 1: keep the elimination on when the caller asks for logits (parity tests: walked locations only)
     int tp_ahead = 16;           // stages [0, tp_ahead) of a throughput-form launch are computed by the launch in front of it (0: off)
     int col_ahead = 16;          // the same for the latency form (0: off -- k_column as before)
@@ -140,6 +143,9 @@ struct ps_pixelcnn {
     uint32_t *perm_sorted = nullptr;   // scratch: (key << 12 | rank) of every frame, sorted
     int32_t *perm_cnt = nullptr;    // scratch: [2][512 * maxF] run lengths -> first positions
     int32_t *perm_tsum = nullptr;   // scratch: [2][maxF] totals of that table's tiles of 1024 entries
+    uint32_t *pbits = nullptr;      // (N_EVAL, F, ceil(L / 32)) the exact set of ranks evaluated per stage and frame, a bit per rank (k_prefix_sets)
+    int2 *cperm = nullptr;          // [N_EVAL - 1][maxF * L] the product stages' own item lists: the evaluated entries of permq (k_perm_compact)
+    int32_t *cperm_cnt = nullptr;   // [N_EVAL - 1][maxF] their lengths, per share (a frame range's shares at its first frame on)
     int *ctl1 = nullptr;            // the chain roles' control records
     unsigned *cnt = nullptr;        // [2][NST][MAX_TILES] padded completion counters of the neighbour role, never reset
     int *err = nullptr;             // device flag: a bounded wait of a column launch ran out

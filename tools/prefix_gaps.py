@@ -17,7 +17,7 @@ d, host = bench.make_inputs(0, 128, dev)
 side = bench.side_stream()
 bench.run_steps(model, d, 1, 4, side)
 torch.cuda.synchronize()
-eng = model.outpaint2.engine(32, 32, 256)
+eng = model.outpaint2.engine(32, 32, model.pipe_frames(128))   # (the handle the pipelined step runs in)
 marks = []     # (kind, stream id, event)
 ev = lambda: torch.cuda.Event(enable_timing=True)
 real_prefix, real_cols = eng.ar_prefix, model._pipe_columns
