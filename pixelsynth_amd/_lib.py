@@ -1,5 +1,6 @@
 """ctypes binding of libpixelsynth_hip.so (the C ABI declared in include/pixelsynth_hip.h; the measurement / tuning / debugging
-entry points tests, bench.py and tools use are declared in include/pixelsynth_hip_debug.h).
+entry points tests, bench.py and tools use are declared in include/pixelsynth_hip_debug.h) and of the libraries beside it
+(_libraries.LIBRARIES): one prototype table each, one loader, library(name).
 
 The package calls the library through call() alone.  The product path has NO fallback: if the shared library is missing or a call
 fails, a RuntimeError is raised.  Nothing here (or anywhere under pixelsynth_amd/) imports oracle/.
@@ -8,11 +9,11 @@ import ctypes
 import os
 
 import numpy as np
-import torch   # (before the library is loaded: see lib())
+import torch   # (before the library is loaded: see library())
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("PS_HIP_LIB") or os.path.join(_HERE, "libpixelsynth_hip.so")   # (PS_HIP_LIB: tuning builds)
-_lib = None
+from . import _libraries
+
+LIB_PATH = _libraries.path(_libraries.MAIN)    # (PS_HIP_LIB: tuning builds)
 
 c_void_p, c_int, c_float, c_double, c_size_t = (ctypes.c_void_p, ctypes.c_int, ctypes.c_float,
                                                  ctypes.c_double, ctypes.c_size_t)
@@ -96,8 +97,7 @@ _PROTOS = {
 }
 
 
-# libpixelsynth_percsim.so (include/pixelsynth_percsim.h): the PercSim passes, a library of their own beside this one
-PERCSIM_LIB_PATH = os.path.join(_HERE, "libpixelsynth_percsim.so")
+# libpixelsynth_percsim.so (include/pixelsynth_percsim.h): the PercSim passes
 PERCSIM_PROTOS = {
     "ps_percsim_last_error": (ctypes.c_char_p, []),
     "ps_percsim_workspace_bytes": (c_size_t, [c_int] * 3),
@@ -105,20 +105,16 @@ PERCSIM_PROTOS = {
     "ps_percsim_tap": (RC, [c_void_p] + [c_int] * 5 + [c_void_p, c_void_p, c_size_t, STREAM]),
     "ps_percsim_finish": (RC, [c_void_p, c_size_t] + [c_int] * 3 + [c_void_p, c_void_p, STREAM]),
 }
-_percsim = None
 
-# libpixelsynth_consistency.so (include/pixelsynth_consistency.h): the homography consistency score, a library of its own as well
-CONSISTENCY_LIB_PATH = os.path.join(_HERE, "libpixelsynth_consistency.so")
+# libpixelsynth_consistency.so (include/pixelsynth_consistency.h): the homography consistency score
 CONSISTENCY_PROTOS = {
     "ps_consistency_last_error": (ctypes.c_char_p, []),
     "ps_consistency_workspace_bytes": (c_size_t, [c_int] * 3),
     "ps_consistency": (RC, [c_void_p] * 4 + [c_int, c_void_p, c_void_p, c_int, c_void_p] + [c_int] * 4 + [c_void_p, c_void_p, c_void_p,
                                                                                                          c_size_t, STREAM]),
 }
-_consistency = None
 
-# libpixelsynth_fid.so (include/pixelsynth_fid.h): the passes of the FID network, a library of its own as well
-FID_LIB_PATH = os.path.join(_HERE, "libpixelsynth_fid.so")
+# libpixelsynth_fid.so (include/pixelsynth_fid.h): the passes of the FID network
 FID_PROTOS = {
     "ps_fid_last_error": (ctypes.c_char_p, []),
     "ps_fid_input": (RC, [c_void_p, c_void_p] + [c_int] * 4 + [c_void_p, STREAM]),
@@ -128,10 +124,8 @@ FID_PROTOS = {
     "ps_fid_conv": (RC, [c_void_p, c_int, c_void_p, c_size_t, c_void_p] + [c_int] * 10 + [c_void_p, c_int, c_int, STREAM]),
     "ps_fid_pool": (RC, [c_void_p] + [c_int] * 6 + [c_void_p, c_int, c_int, STREAM]),
 }
-_fid = None
 
-# libpixelsynth_scene.so (include/pixelsynth_scene.h): the batched chained-scene step over ragged clouds, a library of its own as well
-SCENE_LIB_PATH = os.path.join(_HERE, "libpixelsynth_scene.so")
+# libpixelsynth_scene.so (include/pixelsynth_scene.h): the batched chained-scene step over ragged clouds
 SCENE_PROTOS = {
     "ps_scene_last_error": (ctypes.c_char_p, []),
     "ps_scene_state_bytes": (c_size_t, [c_int] * 3),
@@ -139,7 +133,14 @@ SCENE_PROTOS = {
     "ps_scene_step_f32": (RC, [c_void_p] * 13 + [c_int] * 6 + [c_double, c_int, c_float, c_int, c_int, c_int, c_void_p, c_void_p,
                                                                 c_void_p, c_size_t, STREAM]),
 }
-_scene = None
+
+# short name of _libraries.LIBRARIES -> its prototype table; _OWNER: entry point -> the table entry of its library, built once
+PROTOS = {"hip": _PROTOS, "percsim": PERCSIM_PROTOS, "consistency": CONSISTENCY_PROTOS, "fid": FID_PROTOS, "scene": SCENE_PROTOS}
+_ENTRIES = {e.name: e for e in _libraries.LIBRARIES}
+assert set(PROTOS) == set(_ENTRIES)
+_OWNER = {fn: _ENTRIES[name] for name, table in PROTOS.items() for fn in table}
+assert len(_OWNER) == sum(map(len, PROTOS.values())), "an entry point is declared in two prototype tables"
+_loaded = {}
 
 
 def exported_symbols():
@@ -147,108 +148,41 @@ def exported_symbols():
     return sorted(_PROTOS)
 
 
-def lib():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise RuntimeError(
-                f"{LIB_PATH} is missing: build it with `python -m pixelsynth_amd.build` "
-                "(there is no CPU/PyTorch fallback for the HIP path)")
+def library(name):
+    """The loaded library `name` of _libraries.LIBRARIES, its prototypes declared to ctypes"""
+    L = _loaded.get(name)
+    if L is None:
+        entry = _ENTRIES[name]
+        main = entry is _libraries.MAIN
+        if not main:
+            lib()                      # the runtime binding below is the main library's: it loads first
+        so = _libraries.path(entry)
+        if not os.path.exists(so):
+            raise RuntimeError(f"{so} is missing: build it with `python -m pixelsynth_amd.build` "
+                               "(there is no CPU/PyTorch fallback for the HIP path)")
         # torch is imported first (top of this module): it brings its own libamdhip64/libhsa-runtime64, and this library has
         # to bind to THAT runtime instance (same streams, same allocations) instead of loading a second one.
-        L = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in _PROTOS.items():
-            if not hasattr(L, name):
-                continue  # optional symbols are checked by tests/test_abi.py
-            fn = getattr(L, name)
+        L = ctypes.CDLL(so)
+        for fn_name, (res, args) in PROTOS[name].items():
+            if main and not hasattr(L, fn_name):
+                continue  # optional symbols (a tuning build's library) are checked by tests/test_abi.py
+            fn = getattr(L, fn_name)
             fn.restype = c_int if res is RC else res
             fn.argtypes = [c_void_p if a is STREAM else a for a in args]
-        _lib = L
-    return _lib
+        _loaded[name] = L
+    return L
 
 
-def percsim_lib():
-    global _percsim
-    if _percsim is None:
-        lib()                          # (the runtime binding: see lib())
-        if not os.path.exists(PERCSIM_LIB_PATH):
-            raise RuntimeError(f"{PERCSIM_LIB_PATH} is missing: build it with `python -m pixelsynth_amd.build` "
-                               "(there is no CPU/PyTorch fallback for the HIP path)")
-        L = ctypes.CDLL(PERCSIM_LIB_PATH)
-        for name, (res, args) in PERCSIM_PROTOS.items():
-            fn = getattr(L, name)
-            fn.restype = c_int if res is RC else res
-            fn.argtypes = [c_void_p if a is STREAM else a for a in args]
-        _percsim = L
-    return _percsim
-
-
-def consistency_lib():
-    global _consistency
-    if _consistency is None:
-        lib()                          # (the runtime binding: see lib())
-        if not os.path.exists(CONSISTENCY_LIB_PATH):
-            raise RuntimeError(f"{CONSISTENCY_LIB_PATH} is missing: build it with `python -m pixelsynth_amd.build` "
-                               "(there is no CPU/PyTorch fallback for the HIP path)")
-        L = ctypes.CDLL(CONSISTENCY_LIB_PATH)
-        for name, (res, args) in CONSISTENCY_PROTOS.items():
-            fn = getattr(L, name)
-            fn.restype = c_int if res is RC else res
-            fn.argtypes = [c_void_p if a is STREAM else a for a in args]
-        _consistency = L
-    return _consistency
-
-
-def fid_lib():
-    global _fid
-    if _fid is None:
-        lib()                          # (the runtime binding: see lib())
-        if not os.path.exists(FID_LIB_PATH):
-            raise RuntimeError(f"{FID_LIB_PATH} is missing: build it with `python -m pixelsynth_amd.build` "
-                               "(there is no CPU/PyTorch fallback for the HIP path)")
-        L = ctypes.CDLL(FID_LIB_PATH)
-        for name, (res, args) in FID_PROTOS.items():
-            fn = getattr(L, name)
-            fn.restype = c_int if res is RC else res
-            fn.argtypes = [c_void_p if a is STREAM else a for a in args]
-        _fid = L
-    return _fid
-
-
-def scene_lib():
-    global _scene
-    if _scene is None:
-        lib()                          # (the runtime binding: see lib())
-        if not os.path.exists(SCENE_LIB_PATH):
-            raise RuntimeError(f"{SCENE_LIB_PATH} is missing: build it with `python -m pixelsynth_amd.build` "
-                               "(there is no CPU/PyTorch fallback for the HIP path)")
-        L = ctypes.CDLL(SCENE_LIB_PATH)
-        for name, (res, args) in SCENE_PROTOS.items():
-            fn = getattr(L, name)
-            fn.restype = c_int if res is RC else res
-            fn.argtypes = [c_void_p if a is STREAM else a for a in args]
-        _scene = L
-    return _scene
-
-
-def _library_of(what):
-    """-> (the loaded library, the name of its last-error function) of the entry point `what`; libpixelsynth_hip.so for any other
-    label (callers of check() name their calls freely)"""
-    if what in PERCSIM_PROTOS:
-        return percsim_lib(), "ps_percsim_last_error"
-    if what in CONSISTENCY_PROTOS:
-        return consistency_lib(), "ps_consistency_last_error"
-    if what in FID_PROTOS:
-        return fid_lib(), "ps_fid_last_error"
-    if what in SCENE_PROTOS:
-        return scene_lib(), "ps_scene_last_error"
-    return lib(), "ps_last_error"
+def lib():
+    return library("hip")
 
 
 def check(rc, what):
+    """Raise for a nonzero status of the entry point `what`, with its library's last error; any other label reports through
+    libpixelsynth_hip.so's (callers name their calls freely)"""
     if rc != 0:
-        L, last = _library_of(what)
-        msg = getattr(L, last)()
+        entry = _OWNER.get(what, _libraries.MAIN)
+        msg = getattr(library(entry.name), entry.last_error)()
         raise RuntimeError(f"{what} failed (rc={rc}): {msg.decode() if msg else '?'}")
 
 
@@ -257,18 +191,17 @@ _POINTERS = (c_void_p, ctypes.c_char_p, ctypes.c_wchar_p)
 
 
 def call(name, *args, stream=None):
-    """The entry point `name` of _PROTOS (or PERCSIM_PROTOS, CONSISTENCY_PROTOS, FID_PROTOS, SCENE_PROTOS) on args: a torch tensor or numpy array goes as its data
-    pointer, None as NULL, a ctypes scalar or array (an out-parameter, a small host table) by reference; anything else (ints, floats,
-    bytes, the engine's handle) as ctypes converts it.  An entry point that ends in a STREAM gets the current stream appended (or
-    `stream`), and each of its tensor arguments must be a CUDA tensor on the current device: else RuntimeError, before anything is
-    queued.  A nonzero RC raises
-    RuntimeError (check); any other return value is handed back."""
-    table = next((t for t in (_PROTOS, PERCSIM_PROTOS, CONSISTENCY_PROTOS, SCENE_PROTOS) if name in t), FID_PROTOS)
-    res, types = table[name]
+    """The entry point `name` (of any table of PROTOS; KeyError for a name none declares) on args: a torch tensor or numpy array goes
+    as its data pointer, None as NULL, a ctypes scalar or array (an out-parameter, a small host table) by reference; anything else
+    (ints, floats, bytes, the engine's handle) as ctypes converts it.  An entry point that ends in a STREAM gets the current stream
+    appended (or `stream`), and each of its tensor arguments must be a CUDA tensor on the current device: else RuntimeError, before
+    anything is queued.  A nonzero RC raises RuntimeError (check); any other return value is handed back."""
+    owner = _OWNER[name].name
+    res, types = PROTOS[owner][name]
     queued = bool(types) and types[-1] is STREAM
     if len(args) != len(types) - queued:
         raise TypeError(f"{name} takes {len(types) - queued} arguments{' besides the stream' if queued else ''}, got {len(args)}")
-    fn = getattr(_library_of(name)[0], name)
+    fn = getattr(library(owner), name)
     conv, device = list(args), None
     for i, a in enumerate(args):
         if isinstance(a, torch.Tensor):

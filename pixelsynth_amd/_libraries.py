@@ -1,0 +1,36 @@
+"""The table of the native libraries: what build.py compiles and _lib.py loads.  No imports beyond os (build.py runs without torch).
+
+libpixelsynth_hip.so ("hip") is the C ABI of include/pixelsynth_hip.h, pinned at version 2; what was added after the pin (PercSim,
+the homography consistency score, the FID network's passes, the batched chained-scene step) lives in a library of its own beside it,
+with its own header and its own last-error function, so that the pinned set of exports never moves.  A further library is one more
+entry here and one prototype table in _lib.py.
+"""
+import os
+from collections import namedtuple
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+NO_CONTRACT = ["-ffp-contract=off"]
+
+# name: the short name library(name) takes; so: the file beside this module; units: (translation unit of csrc/, its flags);
+# headers: the public headers of include/ that declare its exports; last_error: the export that returns the text of a failure
+Library = namedtuple("Library", "name so units headers last_error")
+
+LIBRARIES = (
+    Library("hip", "libpixelsynth_hip.so",
+            [("splat.hip", NO_CONTRACT), ("lmconv.hip", NO_CONTRACT), ("lmconv_grid.hip", NO_CONTRACT),
+             ("lmconv_column.hip", NO_CONTRACT), ("lmconv_tp.hip", NO_CONTRACT), ("vq.hip", NO_CONTRACT), ("nets.hip", NO_CONTRACT),
+             ("conv_f16x3.hip", NO_CONTRACT + ["-Wno-inline-asm"]), ("conv_thin.hip", NO_CONTRACT), ("conv1x1.hip", NO_CONTRACT),
+             ("vq_ends.hip", NO_CONTRACT), ("metrics.hip", NO_CONTRACT), ("host_order.cpp", [])],
+            ("pixelsynth_hip.h", "pixelsynth_hip_debug.h"), "ps_last_error"),
+    Library("percsim", "libpixelsynth_percsim.so", [("percsim.hip", NO_CONTRACT)], ("pixelsynth_percsim.h",), "ps_percsim_last_error"),
+    Library("consistency", "libpixelsynth_consistency.so", [("consistency.hip", NO_CONTRACT)], ("pixelsynth_consistency.h",),
+            "ps_consistency_last_error"),
+    Library("fid", "libpixelsynth_fid.so", [("fid.hip", NO_CONTRACT)], ("pixelsynth_fid.h",), "ps_fid_last_error"),
+    Library("scene", "libpixelsynth_scene.so", [("scene.hip", NO_CONTRACT)], ("pixelsynth_scene.h",), "ps_scene_last_error"),
+)
+MAIN = LIBRARIES[0]
+
+
+def path(entry):
+    """Where the library lies: beside this module; PS_HIP_LIB (tuning builds) overrides the main one alone"""
+    return (entry is MAIN and os.environ.get("PS_HIP_LIB")) or os.path.join(HERE, entry.so)

@@ -14,19 +14,16 @@ find_homography(src, dst) restates cv2.findHomography with method 0 (HomographyE
 Levenberg-Marquardt iterations, modules/calib3d/src/fundam.cpp and levmarq.cpp of OpenCV 4.x) in batched fp64 numpy.  The warp is
 warpPerspective with INTER_LINEAR and BORDER_CONSTANT 0 (csrc/consistency.hip).
 """
-import ctypes
-
 import numpy as np
 import torch
 
-from . import _lib
+from . import _images, _lib
 from .networks import f16x3
+from .perceptual import check_pnet, network_pass, pairs_per_pass
 
 COLUMNS = ("psnr_vis_0", "psnr_vis_1", "psnr_vis", "percsim_vis_0", "percsim_vis_1", "percsim_vis")
 MAPPING = ("R", "L", "U", "D", "UL", "UR", "DR", "DL")    # :20-22, the direction names of the view files
-_DTYPES = {torch.float32: 0, torch.uint8: 1}             # PS_DTYPE_F32, PS_DTYPE_U8
 NO_PERCSIM, PERCSIM, PERCSIM_RAW = 0, 1, 2                # PS_CONSISTENCY_*
-_MAX_B = 65535                                            # grid.z of one launch
 _LM_ITERS = 10
 
 
@@ -213,33 +210,15 @@ def invert_map(H):
 
 
 def _check(img1, img2, mask1, mask2, pnet):
-    for name, t in (("img1", img1), ("img2", img2)):
-        if not torch.is_tensor(t):
-            raise TypeError(f"{name} must be a tensor")
-        if t.dim() != 4:
-            raise ValueError(f"{name} must be (B, 3, H, W), got shape {tuple(t.shape)}")
-    if img1.shape != img2.shape:
-        raise ValueError(f"img1 and img2 differ in shape: {tuple(img1.shape)} vs {tuple(img2.shape)}")
-    B, C, H, W = img1.shape
-    if C != 3:
-        raise ValueError(f"C must be 3, got {C}")
-    if B < 1 or H < 1 or W < 1:
-        raise ValueError(f"empty image batch {tuple(img1.shape)}")
-    if img1.dtype != img2.dtype or img1.dtype not in _DTYPES:
-        raise TypeError(f"img1 and img2 must both be float32 or both uint8, got {img1.dtype} and {img2.dtype}")
+    """-> (B, H, W, the device)"""
+    B, _, H, W = _images.check_images({"img1": img1, "img2": img2}, (3,), "(B, 3, H, W)")
     for name, m in (("mask1", mask1), ("mask2", mask2)):
-        if not torch.is_tensor(m) or tuple(m.shape) != (B, 1, H, W):
-            raise ValueError(f"{name} must be (B, 1, H, W) = {(B, 1, H, W)}, got {tuple(getattr(m, 'shape', ()))}")
-        if m.dtype not in _DTYPES:
-            raise TypeError(f"{name} must be float32 or uint8, got {m.dtype}")
+        _images.check_mask(name, m, (B, 1, H, W), _images.CODED)
     if mask1.dtype != mask2.dtype:
         raise TypeError(f"mask1 and mask2 must have one dtype, got {mask1.dtype} and {mask2.dtype}")
-    if pnet is not None and (not hasattr(pnet, "hip_takes") or not hasattr(pnet, "torch_forward")):
-        raise TypeError("pnet must be a networks.pretrained_networks.PNet")
-    _lib.require_cuda(img1, img2, mask1, mask2)
-    devs = {t.device for t in (img1, img2, mask1, mask2)}
-    if len(devs) != 1:
-        raise ValueError(f"img1, img2, mask1 and mask2 must be on one device, got {sorted(map(str, devs))}")
+    if pnet is not None:
+        check_pnet(pnet)
+    return B, H, W, _images.same_device(img1=img1, img2=img2, mask1=mask1, mask2=mask2)
 
 
 def _maps(B, H12, H21, points):
@@ -257,22 +236,15 @@ def _maps(B, H12, H21, points):
     return np.ascontiguousarray(np.stack([invert_map(H21), invert_map(H12)], 1).reshape(B, 2, 9))
 
 
-def _strides(t):
-    return (ctypes.c_int64 * 4)(*t.stride())
-
-
 def _launch(img1, img2, mask1, mask2, maps, mode, pin, psnr):
     B, _, H, W = img1.shape
-    nbytes = _lib.call("ps_consistency_workspace_bytes", B, H, W)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=img1.device)
-    _lib.call("ps_consistency", img1, _strides(img1), img2, _strides(img2), _DTYPES[img1.dtype], mask1, mask2, _DTYPES[mask1.dtype],
-              maps, B, H, W, mode, pin, psnr, ws, nbytes)
+    ws, nbytes = _images.workspace("ps_consistency_workspace_bytes", B, H, W, device=img1.device)
+    _lib.call("ps_consistency", img1, _images.strides(img1), img2, _images.strides(img2), _images.DTYPES[img1.dtype], mask1, mask2,
+              _images.DTYPES[mask1.dtype], maps, B, H, W, mode, pin, psnr, ws, nbytes)
 
 
 def consistency_rows(img1, img2, mask1, mask2, H12=None, H21=None, points=None, pnet=None):
-    _check(img1, img2, mask1, mask2, pnet)
-    B, _, H, W = img1.shape
-    dev = img1.device
+    B, H, W, dev = _check(img1, img2, mask1, mask2, pnet)
     mask1, mask2 = mask1.contiguous(), mask2.contiguous()
     maps = torch.from_numpy(_maps(B, H12, H21, points)).to(dev)
     probe = torch.empty((1, 3, H, W), dtype=torch.float32, device=dev)   # what PercSim's HIP path takes (no data is read)
@@ -280,15 +252,11 @@ def consistency_rows(img1, img2, mask1, mask2, H12=None, H21=None, points=None, 
     def run():
         out = torch.empty(B, 6 if pnet is not None else 3, dtype=torch.float32, device=dev)
         hip = pnet is not None and pnet.hip_takes(probe, probe)
-        if pnet is None:
-            per = _MAX_B
-        else:
-            from .perceptual import pairs_per_pass
-            per = max(1, min(_MAX_B, pairs_per_pass(H, W) // 2))          # items per network pass (2 pairs each)
+        # items per launch; with a PNet, per network pass (2 pairs each)
+        per = _images.MAX_B if pnet is None else max(1, min(_images.MAX_B, pairs_per_pass(H, W) // 2))
         with torch.cuda.device(dev):
             layers = pnet.hip_layers(dev) if hip else None
-            for b0 in range(0, B, per):
-                b1 = min(B, b0 + per)
+            for b0, b1 in _images.batches(B, per):
                 n = b1 - b0
                 psnr = torch.empty(n, 2, dtype=torch.float32, device=dev)
                 pin = None if pnet is None else torch.empty((4 * n, H, W, 4), dtype=torch.float32, device=dev)
@@ -297,8 +265,7 @@ def consistency_rows(img1, img2, mask1, mask2, H12=None, H21=None, points=None, 
                 out[b0:b1, 0:2] = psnr
                 if pnet is not None:
                     if hip:
-                        from .perceptual import _network
-                        _, total = _network(layers, pin.permute(0, 3, 1, 2), 2 * n, H, W)
+                        _, total = network_pass(layers, pin.permute(0, 3, 1, 2), 2 * n, H, W)
                     else:                                                  # PNet.forward's torch formula on the same inputs
                         x = pin[..., :3].permute(0, 3, 1, 2)
                         total = pnet.torch_forward(x[:2 * n], x[2 * n:])

@@ -15,7 +15,7 @@
 //                         Then the masked comparison in the reference's fp32 operations, and the tile's fp64 sums of m sum_c d^2 and
 //                         of m, reduced in a fixed tree and written to the workspace.  No atomics.
 //   k_consistency_finish  one thread per (item, direction): the tile sums in tile order (fp64), PSNR clamped at 100.
-#include "ps_common.h"
+#include "ps_image.h"
 #include "../../include/pixelsynth_consistency.h"
 
 #include <climits>
@@ -25,23 +25,20 @@ namespace {
 
 constexpr int TX = 64, TY = 4, C_THREADS = TX * TY;
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-struct Img {
-    const void *p;
-    long long sB, sC, sH, sW;            // element strides
-};
+using ps::c_pnet_scale;
+using ps::c_pnet_shift;
+using ps::f32x4;
+using ps::Img;
 
 // TF.to_tensor's value of an input element: fp32 as it is; a byte b as fl32(b / 255), the true division of float().div(255) on the
-// host (not a multiply by the reciprocal), looked up in the workgroup's table of the 256 quotients (16 byte reads per pixel)
+// host (not a multiply by the reciprocal), looked up in the workgroup's table of the 256 quotients (16 byte reads per pixel): this
+// unit's variant of ps::to_unit
 __device__ __forceinline__ float to_unit(float v, const float *) { return v; }
 __device__ __forceinline__ float to_unit(uint8_t v, const float *quot) { return quot[v]; }
 static_assert(C_THREADS == 256, "a thread per entry of the byte table");
 
-// PNet's shift / scale (pretrained_networks.py:45-46) as the fp32 values torch.Tensor([...]) holds: RGB constants, applied to the
-// BGR-ordered channels as the reference does (calc_errors_consistency_homography.py:24-30 feeds cv2's channel order to PNet)
-__constant__ float c_shift[3] = {-0.030f, -0.088f, -0.188f};
-__constant__ float c_scale[3] = {0.458f, 0.448f, 0.450f};
+// PNet's shift / scale (ps_image.h) are RGB constants, applied to the BGR-ordered channels as the reference does
+// (calc_errors_consistency_homography.py:24-30 feeds cv2's channel order to PNet)
 
 // std::max((double)INT_MIN, std::min((double)INT_MAX, v)) then saturate_cast<int> (round to nearest even)
 __device__ __forceinline__ int cv_round_clamped(double v)
@@ -104,8 +101,8 @@ __global__ __launch_bounds__(C_THREADS) void k_consistency_tiles(Img v1, Img v2,
             d2 += (double)(d * d);
             if (pmode != PS_CONSISTENCY_NO_PERCSIM) {
                 const float ta = a * 2.0f - 1.0f, tb = b * 2.0f - 1.0f;   // evaluation/metrics.py:27-31
-                oa[j] = pmode == PS_CONSISTENCY_PERCSIM ? (ta - c_shift[j]) / c_scale[j] : ta;
-                ob[j] = pmode == PS_CONSISTENCY_PERCSIM ? (tb - c_shift[j]) / c_scale[j] : tb;
+                oa[j] = pmode == PS_CONSISTENCY_PERCSIM ? (ta - c_pnet_shift[j]) / c_pnet_scale[j] : ta;
+                ob[j] = pmode == PS_CONSISTENCY_PERCSIM ? (tb - c_pnet_shift[j]) / c_pnet_scale[j] : tb;
             }
         }
         s_d = (double)m * d2;
@@ -118,14 +115,7 @@ __global__ __launch_bounds__(C_THREADS) void k_consistency_tiles(Img v1, Img v2,
     }
     red[tid] = s_d;
     red[C_THREADS + tid] = s_m;
-    __syncthreads();
-    for (int h = C_THREADS / 2; h > 0; h >>= 1) {
-        if (tid < h) {
-            red[tid] += red[tid + h];
-            red[C_THREADS + tid] += red[C_THREADS + tid + h];
-        }
-        __syncthreads();
-    }
+    PS_BLOCK_TREE_SUM(red, tid, 2, C_THREADS);
     if (tid < 2) ws[(((size_t)item * 2 + k) * gridDim.x + tile) * 2 + tid] = red[tid * C_THREADS];
 }
 
@@ -172,33 +162,26 @@ int ps_consistency(const void *view1, const int64_t *strides1, const void *view2
                    const void *mask2, int mask_dtype, const double *inv_maps, int B, int H, int W, int percsim_mode, float *percsim_in,
                    float *psnr, void *workspace, size_t workspace_bytes, void *stream)
 {
-    PS_REQUIRE(view1 && view2 && strides1 && strides2 && mask1 && mask2 && inv_maps && psnr, "consistency: null pointer");
-    PS_REQUIRE(dtype == PS_DTYPE_F32 || dtype == PS_DTYPE_U8, "consistency: dtype must be PS_DTYPE_F32 or PS_DTYPE_U8 (got %d)", dtype);
+    PS_REQUIRE_IMAGES("consistency", view1 && view2 && strides1 && strides2 && mask1 && mask2 && inv_maps && psnr, dtype, B, strides1,
+                      strides2);
     PS_REQUIRE(mask_dtype == PS_DTYPE_F32 || mask_dtype == PS_DTYPE_U8,
                "consistency: mask_dtype must be PS_DTYPE_F32 or PS_DTYPE_U8 (got %d)", mask_dtype);
-    PS_REQUIRE(B >= 1 && B <= 65535, "consistency: 1 <= B <= 65535 required (B = %d)", B);
     PS_REQUIRE(H >= 1 && W >= 1 && H <= 32767 && W <= 32767, "consistency: 1 <= H, W <= 32767 required (H = %d, W = %d)", H, W);
     PS_REQUIRE(percsim_mode >= PS_CONSISTENCY_NO_PERCSIM && percsim_mode <= PS_CONSISTENCY_PERCSIM_RAW, "consistency: percsim_mode %d",
                percsim_mode);
     PS_REQUIRE((percsim_mode == PS_CONSISTENCY_NO_PERCSIM) == (percsim_in == nullptr),
                "consistency: percsim_in goes with PS_CONSISTENCY_PERCSIM / _PERCSIM_RAW");
     PS_REQUIRE(((uintptr_t)percsim_in & 15) == 0, "consistency: percsim_in must be 16-byte aligned");
-    for (int i = 0; i < 4; ++i)
-        PS_REQUIRE(strides1[i] >= 0 && strides2[i] >= 0, "consistency: negative stride");
     const size_t need = ps_consistency_workspace_bytes(B, H, W);
     PS_REQUIRE(workspace && workspace_bytes >= need, "consistency: workspace of %zu bytes required (got %zu)", need, workspace_bytes);
-    const Img a{view1, strides1[0], strides1[1], strides1[2], strides1[3]};
-    const Img b{view2, strides2[0], strides2[1], strides2[2], strides2[3]};
+    const Img a(view1, strides1), b(view2, strides2);
     double *ws = (double *)workspace;
     const hipStream_t s = (hipStream_t)stream;
-    if (dtype == PS_DTYPE_F32 && mask_dtype == PS_DTYPE_F32)
-        launch<float, float>(a, b, mask1, mask2, inv_maps, B, H, W, percsim_mode, percsim_in, ws, s);
-    else if (dtype == PS_DTYPE_F32)
-        launch<float, uint8_t>(a, b, mask1, mask2, inv_maps, B, H, W, percsim_mode, percsim_in, ws, s);
-    else if (mask_dtype == PS_DTYPE_F32)
-        launch<uint8_t, float>(a, b, mask1, mask2, inv_maps, B, H, W, percsim_mode, percsim_in, ws, s);
-    else
-        launch<uint8_t, uint8_t>(a, b, mask1, mask2, inv_maps, B, H, W, percsim_mode, percsim_in, ws, s);
+    ps::for_dtype(dtype, [&](auto t) {
+        ps::for_dtype(mask_dtype, [&](auto tm) {
+            launch<decltype(t), decltype(tm)>(a, b, mask1, mask2, inv_maps, B, H, W, percsim_mode, percsim_in, ws, s);
+        });
+    });
     PS_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_consistency_finish, dim3((2 * B + 63) / 64), dim3(64), 0, s, (const double *)ws, B, tiles_of(H, W), psnr);
     PS_LAUNCH_CHECK();

@@ -27,24 +27,17 @@
 // zero (j = 0 .. 3 outer, group kk = 0 .. 3 inner, k = 16 chunk + 4 kk + j); the chunks of four stages (16 chunks, ascending) are added
 // into a middle sum; the middle sums are added in ascending order; the bias last.  The adds are VALU work under the MFMAs.  The order
 // depends on nothing but the layer: bit-reproducible, batch-split invariant.
-#include "ps_common.h"
+#include "ps_image.h"
 #include "../../include/pixelsynth_fid.h"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using ps::f32x4;
+using ps::Img;
+using ps::to_unit;
 
 constexpr int FID_SIZE = 299;
 constexpr int CV_THREADS = 256, CV_WAVES = 4, CV_STAGE_K = 64;
-
-struct Img {
-    const void *p;
-    long long sB, sC, sH, sW;            // element strides
-};
-
-template <typename T> __device__ __forceinline__ float to_unit(T v);
-template <> __device__ __forceinline__ float to_unit<float>(float v) { return v; }
-template <> __device__ __forceinline__ float to_unit<uint8_t>(uint8_t v) { return (float)v / 255.0f; }   // TF.to_tensor's division
 
 template <typename T>
 __global__ __launch_bounds__(256) void k_fid_input(Img im, int H, int W, float sh, float sw, f32x4 *__restrict__ out)
@@ -267,19 +260,15 @@ const char *ps_fid_last_error(void) { return ps::last_error_ref().c_str(); }
 
 int ps_fid_input(const void *img, const int64_t *strides, int dtype, int B, int H, int W, float *out, void *stream)
 {
-    PS_REQUIRE(img && strides && out, "fid_input: null pointer");
-    PS_REQUIRE(dtype == PS_DTYPE_F32 || dtype == PS_DTYPE_U8, "fid_input: dtype must be PS_DTYPE_F32 or PS_DTYPE_U8 (got %d)", dtype);
-    PS_REQUIRE(B >= 1 && B <= 65535, "fid_input: 1 <= B <= 65535 required (B = %d)", B);
+    PS_REQUIRE_IMAGES("fid_input", img && strides && out, dtype, B, strides, nullptr);
     PS_REQUIRE(H >= 1 && W >= 1 && (size_t)H * W < ((size_t)1 << 31), "fid_input: H = %d, W = %d", H, W);
     PS_REQUIRE(((uintptr_t)out & 15) == 0, "fid_input: out must be 16-byte aligned");
-    for (int i = 0; i < 4; ++i) PS_REQUIRE(strides[i] >= 0, "fid_input: negative stride");
-    const Img im{img, strides[0], strides[1], strides[2], strides[3]};
+    const Img im(img, strides);
     const float sh = (float)H / (float)FID_SIZE, sw = (float)W / (float)FID_SIZE;
     const dim3 grid((FID_SIZE * FID_SIZE + 255) / 256, B);
-    if (dtype == PS_DTYPE_F32)
-        hipLaunchKernelGGL(k_fid_input<float>, grid, dim3(256), 0, (hipStream_t)stream, im, H, W, sh, sw, (f32x4 *)out);
-    else
-        hipLaunchKernelGGL(k_fid_input<uint8_t>, grid, dim3(256), 0, (hipStream_t)stream, im, H, W, sh, sw, (f32x4 *)out);
+    ps::for_dtype(dtype, [&](auto t) {
+        hipLaunchKernelGGL(k_fid_input<decltype(t)>, grid, dim3(256), 0, (hipStream_t)stream, im, H, W, sh, sw, (f32x4 *)out);
+    });
     PS_LAUNCH_CHECK();
     return PS_OK;
 }

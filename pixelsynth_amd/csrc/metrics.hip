@@ -16,11 +16,14 @@
 // Per-tile sums (fp64), m = mask, n = 1 - m (fp32, as the caller of the reference forms it):
 //   0: sum_c,p d^2     1: sum_p m sum_c d^2     2: sum_p n sum_c d^2     3: sum_p m     4: sum_p n
 //   5: sum_c,p ssim    6: sum_p m mean_c ssim   7: sum_p n mean_c ssim                 (d = x - y in fp32, squared in fp32)
-#include "ps_common.h"
+#include "ps_image.h"
 
 #include <cmath>
 
 namespace {
+
+using ps::Img;
+using ps::to_unit;
 
 constexpr int MT = 32;                   // output tile edge
 constexpr int MR = 5;                    // window radius
@@ -31,16 +34,6 @@ constexpr int M_SUMS = 8;
 // gaussian(11, 1.5) / its fp32 sum, as models/losses/ssim.py:12-19 builds it in fp32 (tests/test_metrics_cpu.py re-derives them)
 __constant__ float c_gauss[11] = {0x1.0d956cp-10f, 0x1.f1fe02p-8f, 0x1.26eb18p-5f, 0x1.bff0fep-4f, 0x1.b43c3ep-3f, 0x1.106560p-2f,
                                   0x1.b43c3ep-3f,  0x1.bff0fep-4f, 0x1.26eb18p-5f, 0x1.f1fe02p-8f, 0x1.0d956cp-10f};
-
-struct Img {
-    const void *p;
-    long long sB, sC, sH, sW;            // element strides
-};
-
-template <typename T> __device__ __forceinline__ float to_unit(T v);
-template <> __device__ __forceinline__ float to_unit<float>(float v) { return v; }
-// true division, as TF.to_tensor's float().div(255) on the host (not a multiply by the reciprocal)
-template <> __device__ __forceinline__ float to_unit<uint8_t>(uint8_t v) { return (float)v / 255.0f; }
 
 template <typename T>
 __global__ __launch_bounds__(M_THREADS) void k_metrics_tiles(Img a, Img b, const float *mask, int C, int H, int W, int tiles_x,
@@ -134,14 +127,7 @@ __global__ __launch_bounds__(M_THREADS) void k_metrics_tiles(Img a, Img b, const
     double *red = hm;                                    // [sum][thread]
 #pragma unroll
     for (int k = 0; k < M_SUMS; ++k) red[k * M_THREADS + tid] = s[k];
-    __syncthreads();
-    for (int h = M_THREADS / 2; h > 0; h >>= 1) {
-        if (tid < h) {
-#pragma unroll
-            for (int k = 0; k < M_SUMS; ++k) red[k * M_THREADS + tid] += red[k * M_THREADS + tid + h];
-        }
-        __syncthreads();
-    }
+    PS_BLOCK_TREE_SUM(red, tid, M_SUMS, M_THREADS);
     if (tid < M_SUMS) ws[((long long)img * gridDim.x + tile) * M_SUMS + tid] = red[tid * M_THREADS];
 }
 
@@ -184,24 +170,18 @@ size_t ps_image_metrics_workspace_bytes(int B, int C, int H, int W)
 int ps_image_metrics(const void *img1, const int64_t *strides1, const void *img2, const int64_t *strides2, int dtype, const float *mask,
                      int B, int C, int H, int W, float *out, void *workspace, size_t workspace_bytes, void *stream)
 {
-    PS_REQUIRE(img1 && img2 && strides1 && strides2 && out, "image_metrics: null pointer");
-    PS_REQUIRE(dtype == PS_DTYPE_F32 || dtype == PS_DTYPE_U8, "image_metrics: dtype must be PS_DTYPE_F32 or PS_DTYPE_U8 (got %d)", dtype);
-    PS_REQUIRE(B >= 1 && B <= 65535, "image_metrics: 1 <= B <= 65535 required (B = %d)", B);
+    PS_REQUIRE_IMAGES("image_metrics", img1 && img2 && strides1 && strides2 && out, dtype, B, strides1, strides2);
     PS_REQUIRE(C == 1 || C == 3, "image_metrics: C must be 1 or 3 (got %d)", C);
     PS_REQUIRE(H >= 1 && W >= 1, "image_metrics: H, W >= 1 required (H = %d, W = %d)", H, W);
-    for (int i = 0; i < 4; ++i)
-        PS_REQUIRE(strides1[i] >= 0 && strides2[i] >= 0, "image_metrics: negative stride");
     const size_t need = ps_image_metrics_workspace_bytes(B, C, H, W);
     PS_REQUIRE(workspace && workspace_bytes >= need, "image_metrics: workspace of %zu bytes required (got %zu)", need, workspace_bytes);
-    const Img a{img1, strides1[0], strides1[1], strides1[2], strides1[3]};
-    const Img b{img2, strides2[0], strides2[1], strides2[2], strides2[3]};
+    const Img a(img1, strides1), b(img2, strides2);
     const int tiles_x = (W + MT - 1) / MT, tiles = tiles_of(H, W);
     double *ws = (double *)workspace;
-    if (dtype == PS_DTYPE_F32)
-        hipLaunchKernelGGL(k_metrics_tiles<float>, dim3(tiles, B), dim3(M_THREADS), 0, (hipStream_t)stream, a, b, mask, C, H, W, tiles_x, ws);
-    else
-        hipLaunchKernelGGL(k_metrics_tiles<uint8_t>, dim3(tiles, B), dim3(M_THREADS), 0, (hipStream_t)stream, a, b, mask, C, H, W, tiles_x,
-                           ws);
+    ps::for_dtype(dtype, [&](auto t) {
+        hipLaunchKernelGGL(k_metrics_tiles<decltype(t)>, dim3(tiles, B), dim3(M_THREADS), 0, (hipStream_t)stream, a, b, mask, C, H, W,
+                           tiles_x, ws);
+    });
     PS_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_metrics_finish, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, (const double *)ws, B, tiles, C, H, W,
                        mask != nullptr, out);

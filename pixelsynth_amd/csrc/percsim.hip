@@ -17,7 +17,7 @@
 //                     the sum of the five.  A pair's numbers depend neither on its place in the batch nor on the batch's size.
 //
 // Workspace: [layer][pair][tile] doubles, tiles_l = (H_l / 2)(W_l / 2) / 16, H_l = H >> l.
-#include "ps_common.h"
+#include "ps_image.h"
 #include "../../include/pixelsynth_percsim.h"
 
 #include <cmath>
@@ -30,21 +30,11 @@ constexpr int P_LAYERS = 5;              // relu1_2 .. relu5_3
 
 enum { MODE_PLAIN = 0, MODE_VIS = 1, MODE_INVIS = 2, MODE_RAW = 3 };
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-struct Img {
-    const void *p;
-    long long sB, sC, sH, sW;            // element strides
-};
-
-template <typename T> __device__ __forceinline__ float to_unit(T v);
-template <> __device__ __forceinline__ float to_unit<float>(float v) { return v; }
-// true division, as TF.to_tensor's float().div(255) on the host (not a multiply by the reciprocal)
-template <> __device__ __forceinline__ float to_unit<uint8_t>(uint8_t v) { return (float)v / 255.0f; }
-
-// PNet's shift / scale (pretrained_networks.py:45-46) as the fp32 values torch.Tensor([...]) holds
-__constant__ float c_shift[3] = {-0.030f, -0.088f, -0.188f};
-__constant__ float c_scale[3] = {0.458f, 0.448f, 0.450f};
+using ps::c_pnet_scale;
+using ps::c_pnet_shift;
+using ps::f32x4;
+using ps::Img;
+using ps::to_unit;
 
 template <typename T>
 __global__ __launch_bounds__(256) void k_percsim_input(Img a, Img b, const float *__restrict__ mask, int mode, int H, int W,
@@ -68,7 +58,7 @@ __global__ __launch_bounds__(256) void k_percsim_input(Img a, Img b, const float
                 if (mode != MODE_PLAIN) t = t * m;
                 t = t * 2.0f - 1.0f;                     // evaluation/metrics.py:27-31 (the unit is built without FP contraction)
             }
-            o[c] = (t - c_shift[c]) / c_scale[c];
+            o[c] = (t - c_pnet_shift[c]) / c_pnet_scale[c];
         }
         dst[(long long)img * H * W + pix] = o;
     };
@@ -165,11 +155,7 @@ __global__ __launch_bounds__(64) void k_percsim_finish(const double *__restrict_
         double s = 0.0;
         for (int i = l; i < tiles; i += 64) s += t[i];
         red[l] = s;
-        __syncthreads();
-        for (int h = 32; h > 0; h >>= 1) {
-            if (l < h) red[l] += red[l + h];
-            __syncthreads();
-        }
+        PS_BLOCK_TREE_SUM(red, l, 1, 64);
         const double score = 1.0 - red[0] / ((double)Hl * Wl);
         __syncthreads();                                  // before the next layer overwrites red
         if (l == 0) layers[(size_t)pair * P_LAYERS + k] = (float)score;
@@ -194,25 +180,18 @@ size_t ps_percsim_workspace_bytes(int P, int H, int W)
 int ps_percsim_input(const void *img1, const int64_t *strides1, const void *img2, const int64_t *strides2, int dtype, const float *mask,
                      int mode, int B, int H, int W, float *out0, float *out1, void *stream)
 {
-    PS_REQUIRE(img1 && img2 && strides1 && strides2 && out0 && out1, "percsim_input: null pointer");
-    PS_REQUIRE(dtype == PS_DTYPE_F32 || dtype == PS_DTYPE_U8, "percsim_input: dtype must be PS_DTYPE_F32 or PS_DTYPE_U8 (got %d)", dtype);
+    PS_REQUIRE_IMAGES("percsim_input", img1 && img2 && strides1 && strides2 && out0 && out1, dtype, B, strides1, strides2);
     PS_REQUIRE(mode >= MODE_PLAIN && mode <= MODE_RAW, "percsim_input: mode %d", mode);
     PS_REQUIRE(mode != MODE_RAW || (dtype == PS_DTYPE_F32 && !mask), "percsim_input: PS_PERCSIM_RAW takes fp32 images and no mask");
     PS_REQUIRE((mode == MODE_VIS || mode == MODE_INVIS) == (mask != nullptr), "percsim_input: a mask goes with PS_PERCSIM_VIS / _INVIS");
-    PS_REQUIRE(B >= 1 && B <= 65535, "percsim_input: 1 <= B <= 65535 required (B = %d)", B);
     PS_REQUIRE(H >= 1 && W >= 1 && (size_t)H * W < ((size_t)1 << 31), "percsim_input: H = %d, W = %d", H, W);
     PS_REQUIRE((((uintptr_t)out0 | (uintptr_t)out1) & 15) == 0, "percsim_input: out0 / out1 must be 16-byte aligned");
-    for (int i = 0; i < 4; ++i)
-        PS_REQUIRE(strides1[i] >= 0 && strides2[i] >= 0, "percsim_input: negative stride");
-    const Img a{img1, strides1[0], strides1[1], strides1[2], strides1[3]};
-    const Img b{img2, strides2[0], strides2[1], strides2[2], strides2[3]};
+    const Img a(img1, strides1), b(img2, strides2);
     const dim3 grid((unsigned)(((size_t)H * W + 255) / 256), B);
-    if (dtype == PS_DTYPE_F32)
-        hipLaunchKernelGGL(k_percsim_input<float>, grid, dim3(256), 0, (hipStream_t)stream, a, b, mask, mode, H, W, (f32x4 *)out0,
+    ps::for_dtype(dtype, [&](auto t) {
+        hipLaunchKernelGGL(k_percsim_input<decltype(t)>, grid, dim3(256), 0, (hipStream_t)stream, a, b, mask, mode, H, W, (f32x4 *)out0,
                            (f32x4 *)out1);
-    else
-        hipLaunchKernelGGL(k_percsim_input<uint8_t>, grid, dim3(256), 0, (hipStream_t)stream, a, b, mask, mode, H, W, (f32x4 *)out0,
-                           (f32x4 *)out1);
+    });
     PS_LAUNCH_CHECK();
     return PS_OK;
 }

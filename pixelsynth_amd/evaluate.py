@@ -96,52 +96,59 @@ def _decode(item):
     return pred, gt, mask
 
 
+def _pinned(arrays):
+    return torch.from_numpy(np.stack(arrays)).pin_memory()
+
+
 def _stage(decoded):
     """decoded images of one batch -> pinned host tensors (pred, gt (B, H, W, 3) u8; mask (B, 1, H, W) f32 or None)"""
     shapes = {d[0].shape for d in decoded}
     if len(shapes) != 1:
         raise ValueError(f"images of one batch differ in size: {sorted(shapes)} (use --batch 1)")
-    pred = torch.from_numpy(np.stack([d[0] for d in decoded])).pin_memory()
-    gt = torch.from_numpy(np.stack([d[1] for d in decoded])).pin_memory()
-    mask = None
-    if decoded[0][2] is not None:
-        mask = torch.from_numpy(np.stack([d[2] for d in decoded])[:, None]).pin_memory()
-    return pred, gt, mask
+    mask = None if decoded[0][2] is None else _pinned([d[2][None] for d in decoded])
+    return _pinned([d[0] for d in decoded]), _pinned([d[1] for d in decoded]), mask
+
+
+def _score_batches(items, batch, pool, decode, score, width):
+    """The loop of both modes: `decode` runs on the host pool one batch of items ahead of the device; score(items of the batch, what
+    decode gave for each) stages them pinned, uploads and scores them -> a (len, width) device tensor, read back with the batch's one
+    synchronisation.  -> (len(items), width) float64 rows, in order"""
+    own = pool is None
+    pool = pool or ThreadPoolExecutor(max_workers=_threads())
+    try:
+        chunks = [items[i:i + batch] for i in range(0, len(items), batch)]
+        submit = lambda ch: [pool.submit(decode, it) for it in ch]
+        rows = []
+        pending = submit(chunks[0]) if chunks else None
+        for k, chunk in enumerate(chunks):
+            decoded = [f.result() for f in pending]
+            pending = submit(chunks[k + 1]) if k + 1 < len(chunks) else None     # decodes while the device scores this batch
+            rows.append(score(chunk, decoded).cpu().double().numpy())            # the batch's one synchronisation
+        return np.concatenate(rows) if rows else np.zeros((0, width))
+    finally:
+        if own:
+            pool.shutdown()
 
 
 def score_files(items, device, batch=64, pool=None, pnet=None, inception=None):
     """-> (len(items), 6) float64 numpy rows (COLUMNS) of the (pred, gt, sampled) triples, in order; with a PNet `pnet`
     (len(items), 9) rows (ALL_COLUMNS).  With a FIDInception `inception`: -> (those rows, (len(items), 2 * 2048) float64 feature rows,
     the --pred image's features then the --gt image's)."""
-    own = pool is None
-    pool = pool or ThreadPoolExecutor(max_workers=_threads())
-    try:
-        chunks = [items[i:i + batch] for i in range(0, len(items), batch)]
-        submit = lambda ch: [pool.submit(_decode, it) for it in ch]
-        rows, feats = [], []
-        pending = submit(chunks[0]) if chunks else None
-        for k in range(len(chunks)):
-            host = _stage([f.result() for f in pending])
-            pending = submit(chunks[k + 1]) if k + 1 < len(chunks) else None     # decodes while the device scores this batch
-            pred, gt, mask = (None if t is None else t.to(device, non_blocking=True) for t in host)
-            # (B, H, W, 3) storage read as (B, 3, H, W) through its strides: no copy
-            out = image_metrics(gt.permute(0, 3, 1, 2), pred.permute(0, 3, 1, 2), mask)
-            if pnet is not None:
-                out = torch.cat([out, perceptual_rows(pnet, gt.permute(0, 3, 1, 2), pred.permute(0, 3, 1, 2), mask)], 1)
-            if inception is not None:
-                both = FID.inception_features(inception, torch.cat([pred, gt]).permute(0, 3, 1, 2))
-                out = torch.cat([out, both[:len(pred)], both[len(pred):]], 1)
-            out = out.cpu().double().numpy()                                      # the batch's one synchronisation
-            rows.append(out[:, :out.shape[1] - (0 if inception is None else 2 * FID.I.DIMS)])
-            feats.append(out[:, rows[-1].shape[1]:])
-        k = 6 if pnet is None else len(ALL_COLUMNS)
-        rows = np.concatenate(rows) if rows else np.zeros((0, k))
-        if inception is None:
-            return rows
-        return rows, (np.concatenate(feats) if feats else np.zeros((0, 2 * FID.I.DIMS)))
-    finally:
-        if own:
-            pool.shutdown()
+    def score(_, decoded):
+        pred, gt, mask = (None if t is None else t.to(device, non_blocking=True) for t in _stage(decoded))
+        # (B, H, W, 3) storage read as (B, 3, H, W) through its strides: no copy
+        out = image_metrics(gt.permute(0, 3, 1, 2), pred.permute(0, 3, 1, 2), mask)
+        if pnet is not None:
+            out = torch.cat([out, perceptual_rows(pnet, gt.permute(0, 3, 1, 2), pred.permute(0, 3, 1, 2), mask)], 1)
+        if inception is not None:
+            both = FID.inception_features(inception, torch.cat([pred, gt]).permute(0, 3, 1, 2))
+            out = torch.cat([out, both[:len(pred)], both[len(pred):]], 1)
+        return out
+    k = 6 if pnet is None else len(ALL_COLUMNS)
+    out = _score_batches(items, batch, pool, _decode, score, k + (0 if inception is None else 2 * FID.I.DIMS))
+    if inception is None:
+        return out
+    return np.ascontiguousarray(out[:, :k]), np.ascontiguousarray(out[:, k:])
 
 
 def summarize(rows, masked, percsim=False):
@@ -199,40 +206,60 @@ def main(argv=None):
     if args.consistency is not None:
         return _consistency_main(args)
 
+    masked = args.sampled is not None
+
+    def items():
+        found = discover(args.pred, args.gt, args.sampled, args.max_img)
+        if args.inception is not None and len(found) < 2:
+            raise SystemExit(f"--inception: FID needs two images at least, found {len(found)}")
+        return found
+
+    def score(mine, device, pnet):
+        net = None
+        if args.inception is not None:
+            from .networks.inception import FIDInception
+            net = FIDInception(weights=args.inception, use_gpu=True)
+        local = score_files(mine, device, args.batch, pnet=pnet, inception=net)
+        # the feature rows travel with the metric rows: float64 blocks, fp32 features pass unchanged
+        return local if net is None else np.concatenate(local, 1)
+
+    def means_of(rows, percsim):
+        means = summarize(rows, masked, percsim)
+        if args.inception is not None:
+            feats = rows[:, -2 * FID.I.DIMS:]
+            means["FID"] = FID.fid_of_rows(feats[:, :FID.I.DIMS], feats[:, FID.I.DIMS:])
+        return means
+
+    def columns(percsim):
+        cols = COLUMNS if masked else ("psnr", "ssim")
+        if percsim:
+            cols = cols + (PERCSIM_COLUMNS if masked else ("percsim",))
+        return [(c, ALL_COLUMNS.index(c)) for c in cols]
+    return _run(args, ("pred", "gt", "sampled"), items, score, means_of, columns)
+
+
+def _run(args, named, discover_items, score, means_of, columns):
+    """What both modes do around their scoring: set up, deal the items over the ranks, score this rank's (score(items, device, pnet)
+    -> (len, k) rows), gather every rank's rows in item order and, on rank 0, print means_of(rows, percsim) and write --json: n, the
+    arguments `named`, the means and per item the columns(percsim) = [(name, column of rows)]."""
     rank, world, device = _setup()
     try:
-        items = discover(args.pred, args.gt, args.sampled, args.max_img)
+        items = discover_items()
         n = len(items)
-        if args.inception is not None and n < 2:
-            raise SystemExit(f"--inception: FID needs two images at least, found {n}")
         mine = D.shard_views(n, rank, world)
         pnet = None
         if args.vgg16 is not None:
             from .networks.pretrained_networks import PNet
             pnet = PNet(use_gpu=True, weights=args.vgg16)
-        net = None
-        if args.inception is not None:
-            from .networks.inception import FIDInception
-            net = FIDInception(weights=args.inception, use_gpu=True)
-        local_rows = score_files([items[i] for i in mine], device, args.batch, pnet=pnet, inception=net)
-        if net is not None:      # the feature rows travel with the metric rows: float64 blocks, fp32 features pass unchanged
-            local_rows = np.concatenate(local_rows, 1)
-        rows = D.gather_rows(local_rows.T, n).T                                    # (n, 6) -- 9 with --vgg16 --, image order
-        masked = args.sampled is not None
-        means = summarize(rows, masked, pnet is not None)
-        if net is not None and rank == 0:
-            feats = rows[:, -2 * FID.I.DIMS:]
-            means["FID"] = FID.fid_of_rows(feats[:, :FID.I.DIMS], feats[:, FID.I.DIMS:])
+        rows = D.gather_rows(score([items[i] for i in mine], device, pnet).T, n).T          # (n, k), item order
         if rank == 0:
+            means = means_of(rows, pnet is not None)
             for name, v in means.items():
                 print("%s \t %0.5f" % (name, v))
             if args.json:
-                cols = COLUMNS if masked else ("psnr", "ssim")
-                if pnet is not None:
-                    cols = cols + (PERCSIM_COLUMNS if masked else ("percsim",))
-                doc = {"n": n, "pred": args.pred, "gt": args.gt, "sampled": args.sampled, "psnr_clamp": PSNR_CLAMP, "means": means,
-                       **({"fid": means["FID"]} if net is not None else {}),
-                       "rows": [dict(index=i, **{c: float(rows[i, ALL_COLUMNS.index(c)]) for c in cols}) for i in range(n)]}
+                doc = {"n": n, **{k: getattr(args, k) for k in named}, "psnr_clamp": PSNR_CLAMP, "means": means,
+                       **({"fid": means["FID"]} if "FID" in means else {}),
+                       "rows": [dict(index=i, **{c: float(rows[i, j]) for c, j in columns(pnet is not None)}) for i in range(n)]}
                 with open(args.json, "w") as fh:
                     json.dump(doc, fh, indent=1)
     finally:
@@ -315,27 +342,11 @@ def _decode_item(item):
 
 def consistency_files(items, device, batch=64, pool=None, pnet=None):
     """-> (len(items), 3) float64 rows (consistency.COLUMNS[:3]), or (len(items), 6) with a PNet, in order"""
-    own = pool is None
-    pool = pool or ThreadPoolExecutor(max_workers=_threads())
-    k = 3 if pnet is None else 6
-    try:
-        chunks = [items[i:i + batch] for i in range(0, len(items), batch)]
-        submit = lambda ch: [pool.submit(_decode_item, it) for it in ch]
-        rows = []
-        pending = submit(chunks[0]) if chunks else None
-        for c in range(len(chunks)):
-            dec = [f.result() for f in pending]
-            pending = submit(chunks[c + 1]) if c + 1 < len(chunks) else None     # decodes while the device scores this batch
-            labels = [it[0] for it in chunks[c]]
-            H12, H21 = CS.fit_points([d[4] for d in dec], [d[5] for d in dec], labels)
-            host = [torch.from_numpy(np.stack([d[j] for d in dec])).pin_memory() for j in range(4)]
-            v1, v2, m1, m2 = (t.to(device, non_blocking=True) for t in host)
-            out = CS.consistency_rows(v1.permute(0, 3, 1, 2), v2.permute(0, 3, 1, 2), m1[:, None], m2[:, None], H12, H21, pnet=pnet)
-            rows.append(out.cpu().double().numpy())                               # the batch's one synchronisation
-        return np.concatenate(rows) if rows else np.zeros((0, k))
-    finally:
-        if own:
-            pool.shutdown()
+    def score(chunk, dec):
+        H12, H21 = CS.fit_points([d[4] for d in dec], [d[5] for d in dec], [it[0] for it in chunk])
+        v1, v2, m1, m2 = (_pinned([d[j] for d in dec]).to(device, non_blocking=True) for j in range(4))
+        return CS.consistency_rows(v1.permute(0, 3, 1, 2), v2.permute(0, 3, 1, 2), m1[:, None], m2[:, None], H12, H21, pnet=pnet)
+    return _score_batches(items, batch, pool, _decode_item, score, 3 if pnet is None else 6)
 
 
 def consistency_summarize(rows, percsim=False):
@@ -350,33 +361,11 @@ def consistency_summarize(rows, percsim=False):
 
 
 def _consistency_main(args):
-    rank, world, device = _setup()
-    try:
-        items = consistency_discover(args.consistency, args.masks, args.points, args.directions, args.max_img)
-        n = len(items)
-        mine = D.shard_views(n, rank, world)
-        pnet = None
-        if args.vgg16 is not None:
-            from .networks.pretrained_networks import PNet
-            pnet = PNet(use_gpu=True, weights=args.vgg16)
-        local_rows = consistency_files([items[i] for i in mine], device, args.batch, pnet=pnet)
-        k = 3 if pnet is None else 6
-        rows = D.gather_rows(local_rows.reshape(-1, k).T, n).T                     # (n, k), item order
-        means = consistency_summarize(rows, pnet is not None)
-        if rank == 0:
-            for name, v in means.items():
-                print("%s \t %0.5f" % (name, v))
-            if args.json:
-                cols = CS.COLUMNS[:k]
-                doc = {"n": n, "consistency": args.consistency, "masks": args.masks, "points": args.points,
-                       "directions": args.directions, "psnr_clamp": PSNR_CLAMP, "means": means,
-                       "rows": [dict(index=i, **{c: float(rows[i, j]) for j, c in enumerate(cols)}) for i in range(n)]}
-                with open(args.json, "w") as fh:
-                    json.dump(doc, fh, indent=1)
-    finally:
-        if world > 1:
-            torch.distributed.destroy_process_group()
-    return 0
+    k = 3 if args.vgg16 is None else 6
+    return _run(args, ("consistency", "masks", "points", "directions"),
+                lambda: consistency_discover(args.consistency, args.masks, args.points, args.directions, args.max_img),
+                lambda mine, device, pnet: consistency_files(mine, device, args.batch, pnet=pnet).reshape(-1, k),
+                consistency_summarize, lambda percsim: [(c, j) for j, c in enumerate(CS.COLUMNS[:k])])
 
 
 if __name__ == "__main__":

@@ -17,15 +17,12 @@ dropping a small imaginary part); here the trace is the sum of the square roots 
 -- two symmetric eigh in fp64, negative eigenvalues clamped at 0, the second restricted to the range of sigma1 --, the same number where
 sqrtm is well defined and defined where it is not (fewer rows than dimensions make both covariances singular).  Torch fp64 calls on the device the statistics are on: a few
 GFLOP once per run."""
-import ctypes
-
 import numpy as np
 import torch
 
-from . import _lib
+from . import _images, _lib
 from .networks import inception as I
 
-_DTYPES = {torch.float32: 0, torch.uint8: 1}             # PS_DTYPE_F32, PS_DTYPE_U8
 MAX_S2, MAX_S1, AVG_S1, MEAN = 0, 1, 2, 3                 # PS_FID_*
 _POOL_MODES = {"max2": MAX_S2, "max1": MAX_S1, "avg": AVG_S1}
 _PASS_BYTES = 1 << 30
@@ -110,7 +107,7 @@ def input_pass(imgs):
     """imgs (B, 3, H, W) float32 in [0, 1] or uint8, any strides -> (B, 299, 299, 4): resized, 2 x - 1, channel 3 zero"""
     B, _, H, W = imgs.shape
     out = torch.empty((B, I.SIZE, I.SIZE, 4), dtype=torch.float32, device=imgs.device)
-    _lib.call("ps_fid_input", imgs, (ctypes.c_int64 * 4)(*imgs.stride()), _DTYPES[imgs.dtype], B, H, W, out)
+    _lib.call("ps_fid_input", imgs, _images.strides(imgs), _images.DTYPES[imgs.dtype], B, H, W, out)
     return out
 
 
@@ -152,35 +149,18 @@ def _network(layers, x):
     return pool(x, MEAN).view(N, -1)
 
 
-def _check(net, imgs):
+def inception_features(net, imgs):
     if not hasattr(net, "hip_layers") or not hasattr(net, "torch_forward"):
         raise TypeError("net must be a networks.inception.FIDInception")
-    if not torch.is_tensor(imgs):
-        raise TypeError("imgs must be a tensor")
-    if imgs.dim() != 4:
-        raise ValueError(f"imgs must be (B, 3, H, W), got shape {tuple(imgs.shape)}")
-    B, C, H, W = imgs.shape
-    if C != 3:
-        raise ValueError(f"C must be 3, got {C}")
-    if B < 1 or H < 1 or W < 1:
-        raise ValueError(f"empty image batch {tuple(imgs.shape)}")
-    if imgs.dtype not in _DTYPES:
-        raise TypeError(f"imgs must be float32 or uint8, got {imgs.dtype}")
-    _lib.require_cuda(imgs)
-    dev = next(net.parameters()).device
-    if dev != imgs.device:
-        raise ValueError(f"imgs are on {imgs.device}, the network on {dev}")
-
-
-def inception_features(net, imgs):
-    _check(net, imgs)
-    B, dev = imgs.size(0), imgs.device
+    B = _images.check_images({"imgs": imgs}, (3,), "(B, 3, H, W)")[0]
+    dev = _images.same_device(imgs=imgs)
+    if next(net.parameters()).device != dev:
+        raise ValueError(f"imgs are on {dev}, the network on {next(net.parameters()).device}")
     with torch.no_grad(), torch.cuda.device(dev):
         layers = net.hip_layers(dev)
-        per = images_per_pass()
         rows = []
-        for b0 in range(0, B, per):
-            part = imgs[b0:b0 + per]
+        for b0, b1 in _images.batches(B, images_per_pass()):
+            part = imgs[b0:b1]
             if layers is None:
                 rows.append(net.torch_forward(part.float() / 255.0 if part.dtype == torch.uint8 else part))
             else:

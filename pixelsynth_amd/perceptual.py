@@ -13,15 +13,12 @@ ps_percsim_tap on the layer's pre-ReLU output -- the cosine partial sums and, fo
 whose convolutions apply the ReLU on the way in -- and ps_percsim_finish.  Passes are cut so that one activation map stays near 1 GiB;
 a pass is a guarded scope (networks.f16x3.checked).
 """
-import ctypes
-
 import torch
 
-from . import _lib
+from . import _images, _lib
 from .networks import f16x3
 
 COLUMNS = ("percsim", "percsim_vis", "percsim_invis")
-_DTYPES = {torch.float32: 0, torch.uint8: 1}             # PS_DTYPE_F32, PS_DTYPE_U8
 PLAIN, VIS, INVIS, RAW = 0, 1, 2, 3                       # PS_PERCSIM_*
 _LEVELS = ((0, 1), (2, 3), (4, 5, 6), (7, 8, 9), (10, 11, 12))    # the convolutions before each tap
 _MAP_BYTES = 1 << 30                                      # one activation map of a pass at most (the 64-channel maps at full size)
@@ -35,14 +32,14 @@ def _nhwc(N, C, H, W, dev):
     return torch.empty((N, C, H, W), dtype=torch.float32, device=dev, memory_format=torch.channels_last)
 
 
-def _network(layers, x, P, H, W):
-    """The pass over x (2P, 4, H, W) channels_last (the input pass's output) -> (layers (P, 5), total (P)) f32."""
+def network_pass(layers, x, P, H, W):
+    """The pass over x (2P, 4, H, W) channels_last (the input pass's output, or consistency.py's) with pnet.hip_layers `layers`
+    -> (layers (P, 5), total (P)) f32.  At most pairs_per_pass(H, W) pairs; inside the caller's guarded scope."""
     dev, N = x.device, 2 * P
     ones = torch.ones(N * 512, dtype=torch.float32, device=dev)
     zeros = torch.zeros(N * 512, dtype=torch.float32, device=dev)
     relu = lambda C: (ones[:N * C].view(N, C), zeros[:N * C].view(N, C))     # act(x) = max(x * 1 - 0, 0)
-    nbytes = _lib.call("ps_percsim_workspace_bytes", P, H, W)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    ws, nbytes = _images.workspace("ps_percsim_workspace_bytes", P, H, W, device=dev)
     h = None
     for level, convs in enumerate(_LEVELS):
         for i in convs:
@@ -64,10 +61,6 @@ def _network(layers, x, P, H, W):
     return per_layer, total
 
 
-def _strides(t):
-    return (ctypes.c_int64 * 4)(*t.stride())
-
-
 def _passes(pnet, img1, img2, mask, modes):
     """Network passes over the pairs (img1, img2) in each mode of `modes` (one row block per mode) -> (total (len(modes), B),
     layers (len(modes), B, 5)), on the HIP path.  Inside the caller's guarded scope."""
@@ -78,16 +71,15 @@ def _passes(pnet, img1, img2, mask, modes):
     per = max(1, pairs_per_pass(H, W) // V)
     total = torch.empty(V, B, dtype=torch.float32, device=dev)
     per_layer = torch.empty(V, B, 5, dtype=torch.float32, device=dev)
-    for b0 in range(0, B, per):
-        b1 = min(B, b0 + per)
+    for b0, b1 in _images.batches(B, per):
         n, P = b1 - b0, (b1 - b0) * V
         x = torch.empty((2 * P, H, W, 4), dtype=torch.float32, device=dev)
         a, b = img1[b0:b1], img2[b0:b1]
         m = None if mask is None else mask[b0:b1]
         for v, mode in enumerate(modes):
-            _lib.call("ps_percsim_input", a, _strides(a), b, _strides(b), _DTYPES[img1.dtype], m if mode in (VIS, INVIS) else None,
-                      mode, n, H, W, x[v * n:(v + 1) * n], x[P + v * n:P + (v + 1) * n])
-        pl, tot = _network(layers, x.permute(0, 3, 1, 2), P, H, W)
+            _lib.call("ps_percsim_input", a, _images.strides(a), b, _images.strides(b), _images.DTYPES[img1.dtype],
+                      m if mode in (VIS, INVIS) else None, mode, n, H, W, x[v * n:(v + 1) * n], x[P + v * n:P + (v + 1) * n])
+        pl, tot = network_pass(layers, x.permute(0, 3, 1, 2), P, H, W)
         total[:, b0:b1] = tot.view(V, n)
         per_layer[:, b0:b1] = pl.view(V, n, 5)
     return total, per_layer
@@ -106,32 +98,9 @@ def pnet_pairs(pnet, in0, in1):
     return f16x3.checked(in0.device, run)
 
 
-def _check(pnet, img1, img2, mask):
+def check_pnet(pnet):
     if not hasattr(pnet, "hip_takes") or not hasattr(pnet, "torch_forward"):
         raise TypeError("pnet must be a networks.pretrained_networks.PNet")
-    for name, t in (("img1", img1), ("img2", img2)):
-        if not torch.is_tensor(t):
-            raise TypeError(f"{name} must be a tensor")
-        if t.dim() != 4:
-            raise ValueError(f"{name} must be (B, 3, H, W), got shape {tuple(t.shape)}")
-    if img1.shape != img2.shape:
-        raise ValueError(f"img1 and img2 differ in shape: {tuple(img1.shape)} vs {tuple(img2.shape)}")
-    B, C, H, W = img1.shape
-    if C != 3:
-        raise ValueError(f"C must be 3, got {C}")
-    if B < 1 or H < 1 or W < 1:
-        raise ValueError(f"empty image batch {tuple(img1.shape)}")
-    if img1.dtype != img2.dtype or img1.dtype not in _DTYPES:
-        raise TypeError(f"img1 and img2 must both be float32 or both uint8, got {img1.dtype} and {img2.dtype}")
-    if mask is not None:
-        if not torch.is_tensor(mask) or tuple(mask.shape) != (B, 1, H, W):
-            raise ValueError(f"mask must be (B, 1, H, W) = {(B, 1, H, W)}, got {tuple(getattr(mask, 'shape', ()))}")
-        if not (mask.dtype.is_floating_point or mask.dtype == torch.bool):
-            raise TypeError(f"mask must be floating point or bool, got {mask.dtype}")
-    _lib.require_cuda(img1, img2, mask)
-    devs = {t.device for t in (img1, img2, mask) if t is not None}
-    if len(devs) != 1:
-        raise ValueError(f"img1, img2 and mask must be on one device, got {sorted(map(str, devs))}")
 
 
 def _torch_rows(pnet, img1, img2, mask):
@@ -146,9 +115,11 @@ def _torch_rows(pnet, img1, img2, mask):
 
 
 def perceptual_rows(pnet, img1, img2, mask=None):
-    _check(pnet, img1, img2, mask)
-    B, _, H, W = img1.shape
-    dev = img1.device
+    check_pnet(pnet)
+    B, _, H, W = _images.check_images({"img1": img1, "img2": img2}, (3,), "(B, 3, H, W)")
+    if mask is not None:
+        _images.check_mask("mask", mask, (B, 1, H, W), _images.FLOAT_OR_BOOL)
+    dev = _images.same_device(img1=img1, img2=img2, mask=mask)
     if mask is not None:
         mask = mask.to(torch.float32).contiguous()
     probe = torch.empty((1, 3, H, W), dtype=torch.float32, device=dev)   # what the HIP path takes (no data is read)

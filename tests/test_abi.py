@@ -7,16 +7,11 @@ import re
 import numpy as np
 import pytest
 
+from abi_util import assert_library_matches_header, ends_in_stream, header_symbols
 from oracle import c_oracle
-from pixelsynth_amd import _lib, synthetic as syn
+from pixelsynth_amd import _lib, _libraries, synthetic as syn
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def header_symbols(name="pixelsynth_hip.h"):
-    txt = open(os.path.join(ROOT, "include", name)).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return sorted(set(re.findall(r"\b(ps_[a-z0-9_]+)\s*\(", txt)))
 
 
 DEBUG_ONLY = {"ps_pixelcnn_set_tuning", "ps_pixelcnn_get_tuning", "ps_pixelcnn_time_ar_run_waves", "ps_pixelcnn_time_ar_run_waves_range", "ps_pixelcnn_time_column_step",
@@ -33,10 +28,7 @@ def test_library_exports_every_declared_symbol():
     assert set(debug) == DEBUG_ONLY and not set(names) & DEBUG_ONLY, "measurement / tuning entry points belong in pixelsynth_hip_debug.h"
     assert set(_lib.exported_symbols()) == set(names) | set(debug), "python prototypes out of sync with the headers"
     # ... and nothing else of the ps_ namespace leaves the library
-    import subprocess
-    out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True).stdout
-    exported = {ln.split()[-1] for ln in out.splitlines() if ln.split() and ln.split()[-1].startswith("ps_")}
-    assert exported == set(names) | set(debug), exported ^ (set(names) | set(debug))
+    assert set(assert_library_matches_header("hip")) == set(names) | set(debug)
     assert L.ps_abi_version() == 2
     # the library says what it was built from: the in-tree one is a product build (no tuning / trace / experiment macro)
     info = L.ps_build_info().decode()
@@ -52,28 +44,32 @@ def test_error_channel():
     assert L.ps_splat_workspace_bytes(1, 65536, 256, 4.0) > 65536 * 8
 
 
-def header_prototypes():
-    """{name: [parameter text]} of every prototype of the two headers (comments stripped)."""
-    protos = {}
-    for name in ("pixelsynth_hip.h", "pixelsynth_hip_debug.h"):
-        txt = open(os.path.join(ROOT, "include", name)).read()
-        txt = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", txt, flags=re.S))
-        for fn, params in re.findall(r"\b(ps_[a-z0-9_]+)\s*\(([^;{)]*)\)\s*;", txt):
-            protos[fn] = [p.strip() for p in params.split(",")] if params.strip() not in ("", "void") else []
-    return protos
-
-
 def test_bindings_match_the_header_prototypes():
     """Every _PROTOS entry has as many arguments as its prototype, and the entries marked STREAM are exactly the prototypes that end
-    in `void *stream`: the ones call() appends the current stream to."""
-    protos = header_prototypes()
+    in `void *stream`: the ones call() appends the current stream to (abi_util.assert_library_matches_header)."""
+    protos = assert_library_matches_header("hip")
     assert len(protos) == 69 and set(protos) == set(_lib._PROTOS)
-    for name, (_, args) in _lib._PROTOS.items():
-        assert len(args) == len(protos[name]), (name, len(args), protos[name])
-    ends_in_stream = {n for n, p in protos.items() if p and re.fullmatch(r"void\s*\*\s*stream", p[-1])}
-    assert len(ends_in_stream) == 42
-    assert {n for n, (_, args) in _lib._PROTOS.items() if args and args[-1] is _lib.STREAM} == ends_in_stream
-    assert all(a is not _lib.STREAM for _, args in _lib._PROTOS.values() for a in args[:-1])
+    assert len(ends_in_stream(protos)) == 42
+
+
+def test_registry_names_every_library_once():
+    """_libraries.LIBRARIES is what build.py builds and _lib.py loads: every library is there after the build, every entry point
+    belongs to exactly one library, and a failed status is reported through the last-error function of the entry point's own library."""
+    assert [e.name for e in _libraries.LIBRARIES] == list(_lib.PROTOS) and _libraries.LIBRARIES[0] is _libraries.MAIN
+    assert len({e.so for e in _libraries.LIBRARIES}) == len(_libraries.LIBRARIES)
+    names = [fn for table in _lib.PROTOS.values() for fn in table]
+    assert len(names) == len(set(names)) == len(_lib._OWNER)
+    for entry in _libraries.LIBRARIES:
+        assert os.path.isfile(_libraries.path(entry)), entry.so
+        assert all(os.path.isfile(os.path.join(ROOT, "include", h)) for h in entry.headers)
+        assert all(os.path.isfile(os.path.join(ROOT, "pixelsynth_amd", "csrc", u)) for u, _ in entry.units)
+        assert all(_lib._OWNER[fn] is entry for fn in _lib.PROTOS[entry.name])
+        assert _lib.PROTOS[entry.name][entry.last_error] == (ctypes.c_char_p, [])
+        if entry is not _libraries.MAIN:
+            name = next(fn for fn, (res, _) in _lib.PROTOS[entry.name].items() if res is _lib.RC)
+            with pytest.raises(RuntimeError, match=r"^%s failed \(rc=-2\): " % name):
+                _lib.check(-2, name)
+    assert _lib.library("hip") is _lib.lib()
 
 
 def test_call_refuses_host_tensors_before_touching_a_stream():

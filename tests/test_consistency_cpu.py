@@ -3,16 +3,14 @@ point conversion and two separate fits, the golden file against the fp64 restate
 CLI's discovery and argument checks, before any device is touched."""
 import json
 import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
+from abi_util import assert_library_matches_header
 import consistency_ref64 as R
 from pixelsynth_amd import _lib, consistency as C, evaluate
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _known(seed=0, n=30, deg=(3.0, -2.0, 1.0)):
@@ -130,17 +128,8 @@ def test_golden_file_matches_the_restatement(golden_dir):
 
 
 def test_consistency_library_exports_its_header():
-    txt = open(os.path.join(ROOT, "include", "pixelsynth_consistency.h")).read()
-    txt = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", txt, flags=re.S))
-    protos = {fn: [p.strip() for p in params.split(",")] if params.strip() not in ("", "void") else []
-              for fn, params in re.findall(r"\b(ps_[a-z0-9_]+)\s*\(([^;{)]*)\)\s*;", txt)}
-    assert set(protos) == set(_lib.CONSISTENCY_PROTOS)
-    for name, (_, args) in _lib.CONSISTENCY_PROTOS.items():
-        assert len(args) == len(protos[name]), name
-        assert (bool(args) and args[-1] is _lib.STREAM) == bool(protos[name] and re.fullmatch(r"void\s*\*\s*stream", protos[name][-1]))
-    L = _lib.consistency_lib()
-    out = subprocess.run(["nm", "-D", "--defined-only", _lib.CONSISTENCY_LIB_PATH], capture_output=True, text=True).stdout
-    assert {ln.split()[-1] for ln in out.splitlines() if ln.split() and ln.split()[-1].startswith("ps_")} == set(protos)
+    assert_library_matches_header("consistency")
+    L = _lib.library("consistency")
     assert _lib.call("ps_consistency_workspace_bytes", 3, 256, 256) == 3 * 2 * 256 * 2 * 8
     assert _lib.call("ps_consistency_workspace_bytes", 1, 5, 70) == 2 * 4 * 2 * 8          # tiles of 64 x 4: 2 x 2
     assert _lib.call("ps_consistency_workspace_bytes", 0, 256, 256) == 0

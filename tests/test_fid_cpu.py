@@ -7,17 +7,16 @@ The float bound of the network is 4 x err32, the restatement's own fp32 error ag
 summation order only)."""
 import json
 import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
+from abi_util import assert_library_matches_header
 import fid_ref64 as R
 from pixelsynth_amd import _lib, fid, synthetic as syn
 from pixelsynth_amd.networks import inception as I
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
@@ -218,18 +217,8 @@ def test_cli_inception_argument_errors(tmp_path, capsys):
 
 
 def test_fid_library_exports_its_header():
-    txt = open(os.path.join(ROOT, "include", "pixelsynth_fid.h")).read()
-    txt = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", txt, flags=re.S))
-    protos = {fn: [p.strip() for p in params.split(",")] if params.strip() not in ("", "void") else []
-              for fn, params in re.findall(r"\b(ps_[a-z0-9_]+)\s*\(([^;{)]*)\)\s*;", txt)}
-    assert set(protos) == set(_lib.FID_PROTOS)
-    for name, (_, args) in _lib.FID_PROTOS.items():
-        assert len(args) == len(protos[name]), name
-        assert (bool(args) and args[-1] is _lib.STREAM) == bool(protos[name] and re.fullmatch(r"void\s*\*\s*stream", protos[name][-1]))
-    import subprocess
-    L = _lib.fid_lib()
-    out = subprocess.run(["nm", "-D", "--defined-only", _lib.FID_LIB_PATH], capture_output=True, text=True).stdout
-    assert {ln.split()[-1] for ln in out.splitlines() if ln.split() and ln.split()[-1].startswith("ps_")} == set(protos)
+    assert_library_matches_header("fid")
+    L = _lib.library("fid")
     with pytest.raises(RuntimeError, match="ps_fid_pool failed.*null"):
         _lib.call("ps_fid_pool", None, 4, 0, 1, 8, 8, 4, None, 4, 0, stream=0)
     with pytest.raises(RuntimeError, match="ps_fid_conv failed.*null"):

@@ -9,12 +9,12 @@ import numpy as np
 import pytest
 import torch
 
+from abi_util import assert_library_matches_header
 import percsim_ref64 as R
 from pixelsynth_amd import _lib, synthetic as syn
 from pixelsynth_amd.networks.pretrained_networks import PNet, cos_sim, normalize_tensor
 from pixelsynth_amd.perceptual import perceptual_rows
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MARGIN = 1e-7      # beyond the reference's own recorded fp32 error: a different order of fp32 sums
 
 
@@ -120,18 +120,8 @@ def test_cli_rejects_a_missing_vgg16_file(tmp_path, capsys):
 
 
 def test_percsim_library_exports_its_header():
-    txt = open(os.path.join(ROOT, "include", "pixelsynth_percsim.h")).read()
-    txt = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", txt, flags=re.S))
-    protos = {fn: [p.strip() for p in params.split(",")] if params.strip() not in ("", "void") else []
-              for fn, params in re.findall(r"\b(ps_[a-z0-9_]+)\s*\(([^;{)]*)\)\s*;", txt)}
-    assert set(protos) == set(_lib.PERCSIM_PROTOS)
-    for name, (_, args) in _lib.PERCSIM_PROTOS.items():
-        assert len(args) == len(protos[name]), name
-        assert (bool(args) and args[-1] is _lib.STREAM) == bool(protos[name] and re.fullmatch(r"void\s*\*\s*stream", protos[name][-1]))
-    import subprocess
-    L = _lib.percsim_lib()
-    out = subprocess.run(["nm", "-D", "--defined-only", _lib.PERCSIM_LIB_PATH], capture_output=True, text=True).stdout
-    assert {ln.split()[-1] for ln in out.splitlines() if ln.split() and ln.split()[-1].startswith("ps_")} == set(protos)
+    assert_library_matches_header("percsim")
+    L = _lib.library("percsim")
     assert _lib.call("ps_percsim_workspace_bytes", 2, 256, 256) == 2 * (1024 + 256 + 64 + 16 + 4) * 8
     assert _lib.call("ps_percsim_workspace_bytes", 2, 96, 160) == 0
     with pytest.raises(RuntimeError, match="ps_percsim_finish failed.*null"):

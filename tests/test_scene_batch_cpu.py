@@ -2,16 +2,14 @@
 evaluate --consistency lists, the directions file and flags, the deal of scenes over ranks -- on fake tensors, no device; and the C ABI
 of libpixelsynth_scene.so against its header and bindings."""
 import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+from abi_util import assert_library_matches_header
 from pixelsynth_amd import _lib, driver, evaluate
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 S = 16
 
 
@@ -134,18 +132,8 @@ def test_scenes_are_dealt_over_ranks_without_loss_or_duplication(n, batch, world
 def test_scene_library_exports_what_its_header_declares():
     """include/pixelsynth_scene.h, the exports of libpixelsynth_scene.so and _lib.SCENE_PROTOS name the same entry points with the same
     number of parameters; libpixelsynth_hip.so's ABI is untouched (tests/test_abi.py) and its version stays 2."""
-    txt = open(os.path.join(ROOT, "include", "pixelsynth_scene.h")).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    protos = {fn: ([p for p in params.split(",")] if params.strip() not in ("", "void") else [])
-              for fn, params in re.findall(r"\b(ps_[a-z0-9_]+)\s*\(([^;{)]*)\)\s*;", txt)}
+    protos = assert_library_matches_header("scene")
     assert set(protos) == set(_lib.SCENE_PROTOS) and len(protos) == 4
-    for name, (_, args) in _lib.SCENE_PROTOS.items():
-        assert len(args) == len(protos[name]), name
-        assert (bool(args) and args[-1] is _lib.STREAM) == bool(protos[name] and re.fullmatch(r"void\s*\*\s*stream", protos[name][-1].strip())), name
-    _lib.scene_lib()
-    out = subprocess.run(["nm", "-D", "--defined-only", _lib.SCENE_LIB_PATH], capture_output=True, text=True).stdout
-    exported = {ln.split()[-1] for ln in out.splitlines() if ln.split() and ln.split()[-1].startswith("ps_")}
-    assert exported == set(protos), exported ^ set(protos)
     assert _lib.call("ps_abi_version") == 2
 
 
@@ -156,6 +144,6 @@ def test_scene_size_queries_are_host_arithmetic():
     ws, splat = _lib.call("ps_scene_workspace_bytes", B, cap, S_, 4.0), _lib.call("ps_splat_workspace_bytes", B, cap, S_, 4.0)
     assert splat < ws <= splat + 4 * B * (S_ * S_ // 256 + 1) + 256   # the splat's for clouds of cap points + the compaction's block sums
     # refused on the host before anything is enqueued (no stream is touched: NULL pointers fail first)
-    L = _lib.scene_lib()
+    L = _lib.library("scene")
     assert L.ps_scene_step_f32(*([None] * 13), 1, 3, 16, 256, 0, 256, 4.0, 8, 1.0, 2, 0, 13, None, None, None, 0, None) < 0
     assert b"null pointer" in L.ps_scene_last_error()

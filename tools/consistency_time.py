@@ -94,7 +94,7 @@ def main():
     nbytes = C._lib.call("ps_consistency_workspace_bytes", B, S, S)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     psnr = torch.empty(B, 2, dtype=torch.float32, device=dev)
-    strides = lambda t: C._strides(t)
+    strides = C._images.strides
 
     def kernel():
         C._lib.call("ps_consistency", v1, strides(v1), v2, strides(v2), 1, m1, m2, 1, maps, B, S, S, 0, None, psnr, ws, nbytes)
