@@ -134,8 +134,16 @@ SCENE_PROTOS = {
                                                                 c_void_p, c_size_t, STREAM]),
 }
 
+# libpixelsynth_plan.so (include/pixelsynth_plan.h): the generation orders of an AR plan from background masks on the device
+PLAN_PROTOS = {
+    "ps_plan_last_error": (ctypes.c_char_p, []),
+    "ps_plan_order_takes": (c_int, [c_int, c_int]),
+    "ps_plan_order": (RC, [c_void_p, c_int, c_int, c_int] + [c_void_p] * 4 + [STREAM]),
+}
+
 # short name of _libraries.LIBRARIES -> its prototype table; _OWNER: entry point -> the table entry of its library, built once
-PROTOS = {"hip": _PROTOS, "percsim": PERCSIM_PROTOS, "consistency": CONSISTENCY_PROTOS, "fid": FID_PROTOS, "scene": SCENE_PROTOS}
+PROTOS = {"hip": _PROTOS, "percsim": PERCSIM_PROTOS, "consistency": CONSISTENCY_PROTOS, "fid": FID_PROTOS, "scene": SCENE_PROTOS,
+          "plan": PLAN_PROTOS}
 _ENTRIES = {e.name: e for e in _libraries.LIBRARIES}
 assert set(PROTOS) == set(_ENTRIES)
 _OWNER = {fn: _ENTRIES[name] for name, table in PROTOS.items() for fn in table}

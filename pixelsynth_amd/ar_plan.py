@@ -82,12 +82,46 @@ class ARPlan:
                 if t is not None]
 
 
-def build_ar_plan(background_mask, G=32, device=None, count_background=False):
+PLAN_ORDER_ROUTES = ("host", "device")
+
+
+def _order_route(order_on):
+    """order_on of build_ar_plan -> "host" / "device"; None: the environment variable PS_PLAN_ORDER (read per call), host by default"""
+    route = os.environ.get("PS_PLAN_ORDER", "host") if order_on is None else order_on
+    if route not in PLAN_ORDER_ROUTES:
+        raise ValueError(f"build_ar_plan: order_on / PS_PLAN_ORDER is {route!r}, expected one of {PLAN_ORDER_ROUTES}")
+    return route
+
+
+def _finish_plan(plan, G, device, first_steps_dev=None):
+    """The schedules of a plan whose orders are on the host (both routes of build_ar_plan).  first_steps_dev: the device copy of
+    plan.first_steps where the caller has one already; uploaded otherwise."""
+    B = len(plan.order_host)
+    if PER_FRAME_PREFIX and int(plan.first_steps.max()) > plan.first_step:
+        if first_steps_dev is None:
+            fs_t = _pinned("first_steps", (B,), torch.int32)
+            fs_t.numpy()[:] = plan.first_steps
+            first_steps_dev = fs_t.to(device, non_blocking=True)
+        plan.first_steps_dev = first_steps_dev
+        plan.waves_frames = wavefronts(plan.order_host, G, G, plan.first_step, device, first_steps=plan.first_steps)
+    if plan.waves_frames is None or B < TP_MIN_FRAMES:
+        plan.waves   # (no per-frame schedule, or a small batch, whose outpaint_planned runs this one: built here, off the AR stream)
+    _lib.read_status("ps_order_masks_f32", device)   # synchronises: the staging buffers are free again, and a bad order is an error
+
+
+def build_ar_plan(background_mask, G=32, device=None, count_background=False, order_on=None):
     """background_mask (B,S,S) bool/uint8 tensor (device or host) -> ARPlan on `device`.
-    One device->host copy of the mask (the reference does four, z_buffermodel.py:662-669), the integer work (pooling,
+    order_on "host": one device->host copy of the mask (the reference does four, z_buffermodel.py:662-669), the integer work (pooling,
     distance transforms, generation order) in C++ on the host (csrc/host_order.cpp), the orders back up, and the three
     kernel masks built from them on the device (ps_order_masks_f32) -- nothing bigger than the orders crosses PCIe.
+    order_on "device": the same integer work in one kernel on the masks where they are (csrc/ar_order.hip, bit for bit the host's
+    results), the kernel masks queued behind it; what comes down for the host's wavefront schedules is the orders, the regions and
+    the first sampled ranks.  Needs a mask on the device and a shape ps_plan_order_takes accepts: ValueError otherwise, no fallback.
+    order_on None: the environment variable PS_PLAN_ORDER, "host" where it is not set.
     count_background: also keep every mask's number of set pixels (plan.background_counts), for PtsManipulator.forward_scene_step."""
+    route = _order_route(order_on)
+    if route == "device":
+        return _build_ar_plan_device(background_mask, G, device, count_background)
     device = device or (background_mask.device if background_mask.is_cuda else torch.device("cuda", torch.cuda.current_device()))
     B, S, _ = background_mask.shape
     L = G * G
@@ -110,14 +144,49 @@ def build_ar_plan(background_mask, G=32, device=None, count_background=False):
         plan = ARPlan(d_order, d_region, *masks, order_loc.copy(), region, (G, G))   # (the staging buffers are reused by the next plan)
         if count_background:   # set pixels per mask: what a batched chained scene's next frame adds to every cloud
             plan.background_counts = np.count_nonzero(np.asarray(bg).reshape(B, -1), axis=1).tolist()
-        if PER_FRAME_PREFIX and int(plan.first_steps.max()) > plan.first_step:
-            fs_t = _pinned("first_steps", (B,), torch.int32)
-            fs_t.numpy()[:] = plan.first_steps
-            plan.first_steps_dev = fs_t.to(device, non_blocking=True)
-            plan.waves_frames = wavefronts(plan.order_host, G, G, plan.first_step, device, first_steps=plan.first_steps)
-        if plan.waves_frames is None or B < TP_MIN_FRAMES:
-            plan.waves   # (no per-frame schedule, or a small batch, whose outpaint_planned runs this one: built here, off the AR stream)
-        _lib.read_status("ps_order_masks_f32", device)   # synchronises: the staging buffers are free again, and a bad order is an error
+        _finish_plan(plan, G, device)
+    return plan
+
+
+def _build_ar_plan_device(background_mask, G, device, count_background):
+    """build_ar_plan(order_on="device"): ps_plan_order and ps_order_masks_f32 queued on the current stream, the orders, regions and first
+    sampled ranks (5 KB per frame at G = 32) down through pinned buffers, one synchronisation, the schedules on the host as ever."""
+    if not (isinstance(background_mask, torch.Tensor) and background_mask.is_cuda):
+        raise ValueError("build_ar_plan(order_on='device') needs the background mask on the device (a CPU mask takes order_on='host')")
+    if background_mask.dim() != 3 or background_mask.shape[1] != background_mask.shape[2]:
+        raise ValueError(f"build_ar_plan: background_mask must be (B,S,S), got {tuple(background_mask.shape)}")
+    B, S, _ = background_mask.shape
+    if B < 1 or not _lib.call("ps_plan_order_takes", S, G):
+        raise ValueError(f"build_ar_plan(order_on='device'): B = {B}, S = {S}, G = {G} is not a shape ps_plan_order takes")
+    if device is not None and torch.device(device) != background_mask.device:
+        raise ValueError(f"build_ar_plan(order_on='device'): the plan is built where the mask is ({background_mask.device}), not on {device}")
+    device = background_mask.device
+    L = G * G
+    with _PLAN_LOCK, torch.cuda.device(device):
+        as_u8 = (background_mask.view(torch.uint8) if background_mask.dtype == torch.bool and background_mask.is_contiguous()
+                 else background_mask.to(torch.uint8).contiguous())
+        d_order = torch.empty(B, L, dtype=torch.int32, device=device)
+        d_region = torch.empty(B, L, dtype=torch.uint8, device=device)
+        d_first = torch.empty(B, dtype=torch.int32, device=device)
+        d_counts = torch.empty(B, dtype=torch.int32, device=device) if count_background else None
+        _lib.call("ps_plan_order", as_u8, B, S, G, d_order, d_region, d_first, d_counts)
+        masks = [torch.empty(B, 9, L, dtype=torch.float32, device=device) for _ in range(3)]
+        _lib.call("ps_order_masks_f32", d_order, B, G, G, *masks, _lib.status_word(device))
+        order_t, region_t = _pinned("order", (B, L), torch.int32), _pinned("region", (B, L), torch.uint8)
+        first_t = _pinned("first_steps", (B,), torch.int32)
+        order_t.copy_(d_order, non_blocking=True)
+        region_t.copy_(d_region, non_blocking=True)
+        first_t.copy_(d_first, non_blocking=True)
+        if count_background:
+            counts_t = _pinned("bg_counts", (B,), torch.int32)
+            counts_t.copy_(d_counts, non_blocking=True)
+        torch.cuda.current_stream().synchronize()
+        plan = ARPlan(d_order, d_region, *masks, order_t.numpy().copy(), region_t.numpy(), (G, G))
+        if not np.array_equal(plan.first_steps, first_t.numpy()):   # (the kernel's first ranks against the ones its orders and regions give)
+            raise RuntimeError("ps_plan_order: first_steps disagree with order_loc / region")
+        if count_background:
+            plan.background_counts = counts_t.numpy().tolist()
+        _finish_plan(plan, G, device, first_steps_dev=d_first)
     return plan
 
 
