@@ -46,7 +46,7 @@ __device__ __forceinline__ void c1_store(const C1Args &a, size_t p, int co, f32x
         if (a.bias) acc = acc + *(const f32x4 *)(a.bias + co);
         if (a.res) {
             f32x4 r = *(const f32x4 *)(a.res + p * (size_t)Co + co);
-            if (a.relu_res) r = __builtin_elementwise_max(r, (f32x4){0.0f, 0.0f, 0.0f, 0.0f});
+            if (a.relu_res) r = ps::relu_keep_nan(r);
             acc = acc + r;
         }
         *(f32x4 *)dst = acc;
@@ -58,7 +58,7 @@ __device__ __forceinline__ void c1_store(const C1Args &a, size_t p, int co, f32x
             if (a.bias) v = v + a.bias[co + r];
             if (a.res) {
                 const float q = a.res[p * (size_t)Co + co + r];
-                v = v + (a.relu_res ? fmaxf(q, 0.0f) : q);
+                v = v + (a.relu_res ? ps::relu_keep_nan(q) : q);
             }
             dst[r] = v;
         }
@@ -104,7 +104,7 @@ __global__ __launch_bounds__(C1_THREADS) void k_conv1x1(C1Args a)
 #pragma unroll
                 for (int c = 0; c < NCH; ++c) {
                     b[t][c] = *(const f32x4 *)(row + 16 * c);
-                    if (a.relu_in) b[t][c] = __builtin_elementwise_max(b[t][c], (f32x4){0.0f, 0.0f, 0.0f, 0.0f});
+                    if (a.relu_in) b[t][c] = ps::relu_keep_nan(b[t][c]);
                 }
             }
             for (int ot = 0; ot < a.cot; ++ot) {
@@ -131,7 +131,7 @@ __global__ __launch_bounds__(C1_THREADS) void k_conv1x1(C1Args a)
 #pragma unroll
             for (int t = 0; t < C1_PT; ++t) {
                 b[t] = a.x[(p[t] < a.npix ? p[t] : a.npix - 1) * (size_t)a.ldx + kk];
-                if (a.relu_in) b[t] = fmaxf(b[t], 0.0f);
+                if (a.relu_in) b[t] = ps::relu_keep_nan(b[t]);
             }
             for (int ot = 0; ot < a.cot; ++ot) {
                 const float w1 = sWf[ot * 64 + lane];

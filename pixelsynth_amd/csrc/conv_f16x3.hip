@@ -8,8 +8,9 @@
 // (22 of fp32's 24 mantissa bits; below 2^-3 the low half is subnormal and the split is exact to 2^-25 absolute) and a product is
 // three MFMAs:  a * b ~= a.hi * b.hi + a.hi * b.lo + a.lo * b.hi;  the dropped a.lo * b.lo is below 2^-22 relative.  The result
 // differs from an fp32 convolution's by about as much as two fp32 summation orders differ from each other (tests/test_nets_gpu.py
-// holds both against an fp64 reference).  fp16 overflows at 65504: an activation beyond 65000 raises `overflow` (the layers in
-// front of these convolutions are normalisations; the caller checks the flag and falls back).
+// holds both against an fp64 reference).  fp16 overflows at 65504: an activation beyond 65000, or a NaN (the fused ReLU keeps
+// it: ps::relu_keep_nan), raises `overflow` (the layers in front of these convolutions are normalisations; the caller checks the flag
+// and falls back).
 //
 // One workgroup = 8 waves = a 16 x 16 tile of output pixels x 128 output channels; a wave owns 4 rows x 16 pixels x 64 channels as
 // 2 x 2 MFMA tiles of 32 x 32 (64 accumulator registers).  K runs over (32 input channels) x (9 taps) x ...:
@@ -184,7 +185,7 @@ template <bool FUSE, bool PERM = false> __global__ __launch_bounds__(NT) void k_
         for (int i = 0; i < NA; ++i) {
             if (s + 64 * i >= PP) continue;
             f32x4 v = ra[i];
-            if (FUSE) v = __builtin_elementwise_max(v * rsc - rsh, (f32x4){0.f, 0.f, 0.f, 0.f});
+            if (FUSE) v = ps::relu_keep_nan(v * rsc - rsh);   // (not max(): maxNum would turn a NaN into 0 in front of the guard below)
             if (!((valid >> i) & 1)) v = (f32x4){0.f, 0.f, 0.f, 0.f};
             h4 hi, lo;
 #pragma unroll

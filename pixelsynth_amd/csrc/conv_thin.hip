@@ -46,7 +46,7 @@ template <bool FUSE> __global__ __launch_bounds__(256) void k_thin_in(const f32x
             f32x4 v = zero;
             if (iy >= 0 && iy < H && ix >= 0 && ix < W) {
                 v = x[((size_t)b * H + iy) * W + ix];
-                if (FUSE) v = __builtin_elementwise_max(v * sc - sh, zero);
+                if (FUSE) v = ps::relu_keep_nan(v * sc - sh);
             }
             in[r][c] = v;
         }
@@ -96,7 +96,7 @@ template <int CO, bool FUSE> __global__ __launch_bounds__(256) void k_thin_out(c
                 v = *(const f32x4 *)(xb + ((size_t)iy * W + ix) * Ci + c0 + 4 * c4);
                 if (FUSE) {
                     const f32x4 sc = *(const f32x4 *)(scale + (size_t)b * Ci + c0 + 4 * c4), sh = *(const f32x4 *)(shift + (size_t)b * Ci + c0 + 4 * c4);
-                    v = __builtin_elementwise_max(v * sc - sh, zero);
+                    v = ps::relu_keep_nan(v * sc - sh);
                 }
             }
             patch[c4][p] = v;
@@ -171,7 +171,7 @@ template <bool FUSE> __global__ __launch_bounds__(256) void k_thin_in_mfma(const
             const int iy = oy + t / 3 - 1, ix = ox + t % 3 - 1;
             if (t < 9 && iy >= 0 && iy < H && ix >= 0 && ix < W) {
                 v = x[((size_t)b * H + iy) * W + ix];
-                if (FUSE) v = __builtin_elementwise_max(v * sc - sh, zero);
+                if (FUSE) v = ps::relu_keep_nan(v * sc - sh);
             }
             return v;
         };

@@ -31,7 +31,7 @@ __global__ __launch_bounds__(256) void k_affine_relu(const f32x4 *__restrict__ x
         const size_t b = i / per_frame4;
         const int c4 = (int)(i % C4);
         const f32x4 v = x[i] * scale[b * C4 + c4] - shift[b * C4 + c4];
-        y[i] = __builtin_elementwise_max(v, zero);
+        y[i] = ps::relu_keep_nan(v);
     }
 }
 

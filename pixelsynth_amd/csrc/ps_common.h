@@ -45,4 +45,13 @@ inline int fail(int code, const char *fmt, ...)
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// The ReLU of the kernels that stand in for torch.relu / clamp_min: a NaN stays a NaN.  max(v, 0) is IEEE maxNum (v_max_f32), which
+// answers 0 for a NaN -- a clean-looking result from a broken input, and nothing left for the split-fp16 overflow guard to see.
+// float or an ext_vector of floats; -inf and any negative value give 0, +inf stays.
+template <typename T> __device__ __forceinline__ T relu_keep_nan(T v)
+{
+    const T zero = {};
+    return v < zero ? zero : v;
+}
+
 }  // namespace ps

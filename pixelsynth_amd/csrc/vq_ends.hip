@@ -72,7 +72,9 @@ struct HeadArgs {
     int B, Hh, Wh;
 };
 
-__global__ __launch_bounds__(VE_THREADS) void k_vq_head(HeadArgs a)
+// (two waves per SIMD, as with the single accumulator this kernel had: the three rows' loads in flight plus one accumulator per tap
+// would otherwise take 264 registers and halve the occupancy)
+__global__ __launch_bounds__(VE_THREADS) __attribute__((amdgpu_waves_per_eu(2))) void k_vq_head(HeadArgs a)
 {
     __shared__ f32x4 sW[9 * 4 * 64];        // [tap (dy, dx)][16-channel chunk c][lane (row m, kk)] = W'[m][tap][16 c + 4 kk ..]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, i = lane & 15, kk = lane >> 4;
@@ -96,7 +98,11 @@ __global__ __launch_bounds__(VE_THREADS) void k_vq_head(HeadArgs a)
         const size_t rest = tile / tiles_row;
         const int y = (int)(rest % Hh), b = (int)(rest / Hh), x = 16 * xg + i;
         const float *frame = a.h + (size_t)b * Hh * Wh * 64 + 4 * kk;
-        f32x4 acc = zero;
+        // One accumulator per tap: a tap feeds only the parities that reach it (row 2 y + py takes input row y + dy for dy = py - 1, py),
+        // the other rows of its MFMAs multiply ZERO weights -- and 0 * NaN = NaN, 0 * inf = NaN.  Summed into one accumulator that would
+        // carry a NaN or inf of h to a 6 x 6 block of output pixels where the layer reaches 4 x 4; kept apart (three at a time, one row
+        // of taps), each output row picks up the taps that are its own and never sees the others'.
+        f32x4 out = zero;
         // A row of the 3 x 3 neighbourhood is read ONCE: lane (i, kk) fetches its own position and -- lanes 0 / 15 -- the position left /
         // right of the tile; the dx = -1 / +1 operands are the neighbouring lanes' registers (DPP row shifts: a row of 16 lanes is the 16
         // positions of one kk), the edge value standing in where the shift runs out of the row.  3.4 instead of 9 fetches per position.
@@ -106,13 +112,13 @@ __global__ __launch_bounds__(VE_THREADS) void k_vq_head(HeadArgs a)
             const int yy = y + dy;
             const bool rin = yy >= 0 && yy < Hh, ein = rin && xe >= 0 && xe < Wh;
             const float *rc = frame + ((size_t)(rin ? yy : y) * Wh + x) * 64, *re = frame + ((size_t)(rin ? yy : y) * Wh + (ein ? xe : x)) * 64;
-            f32x4 ctr[4], edge[4];
+            f32x4 ctr[4], edge[4], acc[3] = {zero, zero, zero};
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
                 ctr[c] = *(const f32x4 *)(rc + 16 * c);
                 edge[c] = *(const f32x4 *)(re + 16 * c);
-                ctr[c] = rin ? __builtin_elementwise_max(ctr[c], zero) : zero;       // the ReLU in front of the layer; zero padding
-                edge[c] = ein ? __builtin_elementwise_max(edge[c], zero) : zero;
+                ctr[c] = rin ? ps::relu_keep_nan(ctr[c]) : zero;       // the ReLU in front of the layer; zero padding
+                edge[c] = ein ? ps::relu_keep_nan(edge[c]) : zero;
             }
 #pragma unroll
             for (int dx = -1; dx <= 1; ++dx) {
@@ -127,8 +133,15 @@ __global__ __launch_bounds__(VE_THREADS) void k_vq_head(HeadArgs a)
                     }
                     const f32x4 w4 = sW[(tap * 4 + c) * 64 + lane];
 #pragma unroll
-                    for (int q = 0; q < 4; ++q) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(w4[q], v[q], acc, 0, 0, 0);
+                    for (int q = 0; q < 4; ++q) acc[dx + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(w4[q], v[q], acc[dx + 1], 0, 0, 0);
                 }
+            }
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {   // (selects, not products: the taps of the other parities may hold anything)
+                const int m = 4 * kk + r, py = m / 6, px = (m / 3) & 1;
+                const bool row = dy == py - 1 || dy == py;
+#pragma unroll
+                for (int dx = -1; dx <= 1; ++dx) out[r] += (row && (dx == px - 1 || dx == px)) ? acc[dx + 1][r] : 0.0f;
             }
         }
         // lane (position i, kk) holds rows m = 4 kk + r of the tile: (parity, channel) = (m / 3, m % 3)
@@ -137,7 +150,7 @@ __global__ __launch_bounds__(VE_THREADS) void k_vq_head(HeadArgs a)
             const int m = 4 * kk + r;
             if (m >= 12) continue;
             const int py = m / 6, px = (m / 3) & 1, co = m % 3;
-            a.y[(((size_t)b * 3 + co) * (2 * Hh) + 2 * y + py) * (2 * Wh) + 2 * x + px] = acc[r] + a.bias[co];
+            a.y[(((size_t)b * 3 + co) * (2 * Hh) + 2 * y + py) * (2 * Wh) + 2 * x + px] = out[r] + a.bias[co];
         }
     }
 }

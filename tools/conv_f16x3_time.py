@@ -1,4 +1,5 @@
-"""Time csrc/conv_f16x3.hip alone on some of the decoder's shapes (tuning builds: PS_HIP_LIB).  usage: python tools/conv_f16x3_time.py [views]"""
+"""Time csrc/conv_f16x3.hip alone on some of the decoder's shapes (tuning builds: PS_HIP_LIB).  usage: python tools/conv_f16x3_time.py [views] [--res] [--fuse]
+--fuse: the norm + ReLU on the way in, a scale / shift per view (the form every product call takes)."""
 import sys
 import torch
 sys.path.insert(0, ".")
@@ -16,7 +17,8 @@ for (H, Ci, Co) in [(256, 64, 128), (256, 128, 128), (128, 256, 256), (64, 256, 
     _lib.check(L.ps_conv3x3_f16x3_pack(w.data_ptr(), Co, Ci, wp.data_ptr(), st()), "pack")
     y = torch.empty(V, H, H, Co, device=dev)
     res = torch.randn(V, H, H, Co, device=dev) if "--res" in sys.argv else None
-    fn = lambda: _lib.check(L.ps_conv3x3_f16x3_nhwc(x.data_ptr(), None, None, wp.data_ptr(), None, None if res is None else res.data_ptr(), V, H, H, Ci, Co,
+    sc, sh = (torch.rand(V, Ci, device=dev) + 0.5, torch.randn(V, Ci, device=dev) * 0.3) if "--fuse" in sys.argv else (None, None)
+    fn = lambda: _lib.check(L.ps_conv3x3_f16x3_nhwc(x.data_ptr(), None if sc is None else sc.data_ptr(), None if sh is None else sh.data_ptr(), wp.data_ptr(), None, None if res is None else res.data_ptr(), V, H, H, Ci, Co,
                                                     y.data_ptr(), flag.data_ptr(), st()), "conv")
     for _ in range(3):
         fn()
