@@ -141,9 +141,18 @@ PLAN_PROTOS = {
     "ps_plan_order": (RC, [c_void_p, c_int, c_int, c_int] + [c_void_p] * 4 + [STREAM]),
 }
 
+# libpixelsynth_rank.so (include/pixelsynth_rank.h): scoring and ranking the best-of-N candidates on the device
+RANK_PROTOS = {
+    "ps_rank_last_error": (ctypes.c_char_p, []),
+    "ps_rank_classifier_input": (RC, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, STREAM]),
+    "ps_rank_entropy": (RC, [c_void_p, c_int, c_int, c_void_p, STREAM]),
+    "ps_rank_hinge_fake": (RC, [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, STREAM]),
+    "ps_rank_select": (RC, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, STREAM]),
+}
+
 # short name of _libraries.LIBRARIES -> its prototype table; _OWNER: entry point -> the table entry of its library, built once
 PROTOS = {"hip": _PROTOS, "percsim": PERCSIM_PROTOS, "consistency": CONSISTENCY_PROTOS, "fid": FID_PROTOS, "scene": SCENE_PROTOS,
-          "plan": PLAN_PROTOS}
+          "plan": PLAN_PROTOS, "rank": RANK_PROTOS}
 _ENTRIES = {e.name: e for e in _libraries.LIBRARIES}
 assert set(PROTOS) == set(_ENTRIES)
 _OWNER = {fn: _ENTRIES[name] for name, table in PROTOS.items() for fn in table}

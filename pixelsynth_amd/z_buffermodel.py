@@ -41,6 +41,20 @@ def rank_samples(discrim_scores, entropy_scores):
     return int(np.argmax(.5 * (n - 1 - entr_rank) + .5 * disc_rank))
 
 
+RANK_ROUTES = ("host", "device")
+
+
+def _rank_route(rank_on, opt):
+    """rank_on of get_best_sample -> "host" / "device"; None: opt.rank_on, then the environment variable PS_RANK (read per call), host
+    by default"""
+    route = rank_on if rank_on is not None else getattr(opt, "rank_on", None)
+    if route is None:
+        route = os.environ.get("PS_RANK", "host")
+    if route not in RANK_ROUTES:
+        raise ValueError(f"get_best_sample: rank_on / opt.rank_on / PS_RANK is {route!r}, expected one of {RANK_ROUTES}")
+    return route
+
+
 class _SceneState:
     """What forward_scene carries from one rendered frame to the next (z_buffermodel.py:436-443)."""
 
@@ -465,10 +479,10 @@ class ZbufferModelPts(nn.Module):
 
     # ---------------------------------------------------------------- reference-shaped single image path
     @torch.no_grad()
-    def forward_image(self, batch, netD=None):
+    def forward_image(self, batch, netD=None, rank_on=None):
         """Hot-path part of forward_image (z_buffermodel.py:291-419) for model_setting gen_img / gen_paired_img.
         batch: {"images": [(B,3,S,S)], "cameras": [{"P","Pinv","K","Kinv"}], optional "depths": [(B,1,S,S)],
-        optional "codes": (B,32,32)} -> (None, outputs dict with the reference's keys)."""
+        optional "codes": (B,32,32)} -> (None, outputs dict with the reference's keys).  rank_on: get_best_sample's."""
         dev = next(self.parameters()).device   # (the renderer itself refuses anything but the GPU)
         input_img = batch["images"][0].to(dev)
         cam = {k: v.to(dev) for k, v in batch["cameras"][0].items() if torch.is_tensor(v)}
@@ -498,7 +512,7 @@ class ZbufferModelPts(nn.Module):
         if max(int(getattr(self.opt, "num_samples", 1)), 1) > 1:   # :349 -> get_best_sample with opt.num_samples candidates
             plan = self.get_masks_for_batch(output_RT, input_RTinv, background_mask, compact=True)
             outputs["PredImg"] = self.get_best_sample(plan, downsampled_fs, background_mask, gen_fs, netD, input_img,
-                                                      shard=bool(getattr(self.opt, "shard_samples", False)))
+                                                      shard=bool(getattr(self.opt, "shard_samples", False)), rank_on=rank_on)
             return None, outputs
         masks_init, masks_undilated, masks_dilated, gen_order = self.get_masks_for_batch(output_RT, input_RTinv,
                                                                                          background_mask)
@@ -539,7 +553,7 @@ class ZbufferModelPts(nn.Module):
         return x if self.projector is None else checked(x.device, lambda: self.projector(x, *mask))
 
     @torch.no_grad()
-    def get_best_sample(self, *args, uniforms=None, shard=False):
+    def get_best_sample(self, *args, uniforms=None, shard=False, rank_on=None):
         """z_buffermodel.py:244-276 on the fused sampler: num_samples outpaintings of the same view, the best by
         discriminator + entropy rank is kept.  Two call forms:
           get_best_sample(gen_order, masks, downsampled_fs, background_mask, gen_fs, netD, input_img)   the reference's (:244),
@@ -550,8 +564,16 @@ class ZbufferModelPts(nn.Module):
         uniforms: optional (num_samples,B,L) draws (otherwise torch.Generator seeded i, as sample() reseeds with i).
         shard (or opt.shard_samples through forward_image): under torch.distributed the candidates are dealt over the ranks
         (candidate i on rank i % W: SURVEY 8e), two scalars per candidate are gathered, every rank applies the rank rule and
-        the owner of the winner broadcasts it."""
+        the owner of the winner broadcasts it.
+        rank_on "host": every candidate is scored as the reference scores it, one at a time through the host (run_discriminator_one_step,
+        _entropy_score).  rank_on "device": the candidates, decoded exactly as on the host route, are stacked and scored in one batch
+        where they are (ranking.score_candidates), the rank rule runs there too and the winner comes back through index_select -- no
+        score comes down (under `shard`: the two vectors of a rank's own candidates, once).  It applies where ranking.can_score_on_device
+        holds and B = 1; any other scorer, stand-ins included, takes the host route.  None: opt.rank_on, then the environment variable
+        PS_RANK, "host" where neither is set."""
         from . import distributed as D
+        from . import ranking
+        route = _rank_route(rank_on, self.opt)
         if isinstance(args[0], ARPlan):
             plan, codes, background_mask, gen_fs, netD, input_img = args
         else:
@@ -573,7 +595,7 @@ class ZbufferModelPts(nn.Module):
         # launches of one run instead of k runs one after the other (the num_samples candidates are one of
         # the path's natural parallel axes).
         per = max(1, min(len(mine), self.sample_batch // max(B, 1)))          # candidates per engine run
-        imgs, disc, entr = {}, [], []
+        imgs, disc, entr, on_device = {}, [], [], None
         for s0 in range(0, len(mine), per):
             idx = mine[s0:s0 + per]
             k = len(idx)
@@ -590,11 +612,19 @@ class ZbufferModelPts(nn.Module):
             for j, i in enumerate(idx):
                 img = self._decode_checked(gen_fs, background_mask, c[j * B:(j + 1) * B].view(B, G, self.obs[2]))
                 imgs[i] = img
-                if n > 1:
+                if n > 1 and on_device is None:
+                    on_device = route == "device" and B == 1 and ranking.can_score_on_device(netD, self.classifier, img)
+                if n > 1 and not on_device:
                     disc.append(float(netD.run_discriminator_one_step(img, input_img)["D_Fake"].mean().cpu()))
                     entr.append(self._entropy_score(img))
         if n == 1:
             return imgs[0]
+        if on_device:
+            stack = torch.cat([imgs[i] for i in mine])
+            disc_dev, entr_dev = ranking.score_candidates(stack, netD, self.classifier)
+            if len(mine) == n:
+                return stack.index_select(0, ranking.select(disc_dev, entr_dev))
+            disc, entr = torch.stack([disc_dev, entr_dev]).double().cpu().tolist()    # the one download of this rank's scores
         if len(mine) < n:
             d_all, e_all = D.gather_scores(disc, entr, n)
             best = rank_samples(list(d_all), list(e_all))
