@@ -48,7 +48,8 @@ int ps_rank_hinge_fake(const float *map0, int len0, const float *map1, int len1,
 
 /* The rank rule on disc (n) and entr (n) fp32, 1 <= n <= PS_RANK_MAX_N.  The rank of an element is the number of elements that sort
  * before it: ascending by value, the lower index first among equal values, NaN after every number.  total2 = (n - 1 - entr_rank) +
- * disc_rank; best[0] (int32) = the first index of its maximum.  disc_rank, entr_rank (n) int32 or NULL.  One workgroup. */
+ * disc_rank; best[0] (int32) = the first index of its maximum.  disc_rank, entr_rank (n) int32 or NULL.  One workgroup.  The same rule
+ * for every view of a batch, one workgroup per view, and the winners' hand-over: include/pixelsynth_rank_groups.h. */
 int ps_rank_select(const float *disc, const float *entr, int n, int32_t *best, int32_t *disc_rank, int32_t *entr_rank, void *stream);
 
 /* ps_rank_last_error: the message of this library's last failed call. */

@@ -150,9 +150,17 @@ RANK_PROTOS = {
     "ps_rank_select": (RC, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, STREAM]),
 }
 
+# libpixelsynth_rank_groups.so (include/pixelsynth_rank_groups.h): the rank rule per view of a batch, and the winners' hand-over
+c_long = ctypes.c_long
+RANK_GROUPS_PROTOS = {
+    "ps_rank_groups_last_error": (ctypes.c_char_p, []),
+    "ps_rank_select_groups": (RC, [c_void_p, c_void_p, c_int, c_int, c_long, c_long, c_void_p, c_void_p, c_void_p, STREAM]),
+    "ps_rank_take_groups": (RC, [c_void_p, c_void_p, c_int, c_int, c_long, c_long, c_long, c_void_p, STREAM]),
+}
+
 # short name of _libraries.LIBRARIES -> its prototype table; _OWNER: entry point -> the table entry of its library, built once
 PROTOS = {"hip": _PROTOS, "percsim": PERCSIM_PROTOS, "consistency": CONSISTENCY_PROTOS, "fid": FID_PROTOS, "scene": SCENE_PROTOS,
-          "plan": PLAN_PROTOS, "rank": RANK_PROTOS}
+          "plan": PLAN_PROTOS, "rank": RANK_PROTOS, "rank_groups": RANK_GROUPS_PROTOS}
 _ENTRIES = {e.name: e for e in _libraries.LIBRARIES}
 assert set(PROTOS) == set(_ENTRIES)
 _OWNER = {fn: _ENTRIES[name] for name, table in PROTOS.items() for fn in table}

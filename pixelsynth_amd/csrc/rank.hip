@@ -10,15 +10,18 @@
 //                  host's 3 x 256 table.  Table-driven: the bounds and 22-bit weights are Pillow's, made by the host.
 //   k_rank_entropy one wave per row of logits: maximum, sum of exp, sum of p log p; per-lane strided partial results, one butterfly each.
 //   k_rank_hinge   one wave per candidate: the hinge term of every element of its two patch maps, summed in fp64.
-//   k_rank_select  one workgroup: both lists in LDS, every element's rank by counting, the packed (total, index) maximum.
+//   k_rank_select  one workgroup: both lists in LDS, every element's rank by counting, the packed (total, index) maximum
+//                  (rank_select.h: libpixelsynth_rank_groups.so runs the same code once per view of a batch).
 // The unit is built with -ffp-contract=off: the quantisation's three fp32 operations stay three.
 #include "ps_common.h"
 
 #include "../../include/pixelsynth_rank.h"
+#include "rank_select.h"
 
 namespace {
 
 constexpr int RANK_THREADS = 256;
+static_assert(RANK_THREADS == ps_rank::SELECT_THREADS, "k_rank_select is one workgroup of select_group");
 constexpr int BAND_ROWS = 16;                        // output rows of a workgroup of k_rank_input, fewer where LDS asks for it
 constexpr size_t BAND_LDS_BYTES = 48 * 1024;         // at most, for the horizontal pass's rows
 constexpr int PRECISION_BITS = 32 - 8 - 2;           // Pillow's (src/libImaging/Resample.c)
@@ -130,43 +133,12 @@ __global__ __launch_bounds__(64) void k_rank_hinge(const float *__restrict__ map
     if (lane == 0) d_fake[n] = (float)(0.5 * (m0 + m1));
 }
 
-// a (at index j) sorts before b (at index i): ascending, the lower index first among equals, NaN after every number
-__device__ __forceinline__ bool sorts_before(float a, int j, float b, int i)
-{
-    const bool an = a != a, bn = b != b;
-    if (an || bn) return an == bn ? j < i : bn;
-    return a < b || (a == b && j < i);
-}
-
+// the rank rule itself is rank_select.h's, shared with rank_groups.hip (one workgroup per group of candidates there, one group here)
 __global__ __launch_bounds__(RANK_THREADS) void k_rank_select(const float *__restrict__ disc, const float *__restrict__ entr, int n,
                                                               int32_t *__restrict__ best, int32_t *__restrict__ disc_rank,
                                                               int32_t *__restrict__ entr_rank)
 {
-    __shared__ float s_d[PS_RANK_MAX_N], s_e[PS_RANK_MAX_N];
-    __shared__ uint32_t s_key[RANK_THREADS / 64];
-    const int tid = threadIdx.x;
-    for (int i = tid; i < n; i += RANK_THREADS) s_d[i] = disc[i], s_e[i] = entr[i];
-    __syncthreads();
-    uint32_t key = 0;                                // total2 << 10 | (1023 - index): its maximum is the first index of the largest total2
-    for (int i = tid; i < n; i += RANK_THREADS) {
-        const float d = s_d[i], e = s_e[i];
-        int dr = 0, er = 0;
-        for (int j = 0; j < n; ++j) {
-            dr += sorts_before(s_d[j], j, d, i);
-            er += sorts_before(s_e[j], j, e, i);
-        }
-        if (disc_rank) disc_rank[i] = dr;
-        if (entr_rank) entr_rank[i] = er;
-        key = max(key, ((uint32_t)(n - 1 - er + dr) << 10) | (uint32_t)(PS_RANK_MAX_N - 1 - i));
-    }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) key = max(key, (uint32_t)__shfl_xor((int)key, d, 64));
-    if ((tid & 63) == 0) s_key[tid >> 6] = key;
-    __syncthreads();
-    if (tid == 0) {
-        for (int w = 1; w < RANK_THREADS / 64; ++w) key = max(key, s_key[w]);
-        best[0] = PS_RANK_MAX_N - 1 - (int32_t)(key & (PS_RANK_MAX_N - 1));
-    }
+    ps_rank::select_group(disc, entr, n, 1, best, disc_rank, entr_rank);
 }
 
 }  // namespace

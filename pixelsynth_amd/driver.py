@@ -27,6 +27,11 @@ distributed.shard_views -- no collective, every rank writes its own scenes, scen
 writes the layout of the reference's eval_consistency.py:122-149 under <out>/<%04d>/: input_image_.png,
 output_image_<d>_0001.png, output_image_<d>_0002.png -- the views `python -m pixelsynth_amd.evaluate --consistency` lists.
 
+--num-samples N with --discriminator PATH and --classifier PATH (state_dicts of losses.DiscriminatorLoss and of
+networks.resnet18(num_classes=365)) is the reference's quality mode (num_samples 50 of its demo scripts) on the chained paths, --scene
+and --pairs: every frame of every scene keeps the best of N outpaintings, scored and ranked on the device (pixelsynth_amd/ranking.py;
+a batch of scenes ranks per scene).  The circle / trajectory path renders one sample per view.
+
 The depth regressor (networks.Unet) and the refinement decoder (networks.get_decoder) are part of the package, and ZbufferModelPts
 builds them from the reference's options (norm_G, refine_model_type); THIS driver builds the model without them and ships no trained
 weights: depth is synthetic unless --depth-npy is given, weights are random-init unless --pixelcnn / --vqvae state
@@ -51,9 +56,22 @@ def make_opts(**kw):
     return types.SimpleNamespace(**o)
 
 
-def build_model(device, pixelcnn_sd=None, vqvae_sd=None):
+def build_scorers(discriminator_sd, classifier_sd):
+    """--discriminator / --classifier -> (netD, classifier) of the sample ranking, on the host: the discriminator mirror in hinge mode
+    (the options of the reference's trained model) and the Places365 ResNet-18, each with its state_dict loaded strictly."""
+    from .losses import DiscriminatorLoss
+    from .networks import resnet18
+    opt = argparse.Namespace(discriminator_losses="pix2pixHD", gan_mode="hinge", norm_D="spectralinstance", ndf=64, output_nc=3,
+                             no_ganFeat_loss=False, isTrain=False, lambda_feat=10.0)
+    netD, classifier = DiscriminatorLoss(opt).eval(), resnet18(num_classes=365).eval()
+    netD.load_state_dict(torch.load(discriminator_sd, map_location="cpu"), strict=True)
+    classifier.load_state_dict(torch.load(classifier_sd, map_location="cpu"), strict=True)
+    return netD, classifier
+
+
+def build_model(device, pixelcnn_sd=None, vqvae_sd=None, classifier=None):
     from .z_buffermodel import ZbufferModelPts
-    model = ZbufferModelPts(make_opts()).eval()
+    model = ZbufferModelPts(make_opts(), classifier=classifier).eval()
     load = lambda path, fallback: torch.load(path, map_location="cpu") if path else {k: torch.from_numpy(v) for k, v in fallback.items()}
     model.outpaint2.load_state_dict(load(pixelcnn_sd, syn.pixelcnn_state_dict(0)))
     model.vqvae.load_state_dict(load(vqvae_sd, syn.vqvae_state_dict(0)))
@@ -186,10 +204,11 @@ def pairs_to_disk(outputs, group, direction_ids, out_dir):
 
 
 @torch.no_grad()
-def run_scenes(model, imgs, cam, groups, out_dir, directions=None, num_split=None, pair_directions=None):
+def run_scenes(model, imgs, cam, groups, out_dir, directions=None, num_split=None, pair_directions=None, netD=None):
     """Independent chained scenes in batches: imgs {scene index: (1,3,S,S)}, cam the (1,4,4) demo cameras every scene starts from,
     groups from scene_groups.  pair_directions {scene index: direction index}: gen_two_imgs and the --pairs layout; otherwise
-    gen_scene over `directions` and the per-scene scene/ + video/ layout.  -> scenes written."""
+    gen_scene over `directions` and the per-scene scene/ + video/ layout.  netD: the discriminator of the sample ranking
+    (opt.num_samples > 1).  -> scenes written."""
     done = 0
     for group in groups:
         B = len(group)
@@ -198,7 +217,7 @@ def run_scenes(model, imgs, cam, groups, out_dir, directions=None, num_split=Non
         if pair_directions is not None:
             ids = [pair_directions[i] for i in group]
             batch["direction"] = torch.tensor(ids)
-        _, outputs = model(batch)
+        _, outputs = model(batch, netD)
         model.outpaint2.engine(32, 32, B).check()
         if pair_directions is not None:
             pairs_to_disk(outputs, group, ids, out_dir)
@@ -305,7 +324,15 @@ def main(argv=None):
     ap.add_argument("--out", default="results")
     ap.add_argument("--pixelcnn", help="state_dict of the reference's OurPixelCNN (torch.save)")
     ap.add_argument("--vqvae", help="state_dict of the reference's VQVAETop (torch.save)")
+    ap.add_argument("--num-samples", type=int, default=1, metavar="N", help="--scene / --pairs: outpaintings per frame, the best by "
+                                                                            "discriminator + entropy rank is kept (needs both scorers)")
+    ap.add_argument("--discriminator", metavar="PATH", help="state_dict of losses.DiscriminatorLoss (torch.save)")
+    ap.add_argument("--classifier", metavar="PATH", help="state_dict of networks.resnet18(num_classes=365), the Places365 classifier")
     args = ap.parse_args(argv)
+    if args.num_samples < 1:
+        ap.error("--num-samples must be >= 1")
+    if args.num_samples > 1 and not (args.discriminator and args.classifier):
+        ap.error("--num-samples > 1 ranks candidates with two scorers: give --discriminator PATH and --classifier PATH")
     sources = source_images(args.image, args.image_dir)
     many = args.image_dir is not None or len(sources) > 1 or args.pairs is not None
     if many and not (args.scene or args.pairs):
@@ -332,19 +359,26 @@ def main(argv=None):
             torch.distributed.init_process_group("gloo")
         else:
             torch.distributed.init_process_group("nccl", device_id=device)
-    model = build_model(device, args.pixelcnn, args.vqvae)
+    netD = classifier = None
+    ranked = args.num_samples > 1 and bool(args.scene or args.pairs)       # (the circle / trajectory path stays at one sample)
+    if ranked:
+        netD, classifier = build_scorers(args.discriminator, args.classifier)
+        netD = netD.to(device)
+    model = build_model(device, args.pixelcnn, args.vqvae, classifier)
+    model.opt.num_samples = args.num_samples if ranked else 1
+    if ranked:
+        model.opt.rank_on = "device"     # (a trailing group of one scene scores on the same route as the groups before it)
     t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
     if many:     # independent scenes: dealt over the ranks, no collective, every rank writes its own
         groups = scene_groups(len(sources), args.batch, rank, world)
         imgs = {i: load_image(sources[i]).to(device) for g in groups for i in g}
         cam = {k: t(v) for k, v in syn.demo_cameras(1).items()}
-        model.opt.num_samples = 1
         if args.pairs:
             model.opt.model_setting, model.opt.num_split = "gen_two_imgs", 2      # (gen_two_imgs renders views 2, 1, 0 whatever num_split says)
-            n = run_scenes(model, imgs, cam, groups, args.out, pair_directions=dict(enumerate(pair_ids)))
+            n = run_scenes(model, imgs, cam, groups, args.out, pair_directions=dict(enumerate(pair_ids)), netD=netD)
         else:
             model.opt.directions, model.opt.num_split, model.opt.sequential_outpainting = list(args.scene), args.num_split, args.sequential
-            n = run_scenes(model, imgs, cam, groups, args.out, directions=list(args.scene), num_split=args.num_split)
+            n = run_scenes(model, imgs, cam, groups, args.out, directions=list(args.scene), num_split=args.num_split, netD=netD)
         print(f"rank {rank}: {n} of {len(sources)} scenes ({'pairs' if args.pairs else 'chained ' + ' '.join(args.scene)}) in groups of "
               f"{args.batch} -> {args.out}/%04d/")
         if world > 1:
@@ -355,9 +389,9 @@ def main(argv=None):
     cam = {k: t(v) for k, v in syn.demo_cameras(1).items()}
     if args.scene:
         model.opt.directions, model.opt.num_split = list(args.scene), args.num_split
-        model.opt.sequential_outpainting, model.opt.num_samples = args.sequential, 1
+        model.opt.sequential_outpainting = args.sequential
         batch = {"images": [img], "cameras": [cam], "depth_fn": syn.depth_from_image}
-        _, outputs = model(batch)
+        _, outputs = model(batch, netD)
         model.outpaint2.engine(32, 32, 1).check()
         n = scene_outputs_to_disk(outputs, model.opt.directions, args.num_split, os.path.join(args.out, f"rank{rank}") if world > 1 else args.out)
         print(f"rank {rank}: chained scene {' '.join(args.scene)}: {n} video frames")

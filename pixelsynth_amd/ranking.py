@@ -11,7 +11,14 @@ discriminator sees the candidate next to the same input image N times over.  Her
     select             the rank rule of rank_samples -> the winner's index, on the device
     score_candidates   the four of them around ONE forward of the classifier and ONE of the discriminator, on the N fakes alone
 
-The numpy restatements the tests pin them to (pil_bilinear_tables, classifier_input_reference, select_reference) live here too.
+Best-of-N PER VIEW for a batch of B views (get_best_sample's rank_scope="view": csrc/rank_groups.hip behind
+include/pixelsynth_rank_groups.h) scores the N * B candidates with score_candidates, in chunks, and then
+
+    select_groups      the rank rule in every view's own N candidates -> B winner indices, on the device
+    take_groups        the B winners out of the N * B candidates, the indices read where they are
+
+The numpy restatements the tests pin them to (pil_bilinear_tables, classifier_input_reference, select_reference,
+select_groups_reference) live here too.
 """
 import functools
 import math
@@ -23,6 +30,9 @@ from . import _lib
 
 MEAN, STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)     # the classifier's normalisation (z_buffermodel.py:258)
 MAX_SIDE, MAX_N = 1024, 1024                                 # PS_RANK_MAX_SIDE, PS_RANK_MAX_N
+MAX_GROUPS = 65535                                           # PS_RANK_MAX_GROUPS
+LAYOUTS = ("candidate_major", "group_major")
+SCORE_CHUNK = 64                                             # candidates per forward of the scorers where a cap is asked for (score_candidates)
 PRECISION_BITS = 32 - 8 - 2
 
 
@@ -126,6 +136,27 @@ def select_reference(disc, entr):
     return int(np.argmax((n - 1 - entr_rank) + disc_rank)), disc_rank, entr_rank
 
 
+def group_strides(groups, n, layout):
+    """layout -> (group_stride, cand_stride) of ps_rank_select_groups / ps_rank_take_groups: candidate i of group g lies at
+    g * group_stride + i * cand_stride"""
+    if layout not in LAYOUTS:
+        raise ValueError(f"layout is {layout!r}, expected one of {LAYOUTS}")
+    return (1, groups) if layout == "candidate_major" else (n, 1)
+
+
+def select_groups_reference(disc, entr, groups, n, layout="candidate_major"):
+    """-> (best (groups,), disc_rank, entr_rank (groups * n,) laid out as the scores are): select_reference on every group's own scores"""
+    disc, entr = np.asarray(disc).reshape(-1), np.asarray(entr).reshape(-1)
+    if len(disc) != groups * n or len(entr) != groups * n or groups < 1 or n < 1:
+        raise ValueError(f"select_groups_reference: expected two lists of {groups} * {n} scores, got {len(disc)} and {len(entr)}")
+    gs, cs = group_strides(groups, n, layout)
+    best, disc_rank, entr_rank = np.empty(groups, np.int64), np.empty(groups * n, np.int64), np.empty(groups * n, np.int64)
+    for g in range(groups):
+        at = g * gs + np.arange(n) * cs
+        best[g], disc_rank[at], entr_rank[at] = select_reference(disc[at], entr[at])
+    return best, disc_rank, entr_rank
+
+
 # ---------------------------------------------------------------- the device wrappers
 _TABLES = {}    # (S, T, device index) -> (bounds, coeffs, norm) on that device: uploaded once
 
@@ -197,6 +228,40 @@ def select(disc, entr, want_ranks=False):
     return (best.long(), *ranks) if want_ranks else best.long()
 
 
+def select_groups(disc, entr, groups, n, layout="candidate_major", want_ranks=False):
+    """disc, entr (groups * n) fp32 on the device, candidate i of group g where `layout` puts it (group_strides) -> the kept index of
+    every group as a (groups,) int32 device tensor [, disc_rank, entr_rank (groups * n) int32, laid out as the scores]; one launch"""
+    disc, entr = _fp32("select_groups", disc, 1), _fp32("select_groups", entr, 1)
+    gs, cs = group_strides(groups, n, layout)
+    if not (1 <= n <= MAX_N and 1 <= groups <= MAX_GROUPS) or disc.shape[0] != groups * n or entr.shape[0] != groups * n:
+        raise ValueError(f"select_groups: expected two lists of groups * n scores with n in 1 .. {MAX_N} and groups in 1 .. {MAX_GROUPS}, "
+                         f"got groups = {groups}, n = {n} and lists of {disc.shape[0]} and {entr.shape[0]}")
+    with torch.cuda.device(disc.device):
+        best = torch.empty(groups, dtype=torch.int32, device=disc.device)
+        ranks = [torch.empty(groups * n, dtype=torch.int32, device=disc.device) for _ in range(2)] if want_ranks else [None, None]
+        _lib.call("ps_rank_select_groups", disc, entr, groups, n, gs, cs, best, *ranks)
+    return (best, *ranks) if want_ranks else best
+
+
+def take_groups(src, best, n, layout="candidate_major"):
+    """src (groups * n, ...) fp32 on the device, best (groups,) int32 on the device (select_groups': an index outside 0 .. n-1 is
+    clamped into it) -> (groups, *src.shape[1:]): item best[g] of every group; one launch, the indices are read where they are"""
+    _lib.require_cuda(src, best)
+    if src.dtype != torch.float32 or src.dim() < 1 or best.dtype != torch.int32 or best.dim() != 1:
+        raise ValueError(f"take_groups: expected fp32 items and a 1-d int32 index, got {tuple(src.shape)} {src.dtype} and "
+                         f"{tuple(best.shape)} {best.dtype}")
+    src, best, groups = src.contiguous(), best.contiguous(), best.shape[0]
+    gs, cs = group_strides(groups, n, layout)
+    item = src[0].numel() if src.shape[0] else 0
+    if not (1 <= n <= MAX_N and 1 <= groups <= MAX_GROUPS) or src.shape[0] != groups * n or item < 1:
+        raise ValueError(f"take_groups: expected groups * n non-empty items with n in 1 .. {MAX_N} and groups in 1 .. {MAX_GROUPS}, got "
+                         f"{groups} indices, n = {n} and items {tuple(src.shape)}")
+    with torch.cuda.device(src.device):
+        out = torch.empty((groups,) + tuple(src.shape[1:]), dtype=torch.float32, device=src.device)
+        _lib.call("ps_rank_take_groups", src, best, groups, n, gs, cs, item, out)
+    return out
+
+
 # ---------------------------------------------------------------- the two scorers on a batch of candidates
 def _discriminator(netD):
     """The multiscale discriminator module inside pixelsynth_amd.losses.DiscriminatorLoss (or the reference's class), its loss object"""
@@ -216,14 +281,30 @@ def can_score_on_device(netD, classifier, imgs=None):
 
 
 @torch.no_grad()
-def score_candidates(imgs, netD, classifier):
+def score_candidates(imgs, netD, classifier, chunk=None):
     """imgs (N,3,S,S) fp32 on the device -> (disc (N,), entr (N,)) fp32 device tensors, the scores get_best_sample ranks with; nothing
     comes down to the host.  One classifier_input launch, one forward of the classifier on the N inputs, one entropy launch; one
     forward of the multiscale discriminator on the N candidates alone (every layer of it works per sample, and the input image's half
-    of the host route's batch is read by nobody), one hinge_fake launch."""
+    of the host route's batch is read by nobody), one hinge_fake launch.
+    chunk: None -- the single pass above (the B = 1 route).  A number: the passes run on at most `chunk` candidates at a time and the
+    score vectors are concatenated (a candidate's scores do not depend on its neighbours: every layer works per sample).  It is a cap
+    on memory, not a tuning knob: the N * B candidates of per-view ranking, 50 x 16 say, would put several GB into the discriminator's
+    first layers at once (64 channels of 128 x 128 fp32 per candidate and layer: 4 MB each, 0.27 GB at 64 candidates, 3.4 GB at 800).
+    The per-view route passes opt.rank_chunk, SCORE_CHUNK = 64 where it is unset -- a figure chosen from these activation sizes, not
+    measured."""
+    if chunk is not None and int(chunk) < 1:
+        raise ValueError(f"score_candidates: chunk = {chunk}, expected >= 1 (or None: one pass)")
     if not can_score_on_device(netD, classifier, imgs):
         raise RuntimeError("score_candidates: needs netD.netD.netD with a hinge GANLoss, a classifier module and (N,3,S,S) fp32 "
                            "candidates on the GPU (can_score_on_device); there is no fallback here")
+    if chunk is None or imgs.shape[0] <= int(chunk):
+        return _score_pass(imgs, netD, classifier)
+    parts = [_score_pass(imgs[s:s + int(chunk)], netD, classifier) for s in range(0, imgs.shape[0], int(chunk))]
+    return torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts])
+
+
+def _score_pass(imgs, netD, classifier):
+    """score_candidates' single pass on candidates it has checked"""
     entr = entropy(classifier(classifier_input(imgs)).float())
     disc, _ = _discriminator(netD)
     maps = [p[-1] if isinstance(p, (list, tuple)) else p for p in disc(imgs)]   # the last entry of every scale counts (GANLoss)

@@ -55,6 +55,26 @@ def _rank_route(rank_on, opt):
     return route
 
 
+RANK_SCOPES = ("batch", "view")
+
+
+def _rank_scope(rank_scope, opt):
+    """rank_scope of get_best_sample -> "batch" (one winner index for the whole batch: the reference's rule) / "view" (the best
+    candidate of every view); None: opt.rank_scope, then the environment variable PS_RANK_SCOPE (read per call), batch by default"""
+    scope = rank_scope if rank_scope is not None else getattr(opt, "rank_scope", None)
+    if scope is None:
+        scope = os.environ.get("PS_RANK_SCOPE", "batch")
+    if scope not in RANK_SCOPES:
+        raise ValueError(f"get_best_sample: rank_scope / opt.rank_scope / PS_RANK_SCOPE is {scope!r}, expected one of {RANK_SCOPES}")
+    return scope
+
+
+def view_draws(n, B, L):
+    """(n, B, L) uniforms on the host for n candidates of B views: entry [i, b] is the (1, L) draw of manual_seed(i) for every b -- a
+    view gets the draws of a B = 1 run, never row b of a (B, L) draw: it is the same picture alone or in a batch"""
+    return torch.stack([torch.rand(1, L, generator=torch.Generator(device="cpu").manual_seed(i)).expand(B, L) for i in range(n)])
+
+
 class _SceneState:
     """What forward_scene carries from one rendered frame to the next (z_buffermodel.py:436-443)."""
 
@@ -512,7 +532,8 @@ class ZbufferModelPts(nn.Module):
         if max(int(getattr(self.opt, "num_samples", 1)), 1) > 1:   # :349 -> get_best_sample with opt.num_samples candidates
             plan = self.get_masks_for_batch(output_RT, input_RTinv, background_mask, compact=True)
             outputs["PredImg"] = self.get_best_sample(plan, downsampled_fs, background_mask, gen_fs, netD, input_img,
-                                                      shard=bool(getattr(self.opt, "shard_samples", False)), rank_on=rank_on)
+                                                      shard=bool(getattr(self.opt, "shard_samples", False)), rank_on=rank_on,
+                                                      rank_scope=getattr(self.opt, "rank_scope", None))
             return None, outputs
         masks_init, masks_undilated, masks_dilated, gen_order = self.get_masks_for_batch(output_RT, input_RTinv,
                                                                                          background_mask)
@@ -553,7 +574,7 @@ class ZbufferModelPts(nn.Module):
         return x if self.projector is None else checked(x.device, lambda: self.projector(x, *mask))
 
     @torch.no_grad()
-    def get_best_sample(self, *args, uniforms=None, shard=False, rank_on=None):
+    def get_best_sample(self, *args, uniforms=None, shard=False, rank_on=None, rank_scope=None):
         """z_buffermodel.py:244-276 on the fused sampler: num_samples outpaintings of the same view, the best by
         discriminator + entropy rank is kept.  Two call forms:
           get_best_sample(gen_order, masks, downsampled_fs, background_mask, gen_fs, netD, input_img)   the reference's (:244),
@@ -570,10 +591,19 @@ class ZbufferModelPts(nn.Module):
         where they are (ranking.score_candidates), the rank rule runs there too and the winner comes back through index_select -- no
         score comes down (under `shard`: the two vectors of a rank's own candidates, once).  It applies where ranking.can_score_on_device
         holds and B = 1; any other scorer, stand-ins included, takes the host route.  None: opt.rank_on, then the environment variable
-        PS_RANK, "host" where neither is set."""
+        PS_RANK, "host" where neither is set.
+        rank_scope "batch": the above -- with B > 1 views the host route averages the discriminator's score over the batch and takes the
+        entropy of view 0, so the batch gets ONE winner index (the reference's rule).  rank_scope "view", with B > 1 and num_samples > 1:
+        every view keeps the best of ITS candidates.  Candidate i of every view is drawn as a B = 1 run draws it (view_draws); the
+        candidates are decoded as above, B views per call, stacked candidate-major to (num_samples * B,3,S,S), scored in chunks
+        (ranking.score_candidates, opt.rank_chunk), ranked per view (ranking.select_groups) and every view's winner is handed over
+        (ranking.take_groups) -> (B,3,S,S); no score and no index comes down.  This route exists on the device alone: it needs
+        ranking.can_score_on_device and rank_on unset or "device" (NotImplementedError otherwise), and does not shard (ValueError).
+        None: opt.rank_scope, then the environment variable PS_RANK_SCOPE, "batch" where neither is set."""
         from . import distributed as D
         from . import ranking
         route = _rank_route(rank_on, self.opt)
+        scope = _rank_scope(rank_scope, self.opt)
         if isinstance(args[0], ARPlan):
             plan, codes, background_mask, gen_fs, netD, input_img = args
         else:
@@ -586,6 +616,16 @@ class ZbufferModelPts(nn.Module):
         B, G = codes.shape[0], self.obs[1]
         L = G * self.obs[2]
         dev = codes.device
+        per_view = scope == "view" and B > 1 and n > 1
+        if per_view:
+            if shard:
+                raise ValueError("get_best_sample: rank_scope='view' does not shard its candidates over the ranks (shard=True)")
+            asked = rank_on if rank_on is not None else getattr(self.opt, "rank_on", None) or os.environ.get("PS_RANK")
+            if asked == "host" or not ranking.can_score_on_device(netD, self.classifier):
+                raise NotImplementedError(f"get_best_sample: num_samples = {n} with rank_scope='view' and B = {B} ranks on the device alone: "
+                                          "it needs scorers that ranking.can_score_on_device accepts and rank_on unset or 'device'")
+            if uniforms is None:
+                uniforms = view_draws(n, B, L).to(dev)
         if uniforms is None:
             uniforms = torch.stack([torch.rand(B, L, generator=torch.Generator(device="cpu").manual_seed(i)) for i in range(n)]).to(dev)
         rank, world = D.world()
@@ -612,6 +652,8 @@ class ZbufferModelPts(nn.Module):
             for j, i in enumerate(idx):
                 img = self._decode_checked(gen_fs, background_mask, c[j * B:(j + 1) * B].view(B, G, self.obs[2]))
                 imgs[i] = img
+                if per_view:
+                    continue
                 if n > 1 and on_device is None:
                     on_device = route == "device" and B == 1 and ranking.can_score_on_device(netD, self.classifier, img)
                 if n > 1 and not on_device:
@@ -619,6 +661,14 @@ class ZbufferModelPts(nn.Module):
                     entr.append(self._entropy_score(img))
         if n == 1:
             return imgs[0]
+        if per_view:
+            stack = torch.cat([imgs[i] for i in range(n)])          # candidate-major: candidate i of view b at i * B + b
+            if not ranking.can_score_on_device(netD, self.classifier, stack):
+                raise NotImplementedError(f"get_best_sample: num_samples = {n} with rank_scope='view': ranking.can_score_on_device does "
+                                          f"not take candidates of shape {tuple(stack.shape)} {stack.dtype}")
+            chunk = getattr(self.opt, "rank_chunk", None) or ranking.SCORE_CHUNK      # (a cap on the scorers' memory)
+            disc_dev, entr_dev = ranking.score_candidates(stack, netD, self.classifier, chunk)
+            return ranking.take_groups(stack, ranking.select_groups(disc_dev, entr_dev, B, n), n)
         if on_device:
             stack = torch.cat([imgs[i] for i in mine])
             disc_dev, entr_dev = ranking.score_candidates(stack, netD, self.classifier)
@@ -656,12 +706,11 @@ class ZbufferModelPts(nn.Module):
             gen_fs, background_mask = self._scene_step_batched(st, fs, depth, K, K_inv, in_RT, in_RTinv, out_RT, out_RTinv)
             # a scene is the same picture alone or in a batch: every scene gets the draws of a B = 1 run (candidate i: the (1, L)
             # draw of manual_seed(i)), never row b of a (B, L) draw
-            L = self.obs[1] * self.obs[2]
-            uniforms = torch.rand(1, L, generator=torch.Generator(device="cpu").manual_seed(0)).expand(1, B, L).to(gen_fs.device)
+            uniforms = view_draws(max(int(getattr(self.opt, "num_samples", 1)), 1), B, self.obs[1] * self.obs[2]).to(gen_fs.device)
         if not getattr(self.opt, "no_outpainting", False):
             plan = build_ar_plan(background_mask, self.obs[1], count_background=B > 1)
             gen_img = self.get_best_sample(plan, self.vqvae.encode_codes(gen_fs), background_mask, gen_fs, netD, input_img,
-                                           uniforms=uniforms)
+                                           uniforms=uniforms, rank_scope="view" if B > 1 else None)   # (a batch of scenes ranks per scene)
         else:
             gen_img = self._project_checked(gen_fs)
         st.img, st.cloud, st.feats, st.background, st.out_RTinv = gen_img, cloud, feats, background_mask, out_RTinv
@@ -699,8 +748,10 @@ class ZbufferModelPts(nn.Module):
         B = 1 runs as the reference does (a5 with boolean gathers, which need equal counts per image).  B > 1 -- images (B,3,S,S),
         cameras (B,4,4), for gen_two_imgs a (B,) "direction" -- advances B INDEPENDENT scenes one frame per step together, their
         clouds of different lengths kept on the device (_scene_step_batched); poses are built per scene and stacked, and slice b of
-        every output equals the B = 1 run of scene b.  With per-scene directions (gen_two_imgs) a value is stored under the key of
-        every direction in the batch: slice b is scene b's under ITS direction's keys.
+        every output equals the B = 1 run of scene b; with num_samples > 1 every scene keeps the best of its own candidates at every
+        frame (get_best_sample's rank_scope="view": scorers that ranking.can_score_on_device accepts are needed).  With per-scene
+        directions (gen_two_imgs) a value is stored under the key of every direction in the batch: slice b is scene b's under ITS
+        direction's keys.
         -> (None, outputs) with the reference's keys PredImg_<dir>_<i>, FeaturesImg_..., PredDepthImg_..., ForegroundImg_...
         (ForegroundImg_* (B,1,S,S))."""
         dev = next(self.parameters()).device   # (the renderer itself refuses anything but the GPU)
@@ -713,8 +764,11 @@ class ZbufferModelPts(nn.Module):
             directions = [self.mapping[int(batch["direction"])]] if two else list(self.opt.directions)
         else:
             if max(int(getattr(self.opt, "num_samples", 1)), 1) > 1:
-                raise NotImplementedError("forward_scene with B > 1 renders one sample per frame (num_samples ranks candidates over the "
-                                          "whole batch): use num_samples = 1 or B = 1")
+                from . import ranking
+                if netD is None or self.classifier is None or not ranking.can_score_on_device(netD, self.classifier):
+                    raise NotImplementedError("forward_scene with B > 1 and num_samples > 1 ranks every scene's own candidates, which it "
+                                              "does on the device alone: it needs netD and a classifier that ranking.can_score_on_device "
+                                              "accepts -- or use num_samples = 1 or B = 1")
             if any(v.shape[0] != B for v in (K, K_inv, input_RT, input_RTinv)):
                 raise ValueError(f"forward_scene: {B} images need (B,4,4) cameras")
             if two:   # one sweep, every scene in its own direction

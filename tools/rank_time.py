@@ -4,6 +4,9 @@ rank_on="device" (ranking.score_candidates + ranking.select: one batch, nothing 
 timing) -- on the scorer mirrors with synthetic weights.
 
     python tools/rank_time.py [N ...]        (default: 4 16 50)
+    python tools/rank_time.py --views B [N ...]   per-view ranking of N x B candidates (ranking.score_candidates in chunks,
+                                                  select_groups, take_groups: get_best_sample's rank_scope="view") against B calls of
+                                                  the B = 1 device route above, one per view; each ends at a synchronised device
 
 The N candidates (256 x 256, U(-1,1)) are made once, outside the timed part: decoding is the same on both routes and is not measured.
 Per route: WARM invocations, then CALLS timed ones, each from a synchronised device to the winner's index on the host; the routes
@@ -57,10 +60,59 @@ def device_route(cands, netD, classifier):
     return int(best), disc, entr
 
 
+def per_view_route(stack, views, N, netD, classifier):
+    """get_best_sample's rank_scope="view" lines on the decoded (N * views,3,S,S) candidate-major stack -> (winners (views,3,S,S), disc, entr)"""
+    disc, entr = ranking.score_candidates(stack, netD, classifier, ranking.SCORE_CHUNK)
+    return ranking.take_groups(stack, ranking.select_groups(disc, entr, views, N), N), disc, entr
+
+
+def time_views(views, counts, device, netD, classifier):
+    """--views: N x B candidates ranked per view in one go against B calls of the B = 1 device route; one JSON line per N"""
+    for N in counts:
+        stack = torch.cat([torch.from_numpy(syn.image(100 + i, views, 3, 256)) for i in range(N)]).to(device)   # candidate-major
+        alone = [[stack[i * views + b:i * views + b + 1] for i in range(N)] for b in range(views)]
+        wall, last = {"per_view": [], "one_by_one": []}, {}
+        for rep in range(WARM + CALLS):
+            for route in wall:
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                if route == "per_view":
+                    last[route] = per_view_route(stack, views, N, netD, classifier)
+                else:
+                    last[route] = [device_route(c, netD, classifier) for c in alone]
+                torch.cuda.synchronize()
+                t1 = time.perf_counter()
+                if rep >= WARM:
+                    wall[route].append(1e3 * (t1 - t0))
+        stat = lambda x: [round(float(f(x)), 3) for f in (np.min, np.median, np.max)]
+        winners, disc, entr = last["per_view"]
+        want = [r[0] for r in last["one_by_one"]]
+        same = sum(bool(torch.equal(winners[b], stack[want[b] * views + b])) for b in range(views))
+        diff = [max(float((last["per_view"][k].view(N, views)[:, b] - last["one_by_one"][b][k]).abs().max()) for b in range(views))
+                for k in (1, 2)]
+        rec = dict(N=N, views=views, calls=CALLS, chunk=ranking.SCORE_CHUNK, per_view_wall_ms=stat(wall["per_view"]),
+                   one_by_one_wall_ms=stat(wall["one_by_one"]), max_abs_diff_disc=diff[0], max_abs_diff_entropy=diff[1],
+                   same_winners=same, cpus=len(os.sched_getaffinity(0)))
+        print("N=%d views=%d  scoring + ranking wall per invocation (min / median / max of %d): per view %.2f / %.2f / %.2f ms, %d calls of "
+              "the B = 1 device route %.2f / %.2f / %.2f ms; largest difference of a score: D_Fake %.3g, entropy %.3g; %d of %d winners alike"
+              % (N, views, CALLS, *rec["per_view_wall_ms"], views, *rec["one_by_one_wall_ms"], diff[0], diff[1], same, views))
+        print(json.dumps(rec), flush=True)
+
+
 def main(argv):
-    counts = [int(a) for a in argv] or [4, 16, 50]
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("counts", nargs="*", type=int, metavar="N", help="candidates per view (default: 4 16 50)")
+    ap.add_argument("--views", type=int, metavar="B", help="rank N x B candidates per view against B calls of the B = 1 device route")
+    args = ap.parse_args(argv)
+    counts = args.counts or [4, 16, 50]
     device = torch.device("cuda", 0)
     netD, classifier = scorers(device)
+    if args.views is not None:
+        if args.views < 1:
+            ap.error("--views must be >= 1")
+        with torch.no_grad():
+            time_views(args.views, counts, device, netD, classifier)
+        return
     holder = type("H", (), {"classifier": classifier, "_entropy_score": ZbufferModelPts._entropy_score})()
     real = torch.from_numpy(syn.image(31, 1, 3, 256)).to(device)
     with torch.no_grad():
