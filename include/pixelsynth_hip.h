@@ -80,7 +80,8 @@ size_t ps_splat_workspace_bytes(int B, int N, int S, double radius_px);
  *   Numerics: out_bg and the debug outputs are exact (the K nearest hits per pixel in (z, index) order).  out_feat under
  *   PS_ACC_ALPHACOMPOSITE WITHOUT debug outputs: a pixel's front-to-back walk stops once its transmittance prod(1 - alpha) is below
  *   2^-23 -- the hits behind can add at most that times max |feature| (below one ulp of a unit-magnitude result; the parity tests
- *   state 1e-6) --, a hit's alpha comes from the hardware's 1-ulp square root and the sum cum * alpha * feature is one fused multiply-add
+ *   state 1e-6) --, a hit's alpha comes from the hardware's 1-ulp square root (at tau = 1; the correctly rounded one at tau != 1, where
+ *   the power magnifies an ulp of the root) and the sum cum * alpha * feature is one fused multiply-add
  *   (together <= 3e-7 x max |feature| from the exact walk, measured); with debug outputs, and in the other accumulation modes, every one of
  *   the K hits is walked with the correctly rounded root and separately rounded product and sum (the bit-exact route). */
 int ps_splat_f32(float *pts, const float *feat, int B, int N, int C, int S, double radius_px, int K,

@@ -501,7 +501,8 @@ struct __attribute__((aligned(16))) SplatRec { float x, y, z; uint32_t n; float 
 
 // NC: channels a wave carries -- CG, or 3 when the features have exactly three (RGB: every configuration of the reference): the
 // fourth accumulator of a group of four costs one LDS read and two vector instructions per hit of a walk of ~46
-template <int MODE, bool DEBUG_OUT, bool RECIP, int NC = CG>
+// EXACT_ROOT: the product route with the correctly rounded root (the host asks for it when tau != 1, see the root below)
+template <int MODE, bool DEBUG_OUT, bool RECIP, int NC = CG, bool EXACT_ROOT = false>
 __attribute__((amdgpu_waves_per_eu(PS_COMPOSITE_WAVES, PS_COMPOSITE_WAVES)))
 __global__ __launch_bounds__(64) void k_composite(
     const uint64_t *__restrict__ keys, const uint32_t *__restrict__ tile_off,
@@ -638,11 +639,15 @@ __global__ __launch_bounds__(64) void k_composite(
                 const float d2 = dx * dx + dy * dy;
                 float d = RECIP ? d2 * denom : d2 / denom;
                 d = __builtin_amdgcn_fmed3f(d, 1e-3f, 1.0f);   // = fminf(fmaxf(d, 1e-3f), 1.0f) for every d that is a number, one instruction
-                // The product route (EARLY) takes the hardware's square root as it comes (1 ulp; sqrt_rn_unit's correction is 7 of the walk's
-                // ~38 vector instructions): with the early-out and the fused sum the features stay within 3e-7 x max |feature| of the
-                // oracle's (measured on pile-ups and image-like clouds; 1.8e-7 with the exact root), inside the 1e-6 the parity tests
-                // state.  The list-emitting route -- the one the bit-exact checks go through -- keeps the correctly rounded root.
-                float a = 1.0f - (EARLY ? __builtin_amdgcn_sqrtf(d) : sqrt_rn_unit(d));
+                // The product route (EARLY) at tau = 1 takes the hardware's square root as it comes (1 ulp; sqrt_rn_unit's correction is 7 of
+                // the walk's ~38 vector instructions): with the early-out and the fused sum the features stay within 3e-7 x max |feature|
+                // of the oracle's (measured AT TAU = 1 on pile-ups and image-like clouds; 1.8e-7 with the exact root), inside the 1e-6 the
+                // parity tests state.  At tau != 1 the host picks EXACT_ROOT: a = 1 - root goes through powf, and for tau < 1 the
+                // derivative tau a^(tau - 1) is unbounded where a -> 0, a hit at the rim of its disc -- one ulp of the root moves such an
+                // alpha by up to 3.6e-5.  Measured on the device at tau = 0.5 (S = 40 / 64, r = 4 px, K = 16 / 32) against the oracle:
+                // 1.35e-6 / 8.3e-7 x max |feature| with the hardware root, outside both figures above; at tau = 2, 2.1e-7 either way.
+                // The list-emitting route -- the one the bit-exact checks go through -- always keeps the correctly rounded root.
+                float a = 1.0f - (EARLY && !EXACT_ROOT ? __builtin_amdgcn_sqrtf(d) : sqrt_rn_unit(d));
                 if (tau != 1.0f) a = powf(a, tau);
                 if (MODE == PS_ACC_WSUMNORM && pass == 0) {
                     tsum = tsum + a;
@@ -790,16 +795,24 @@ SplatPlan make_plan(int B, int N, int S, double radius_px)
 }
 
 template <int MODE>
-void launch_composite(bool debug, bool recip, dim3 grid, hipStream_t st, const uint64_t *keys,
+void launch_composite(bool debug, bool recip, bool exact_root, dim3 grid, hipStream_t st, const uint64_t *keys,
                       const uint32_t *tile_off, const float *pts, const float *feat, int N, int C,
                       int S, int tilesX, int NT, float r2, float denom, float tau, int K,
                       float *out_feat, uint8_t *bg0, int32_t *out_idx, float *out_zbuf,
                       float *out_dist)
 {
-#define PS_COMPOSITE(DBG, RCP, NCH)                                                                \
-    hipLaunchKernelGGL((k_composite<MODE, DBG, RCP, NCH>), grid, dim3(64), 0, st, keys, tile_off,  \
-                       pts, feat, N, C, S, tilesX, NT, r2, denom, tau, K, out_feat, bg0, out_idx,  \
+#define PS_COMPOSITE(DBG, RCP, ...)                                                                       \
+    hipLaunchKernelGGL((k_composite<MODE, DBG, RCP, __VA_ARGS__>), grid, dim3(64), 0, st, keys, tile_off, \
+                       pts, feat, N, C, S, tilesX, NT, r2, denom, tau, K, out_feat, bg0, out_idx,         \
                        out_zbuf, out_dist)
+    // (only the product route of the alpha compositing ever takes the hardware root: the one place EXACT_ROOT changes code)
+    if constexpr (MODE == PS_ACC_ALPHACOMPOSITE) {
+        if (!debug && exact_root) {
+            if (C == 3) { if (recip) PS_COMPOSITE(false, true, 3, true); else PS_COMPOSITE(false, false, 3, true); }
+            else        { if (recip) PS_COMPOSITE(false, true, CG, true); else PS_COMPOSITE(false, false, CG, true); }
+            return;
+        }
+    }
     if (debug) { if (recip) PS_COMPOSITE(true, true, CG); else PS_COMPOSITE(true, false, CG); }
     else if (C == 3) { if (recip) PS_COMPOSITE(false, true, 3); else PS_COMPOSITE(false, false, 3); }
     else       { if (recip) PS_COMPOSITE(false, true, CG); else PS_COMPOSITE(false, false, CG); }
@@ -846,15 +859,15 @@ int splat_core(const float *pts, const float *feat, int B, int N, int C, int S, 
     const bool debug = out_idx || out_zbuf || out_dist;
     switch (accumulation) {
     case PS_ACC_ALPHACOMPOSITE:
-        launch_composite<PS_ACC_ALPHACOMPOSITE>(debug, pow2, gc, st, keys, tile_off, pts, feat, N, C, S, p.tilesX,
+        launch_composite<PS_ACC_ALPHACOMPOSITE>(debug, pow2, tau != 1.0f, gc, st, keys, tile_off, pts, feat, N, C, S, p.tilesX,
                                                 p.NT, r2, denom_arg, tau, K, out_feat, bg0, out_idx, out_zbuf, out_dist);
         break;
     case PS_ACC_WSUM:
-        launch_composite<PS_ACC_WSUM>(debug, pow2, gc, st, keys, tile_off, pts, feat, N, C, S, p.tilesX, p.NT, r2,
+        launch_composite<PS_ACC_WSUM>(debug, pow2, tau != 1.0f, gc, st, keys, tile_off, pts, feat, N, C, S, p.tilesX, p.NT, r2,
                                       denom_arg, tau, K, out_feat, bg0, out_idx, out_zbuf, out_dist);
         break;
     default:
-        launch_composite<PS_ACC_WSUMNORM>(debug, pow2, gc, st, keys, tile_off, pts, feat, N, C, S, p.tilesX, p.NT,
+        launch_composite<PS_ACC_WSUMNORM>(debug, pow2, tau != 1.0f, gc, st, keys, tile_off, pts, feat, N, C, S, p.tilesX, p.NT,
                                           r2, denom_arg, tau, K, out_feat, bg0, out_idx, out_zbuf, out_dist);
         break;
     }

@@ -159,7 +159,9 @@ def test_accumulation_modes(acc, tau, tol):
 
 
 def test_many_channels_and_rad_pow():
-    """C=7 (two channel groups) and a non power-of-two radius (true division path)."""
+    """C=7 (two channel groups, the second with three channels) through the debug route.  The radius 2 * 3 / 24 = 0.25 gives a
+    power-of-two denominator, so this is the reciprocal path, at rad_pow = 2; true division and rad_pow != 2 are cases of
+    tests/test_splat_routes_gpu.py."""
     from pixelsynth_amd.layers.z_buffer_layers import RasterizePointsXYsBlending
     S, N, K = 24, 800, 8
     pts = cloud(13, 1, N)

@@ -1,0 +1,72 @@
+"""GPU: the binning, sort and composite routes of pixelsynth_amd/csrc/splat.hip that the parity tests of test_splat_gpu.py never take, on
+the cases of tests/_splat_ref.py (tests/test_splat_routes_cpu.py asserts, without a GPU, that every case reaches its branch).
+
+Debug route (return_debug=True): idx, zbuf, dist, the background mask and the negated points bit-exact against the C oracle, features at
+the tolerance test_splat_gpu.py:test_accumulation_modes states (_splat_ref.debug_tol).
+Product route (what forward_justpts and the benchmark run): the mask bit-exact; wsum / wsumnorm features equal, bit for bit, to the debug
+route's of the same call (the templates differ in what they write and in the channels a wave carries, not in arithmetic); alphacomposite
+features within  E_ref + 4e-7 x max |feature|  of the float64 compositing of the oracle's hit lists, E_ref the fp32 oracle's own distance
+from it on the same inputs (_splat_ref.composite64)."""
+import numpy as np
+import pytest
+import torch
+
+import _splat_ref as R
+from test_splat_gpu import check, dev, make_splatter
+
+pytestmark = pytest.mark.gpu
+
+
+def splatter(c):
+    return make_splatter(c.S, c.K, c.r, tau=c.tau, rad_pow=c.rad_pow, accumulation=c.acc, background_smoothing_kernel_size=c.ksize)
+
+
+def run(c, pts, feat, debug):
+    """One call of the splat on fresh device copies (it negates x, y of its points in place) -> dict of numpy arrays"""
+    tp, tf = torch.tensor(pts, device=dev()), torch.tensor(feat, device=dev())
+    res = splatter(c)(tp, tf, return_debug=debug)
+    torch.cuda.synchronize()
+    got = dict(zip(("feat", "bg", "idx", "zbuf", "dist"), (t.cpu().numpy() for t in res)))
+    got["pts_after"] = tp.cpu().numpy()
+    return got
+
+
+@pytest.mark.parametrize("c", [c for c in R.CASES if c.route in ("debug", "both")], ids=lambda c: c.id)
+def test_debug_route_vs_oracle(c):
+    pts, feat, ref, _, _ = R.reference(c)
+    check(run(c, pts, feat, True), ref, feat_tol=R.debug_tol(c))
+
+
+@pytest.mark.parametrize("c", [c for c in R.CASES if c.route in ("product", "both")], ids=lambda c: c.id)
+def test_product_route_vs_float64(c):
+    """Two bars for the alphacomposite cases, both as multiples of max |feature|:
+      err   = max |gpu - composite64| <= E_ref + 4e-7     (E_ref = max |oracle_fp32 - composite64|, computed here on the same inputs)
+      err32 = max |gpu - oracle_fp32| <= 4e-7             (the allowance as test_splat_gpu.py states it: the early-out at 2^-23
+                                                           transmittance, the fused multiply-add and, at tau = 1, the 1-ulp root)
+    Measured on an MI355X over the sixteen cases: E_ref 1.3e-7 ... 1.0e-6, err 1.2e-7 ... 9.9e-7 (the largest of both at tau = 0.5,
+    S = 64: E_ref 1.01e-6, err 9.92e-7), err32 1.2e-7 ... 2.4e-7.  At tau = 0.5 the kernel took the hardware's 1-ulp root until this
+    test: err32 was 1.35e-6 (S = 40) and 8.3e-7 (S = 64) -- inside the first bar only through E_ref, outside the second; with the
+    correctly rounded root the host now picks at tau != 1 (k_composite's EXACT_ROOT) 1.8e-7 and 2.4e-7.  docs/LAB_NOTEBOOK.md has the
+    table per case."""
+    pts, feat, ref, c64, e_ref = R.reference(c)
+    got = run(c, pts, feat, False)
+    assert np.array_equal(got["bg"], ref["bg"])
+    assert np.array_equal(got["pts_after"], ref["pts_after"], equal_nan=True)
+    fmax = float(np.abs(feat).max())
+    if c.acc != "alphacomposite":
+        dbg = run(c, pts, feat, True)
+        assert np.array_equal(got["feat"], dbg["feat"]) and np.array_equal(got["bg"], dbg["bg"])
+        return
+    err, err32 = float(np.abs(got["feat"] - c64).max()), float(np.abs(got["feat"] - ref["feat"]).max())
+    bar = e_ref + R.PRODUCT_ALLOWANCE * fmax
+    print(f"{c.id}: max |feature| = {fmax:.4g}, E_ref = {e_ref:.3g}, err = {err:.3g}, bar = {bar:.3g}, "
+          f"err vs the fp32 oracle = {err32:.3g}")
+    assert err <= bar, (err, e_ref, bar)
+    # the allowance itself, against the fp32 oracle (the form test_splat_gpu.py states it in): E_ref above is slack the kernel is not owed
+    assert err32 <= R.PRODUCT_ALLOWANCE * fmax, err32
+    if c.branch == "tile_255":
+        # tile coordinate 255 (the top of the 8-bit bbox fields): pixels of the last tile row and column are hit, and carry features
+        hit = ref["idx"][..., 0] >= 0
+        for region in (np.s_[:, -R.TILE:, :], np.s_[:, :, -R.TILE:]):
+            assert hit[region].any() and not got["bg"][region].all()
+            assert np.abs(c64[:, 0][region]).max() > 0.1 * fmax and np.abs(got["feat"][:, 0][region] - c64[:, 0][region]).max() <= bar
