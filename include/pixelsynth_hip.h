@@ -205,7 +205,9 @@ void ps_pixelcnn_destroy(ps_pixelcnn *h);
  *   codes (F,H*W) int32: the class of the one-hot input at each location, -1 = all-zero input
  *   (a not-yet-sampled location, models/lmconv/sample.py:47);
  *   mask_init / mask_undilated / mask_dilated (F,9,H*W) f32 (one copy per image, see above)
- *   -> logits (F,512,H,W) f32. */
+ *   -> logits (F,512,H,W) f32.
+ * Mask values: ANY value, in all three masks.  Like the reference (locally_masked_convolution.py:24-27) the pass multiplies the
+ * unfolded input by whatever the mask holds; a 0 / 1 mask is only the case whose values it need not load. */
 int ps_pixelcnn_forward_f32(ps_pixelcnn *h, const int32_t *codes, const float *mask_init,
                             const float *mask_undilated, const float *mask_dilated, int F,
                             float *logits, void *stream);
@@ -226,6 +228,14 @@ int ps_pixelcnn_forward_f32(ps_pixelcnn *h, const int32_t *codes, const float *m
  *   first_step: order positions < first_step are not walked one by one: they must all be observed
  *   (not in the sample region) in every image, and are covered by one whole-grid pass
  *   (0 is always valid; the caller knows the orders, it built them on the host).
+ * Mask values (this and every ps_pixelcnn_ar_* entry point below): at a location that is walked as a COLUMN -- an order position
+ * >= first_step (>= first_steps[f] with per-frame prefixes), or the `step` of ps_pixelcnn_ar_step -- the values of mask_undilated and
+ * mask_dilated must be exactly 0 or 1, and their centre tap 1.  Masks made from a generation order always are (ps_kernel_masks_f32,
+ * ps_ar_plan, ps_order_masks_f32).  The column kernels take such a tap as open or closed and the centre as open; they do not multiply.
+ * Any other value there, a NaN included, is an argument error that the device flags while it builds the columns' records: the
+ * columns still run, in bounds, on "open or closed", their codes and logits are invalid, and ps_pixelcnn_status reports it.  The
+ * values of mask_init are multiplied by, whatever they are; and so are all three masks at the locations the whole-grid pass covers
+ * (order positions < first_step), as in ps_pixelcnn_forward_f32.
  * Asynchronous on the caller's stream (one launch per order position, enqueued eagerly; see
  * ps_pixelcnn_ar_run_waves for the schedule that needs far fewer dependent launches). */
 int ps_pixelcnn_ar_run(ps_pixelcnn *h, int32_t *codes, const int32_t *order,
@@ -299,7 +309,10 @@ int ps_pixelcnn_ar_step(ps_pixelcnn *h, const int32_t *codes, const int32_t *ord
 /* Inside a column launch the per-frame chains consume results of other workgroups of the same launch; every such
  * wait is bounded, and one that runs out raises a flag in the handle instead of hanging the GPU.  This call
  * synchronises `stream` and returns PS_OK, or an error if any launch since the handle's creation hit that
- * limit (its results are then invalid).  Tests, smoke() and bench.py call it after their runs. */
+ * limit (its results are then invalid).  Tests, smoke() and bench.py call it after their runs.
+ * The same call reports, each with a text of its own (ps_last_error) and all that are raised in one message: a wavefront schedule
+ * that names columns outside its run, and type-B mask values at a walked location that are not 0 / 1 with an open centre (the
+ * mask-value contract at ps_pixelcnn_ar_run).  Every flag is reported once and then cleared; the handle stays usable. */
 int ps_pixelcnn_status(ps_pixelcnn *h, void *stream);
 
 /* Hard z-buffer scatter of DepthManipulator.project_zbuffer (models/projection/depth_manipulator.py:66-104):

@@ -33,6 +33,10 @@
 
 namespace pslm {
 
+// k_ctx_build's flags, in a word of their own beside the column launches' wait-limit flag (h->err[1] / h->err[0]): those launches store a
+// plain 1, which must not erase one of these, nor these that
+enum { CTX_ERR_SCHEDULE = 1, CTX_ERR_MASK_VALUES = 2 };
+
 struct CtxArgs {
     StepCtx *ctx;     // [columns of the run]
     ColTaps *taps;    // [columns of the run] neighbour rows for the throughput form (k_column_tp)
@@ -56,13 +60,20 @@ __global__ __launch_bounds__(32) void k_ctx_build(CtxArgs a, const int32_t *cols
     if (k >= ncols) return;
     int f = cols ? cols[2 * k] : k % a.F, i = cols ? cols[2 * k + 1] : first + k / a.F;
     if (f < 0 || f >= a.F || i < first || i >= a.L) {  // a schedule that does not belong to this run: flag it, stay in bounds
-        if (t == 0) *err = 2;
+        if (t == 0) atomicOr(err, CTX_ERR_SCHEDULE);
         f = 0;
         i = first;
     }
     StepCtx *c = a.ctx + k;
     const int q = a.order[(size_t)f * a.L + i];
-    if (t < 27) c->m[t / 9][t % 9] = a.mask[t / 9][((size_t)f * 9 + t % 9) * a.L + q];
+    if (t < 27) {
+        const float mv = a.mask[t / 9][((size_t)f * 9 + t % 9) * a.L + q];
+        c->m[t / 9][t % 9] = mv;
+        // The column kernels take a type-B tap as open or closed and the centre as open (k_column_tp's neighbour rows below, the chain
+        // roles' centre-tap chains): a walked location whose type-B values say anything else is refused here -- flagged, and the column
+        // still runs in bounds on "open or closed".  (A NaN is neither 0 nor 1.)  The type-A values are multiplied by (uinit_from_codes).
+        if (t >= 9 && !(t % 9 == 4 ? mv == 1.0f : (mv == 0.0f || mv == 1.0f))) atomicOr(err, CTX_ERR_MASK_VALUES);
+    }
     if (t == 27) { c->q = q; c->f = f; }
     if (t < 9) {
         const int loc = ctx_nbr_loc(q, t, H, W);
@@ -515,8 +526,8 @@ int ps_pixelcnn_create(const float *const *params, int n_params, int H, int W, i
         return fail_out(PS_ERR_HIP);
     }
     if ((rc = dev_alloc(h, &h->cnt, 2 * cnt_index(NST, 0)))) return fail_out(rc);
-    if ((rc = dev_alloc(h, &h->err, 1))) return fail_out(rc);
-    if (hipMemset(h->cnt, 0, 2 * cnt_index(NST, 0) * sizeof(unsigned)) != hipSuccess || hipMemset(h->err, 0, sizeof(int)) != hipSuccess) {
+    if ((rc = dev_alloc(h, &h->err, 2))) return fail_out(rc);
+    if (hipMemset(h->cnt, 0, 2 * cnt_index(NST, 0) * sizeof(unsigned)) != hipSuccess || hipMemset(h->err, 0, 2 * sizeof(int)) != hipSuccess) {
         ps::fail(PS_ERR_HIP, "pixelcnn_create: hipMemset failed");
         return fail_out(PS_ERR_HIP);
     }
@@ -558,7 +569,7 @@ int ps_pixelcnn_ar_step(ps_pixelcnn *h, const int32_t *codes, const int32_t *ord
     if (step == first_step) run_grid(h, F, codes, m, nullptr, false, st, order, first_step);
     ChainArgs ca{};
     hipLaunchKernelGGL(k_ctx_build, dim3(F), dim3(32), 0, st, make_ctx_args(h, order, m, F), (const int32_t *)nullptr, F, step,
-                       h->H, h->W, h->err);
+                       h->H, h->W, h->err + 1);
     ca.step_logits = logits;
     ca.temperature = 1.0f;
     run_columns(h, h->ctx, F, codes, ca, st);
@@ -616,7 +627,7 @@ static int ar_run_impl(ps_pixelcnn *h, int32_t *codes, const int32_t *order, con
     const int total = wave_cols ? wave_start[n_waves] : F * nsteps;
     if (total > 0)
         hipLaunchKernelGGL(k_ctx_build, dim3(total), dim3(32), 0, st, make_ctx_args(h, order, m, F), wave_cols, total, first_step,
-                           h->H, h->W, h->err);
+                           h->H, h->W, h->err + 1);
     PS_LAUNCH_CHECK();
     // launches are enqueued eagerly: the host stays far ahead of the GPU (a hipGraph replay was measured slower, and
     // the completion-counter target changes with every launch anyway)
@@ -858,12 +869,18 @@ int ps_pixelcnn_status(ps_pixelcnn *h, void *stream)
 {
     PS_REQUIRE(h, "pixelcnn_status: null handle");
     PS_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
-    int flag = 0;
-    PS_HIP_CHECK(hipMemcpy(&flag, h->err, sizeof(int), hipMemcpyDeviceToHost));
-    if (flag) PS_HIP_CHECK(hipMemset(h->err, 0, sizeof(int)));  // reported once; the handle stays usable
-    if (flag == 2) return ps::fail(PS_ERR_STATE, "pixelcnn: the wavefront schedule names columns outside this run");
-    if (flag) return ps::fail(PS_ERR_STATE, "pixelcnn: a bounded in-launch wait ran out (neighbour slots never arrived)");
-    return PS_OK;
+    int flag[2] = {0, 0};   // [0]: a column launch's wait ran out; [1]: k_ctx_build's CTX_ERR_* bits
+    PS_HIP_CHECK(hipMemcpy(flag, h->err, sizeof(flag), hipMemcpyDeviceToHost));
+    if (!flag[0] && !flag[1]) return PS_OK;
+    PS_HIP_CHECK(hipMemset(h->err, 0, sizeof(flag)));  // reported once; the handle stays usable
+    std::string what;
+    auto add = [&](const char *text) { what += what.empty() ? "" : "; "; what += text; };
+    if (flag[1] & CTX_ERR_SCHEDULE) add("the wavefront schedule names columns outside this run");
+    if (flag[1] & CTX_ERR_MASK_VALUES)
+        add("type-B mask values of a location walked as a column are not 0 / 1 with an open centre (the columns take a tap as open or closed: "
+            "the results of this run are invalid)");
+    if (flag[0]) add("a bounded in-launch wait ran out (neighbour slots never arrived)");
+    return ps::fail(PS_ERR_STATE, "pixelcnn: %s", what.c_str());
 }
 
 int ps_pixelcnn_time_column_step(ps_pixelcnn *h, const int32_t *codes, const int32_t *order, const float *mask_init,
@@ -881,7 +898,7 @@ int ps_pixelcnn_time_column_step(ps_pixelcnn *h, const int32_t *codes, const int
     ca.step_logits = h->col_logits;
     ca.temperature = 1.0f;
     hipLaunchKernelGGL(k_ctx_build, dim3(F), dim3(32), 0, st, make_ctx_args(h, order, Masks{mask_init, mask_undilated, mask_dilated}, F),
-                       (const int32_t *)nullptr, F, step, h->H, h->W, h->err);
+                       (const int32_t *)nullptr, F, step, h->H, h->W, h->err + 1);
     run_columns(h, h->ctx, F, codes, ca, st);  // untimed warm-up
 #ifdef PS_CHAIN_TRACE_BUILD
     if (const char *tp = getenv("PS_CHAIN_TRACE")) {  // tuning builds: per-stage shader-clock stamps of workgroup 0

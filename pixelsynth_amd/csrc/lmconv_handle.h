@@ -148,7 +148,7 @@ struct ps_pixelcnn {
     int32_t *cperm_cnt = nullptr;   // [N_EVAL - 1][maxF] their lengths, per share (a frame range's shares at its first frame on)
     int *ctl1 = nullptr;            // the chain roles' control records
     unsigned *cnt = nullptr;        // [2][NST][MAX_TILES] padded completion counters of the neighbour role, never reset
-    int *err = nullptr;             // device flag: a bounded wait of a column launch ran out
+    int *err = nullptr;             // device flags [2]: a bounded wait of a column launch ran out; k_ctx_build's refusals (CTX_ERR_*, lmconv.hip)
     pslm::NbrWork *work = nullptr;
     int nwork = 0;
     std::vector<int> work_stage;    // stage of every entry of `work` / `work_tp` (entries are stage-major): where a look-ahead depth splits them

@@ -60,7 +60,9 @@ class PixelCNNEngine:
         _lib.call("ps_pixelcnn_create", ptrs, len(arrs), H, W, max_frames, ctypes.byref(self.handle))
 
     def check(self):
-        """Synchronise and raise if any column launch of this engine gave up on an in-launch wait (ps_pixelcnn_status)."""
+        """Synchronise and raise if any column launch of this engine gave up on an in-launch wait, if a schedule named columns outside
+        its run, or if a location walked as a column carried type-B mask values other than 0 / 1 (ps_pixelcnn_status: each reported
+        once; the run's results are invalid, the engine stays usable)."""
         _lib.call("ps_pixelcnn_status", self.handle)
 
     def set_tuning(self, **values):

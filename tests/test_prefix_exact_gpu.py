@@ -136,10 +136,17 @@ def _ar_case(F_, first, fractional):
         reg[b, walked[rs.rand(walked.size) < 0.7]] = 1
         reg[b, order_loc[b][first]] = 1
     masks = [np.concatenate([i[k] for i in infos]).copy() for k in ("mask_init", "mask_undilated", "mask_dilated")]
-    if fractional:   # a third of the open taps of every other frame get a value that is neither 0 nor 1 (open stays open)
+    if fractional:   # a third of the open taps of every other frame get a value that is neither 0 nor 1 (open stays open) -- at the
+        # locations in front of `first` in the frame's order, the ones the prefix pass evaluates: a walked location's type-B values
+        # must stay 0 / 1 (include/pixelsynth_hip.h at ps_pixelcnn_ar_run)
+        prefix = np.zeros((F_, 1, 1024), bool)
+        for b in range(1, F_, 2):
+            prefix[b, 0, order_loc[b][:first]] = True
         for m_ in masks[1:]:
-            scale = np.where(rs.rand(*m_[1::2].shape) < 0.33, 0.25 + 0.5 * rs.rand(*m_[1::2].shape), 1.0).astype(np.float32)
-            m_[1::2] = m_[1::2] * scale
+            scale = np.where(prefix & (rs.rand(*m_.shape) < 0.33), 0.25 + 0.5 * rs.rand(*m_.shape), 1.0).astype(np.float32)
+            open_ = prefix & (m_ > 0)
+            m_ *= scale
+            assert (m_[open_] != 1.0).mean() > 0.2          # (the case cannot silently become a 0 / 1 case)
     ms = [tt(m_) for m_ in masks]
     codes0 = syn.codes(23, F_).reshape(F_, 1024).astype(np.int32)
     u = tt(np.random.RandomState(5).rand(F_, 1024).astype(np.float32))
