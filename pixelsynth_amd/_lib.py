@@ -158,9 +158,15 @@ RANK_GROUPS_PROTOS = {
     "ps_rank_take_groups": (RC, [c_void_p, c_void_p, c_int, c_int, c_long, c_long, c_long, c_void_p, STREAM]),
 }
 
+# libpixelsynth_nll.so (include/pixelsynth_nll.h): the likelihood of given codes under the PixelCNN's logits
+NLL_PROTOS = {
+    "ps_nll_last_error": (ctypes.c_char_p, []),
+    "ps_code_nll_f32": (RC, [c_void_p, c_int, c_void_p, c_void_p, c_double, c_int, c_int] + [c_void_p] * 4 + [STREAM]),
+}
+
 # short name of _libraries.LIBRARIES -> its prototype table; _OWNER: entry point -> the table entry of its library, built once
 PROTOS = {"hip": _PROTOS, "percsim": PERCSIM_PROTOS, "consistency": CONSISTENCY_PROTOS, "fid": FID_PROTOS, "scene": SCENE_PROTOS,
-          "plan": PLAN_PROTOS, "rank": RANK_PROTOS, "rank_groups": RANK_GROUPS_PROTOS}
+          "plan": PLAN_PROTOS, "rank": RANK_PROTOS, "rank_groups": RANK_GROUPS_PROTOS, "nll": NLL_PROTOS}
 _ENTRIES = {e.name: e for e in _libraries.LIBRARIES}
 assert set(PROTOS) == set(_ENTRIES)
 _OWNER = {fn: _ENTRIES[name] for name, table in PROTOS.items() for fn in table}

@@ -7,6 +7,7 @@ create_vid.py for what this repository builds.
     python -m pixelsynth_amd.driver --scene R L --num-split 4 --out results/             (chained, as the reference's gen_scene)
     python -m pixelsynth_amd.driver --scene R L --image-dir imgs/ --batch 16 --out results/   (many chained scenes, 16 at a time)
     python -m pixelsynth_amd.driver --pairs directions.npy --image-dir imgs/ --out views/  (gen_two_imgs: what evaluate --consistency scores)
+    python -m pixelsynth_amd.driver --validate nll.json --image-dir src/ --target-dir tgt/ --trajectory R --out tf/   (teacher-forced)
 
 One source image (a PNG, or the synthetic RealEstate10K-shaped sample), the demo cameras of process_demo_data
 (demo.py:36-96), target poses from ZbufferModelPts.get_rt_from_rot (directions 'R','L','U','D',... in `--frames`
@@ -31,6 +32,15 @@ output_image_<d>_0001.png, output_image_<d>_0002.png -- the views `python -m pix
 networks.resnet18(num_classes=365)) is the reference's quality mode (num_samples 50 of its demo scripts) on the chained paths, --scene
 and --pairs: every frame of every scene keeps the best of N outpaintings, scored and ranked on the device (pixelsynth_amd/ranking.py;
 a batch of scenes ranks per scene).  The circle / trajectory path renders one sample per view.
+
+--validate OUT.json scores held-out pairs instead of drawing anything (ZbufferModelPts.forward_validation, the reference's teacher-forced
+forward, z_buffermodel.py:351-381): source i (--image / --image-dir) with target i, the images of --target-dir in sorted order; the source
+has the demo cameras, the target's pose is the source's turned in the pair's direction at the model's rotation -- --trajectory DIR for
+every pair, or per pair the index of --pairs DIRECTIONS.npy.  In batches of --batch: the target's VQ-VAE codes are scored under the
+PixelCNN in the pair's generation order.  OUT.json gets the numbers of every pair (nats and bits per code, over all, the sampled and the
+observed locations; the accuracy and mean entropy there) and their means over all the pairs' locations; with --out, the teacher-forced
+predictions go to <out>/pred/<i>.png and the targets to <out>/gt/<i>.png, what `python -m pixelsynth_amd.evaluate --pred --gt` reads.
+Nothing is downloaded: the checkpoints are --pixelcnn / --vqvae (random-init stand-ins without them, as everywhere here).
 
 The depth regressor (networks.Unet) and the refinement decoder (networks.get_decoder) are part of the package, and ZbufferModelPts
 builds them from the reference's options (norm_G, refine_model_type); THIS driver builds the model without them and ships no trained
@@ -227,6 +237,94 @@ def run_scenes(model, imgs, cam, groups, out_dir, directions=None, num_split=Non
     return done
 
 
+def validation_setup(args, error):
+    """--validate: the arguments checked before any device is touched -> (source paths, target paths, direction index per pair).
+    error: the parser's (raises SystemExit)."""
+    if args.scene:
+        error("--validate and --scene exclude each other")
+    if args.num_samples != 1:
+        error("--validate draws no sample: --num-samples does not apply")
+    if int(os.environ.get("WORLD_SIZE", 1)) > 1:
+        error("--validate runs on one GPU")
+    if args.batch < 1:
+        error(f"--batch must be >= 1, got {args.batch}")
+    if not args.target_dir:
+        error("--validate needs --target-dir DIR, the target image of every source")
+    try:
+        sources = source_images(args.image, args.image_dir)
+        targets = source_images(None, args.target_dir) if sources else []
+    except (ValueError, OSError) as err:
+        error(str(err).replace("--image-dir " + str(args.target_dir), "--target-dir " + str(args.target_dir)))
+    if not sources:
+        error("--validate needs --image ... or --image-dir, the source images")
+    if len(targets) != len(sources):
+        error(f"--validate: {len(sources)} source images and {len(targets)} images in --target-dir {args.target_dir}: pair i is source i "
+              "and target i, in sorted order")
+    if args.pairs:
+        try:
+            ids = load_directions(args.pairs, len(sources))
+        except (ValueError, OSError) as err:
+            error(str(err))
+    elif args.trajectory in MAPPING:
+        ids = [MAPPING.index(args.trajectory)] * len(sources)
+    else:
+        error(f"--validate: the target's pose is the source's turned in a direction: --trajectory {' | '.join(MAPPING)} (got "
+              f"{args.trajectory!r}) or --pairs DIRECTIONS.npy")
+    return sources, targets, ids
+
+
+def validation_numbers(frames):
+    """A (N,2,4) frames table of likelihood.CodeNLL (any device) -> per row forward_validation's numbers, the mean entropies and the group sizes, as lists of
+    N floats (NaN: a group without a location)"""
+    from .likelihood import CodeNLL
+    s = CodeNLL(None, None, None, frames.detach().double().cpu())
+    cols = {"autoreg_loss": s.mean_nll("all", True), "ar_bits_per_code": s.bits_per_code("all", True),
+            "ar_bits_sampled": s.bits_per_code("sampled", True), "ar_bits_observed": s.bits_per_code("observed", True),
+            "ar_accuracy_sampled": s.accuracy("sampled", True), "ar_entropy_bits_sampled": s.mean_entropy_bits("sampled", True),
+            "ar_entropy_bits_observed": s.mean_entropy_bits("observed", True),
+            "n_sampled": s.sums("sampled", True)[:, 0], "n_observed": s.sums("observed", True)[:, 0]}
+    return {k: v.tolist() for k, v in cols.items()}
+
+
+def validation_report(frames, sources, targets, direction_ids):
+    """The (N,2,4) frames table of N pairs -> what --validate writes: {"pairs": [per pair its files, direction and numbers], "mean":
+    the same numbers over ALL the pairs' locations of a group (for autoreg_loss, 1024 locations a pair, the mean of the pairs'),
+    "count": N}; NaN is written as null"""
+    clean = lambda v: None if v != v else v
+    per = validation_numbers(frames)
+    pooled = validation_numbers(frames.sum(0, keepdim=True))
+    pairs = [dict(index=i, source=sources[i], target=targets[i], direction=MAPPING[direction_ids[i]],
+                  **{k: clean(v[i]) for k, v in per.items()}) for i in range(len(sources))]
+    return {"count": len(pairs), "temperature": 1.0, "mean": {k: clean(v[0]) for k, v in pooled.items()}, "pairs": pairs}
+
+
+@torch.no_grad()
+def run_validation(model, sources, targets, direction_ids, cam, batch, out_dir=None):
+    """forward_validation over the pairs in batches of `batch`: cam the (1,4,4) demo cameras of every source; pair i's target pose is
+    get_rt_from_rot(direction i) of it.  out_dir: PredImg to <out_dir>/pred/<i>.png, the target to <out_dir>/gt/<i>.png.
+    -> the (N,2,4) frames table of the pairs, on the device."""
+    device = cam["P"].device
+    poses = {d: model.get_rt_from_rot(MAPPING[d], cam["P"]) for d in sorted(set(direction_ids))}     # (RTinv, RT)
+    if out_dir:
+        for sub in ("pred", "gt"):
+            os.makedirs(os.path.join(out_dir, sub), exist_ok=True)
+    tables = []
+    for s0 in range(0, len(sources), batch):
+        idx = list(range(s0, min(s0 + batch, len(sources))))
+        B = len(idx)
+        src = torch.cat([load_image(sources[i]) for i in idx]).to(device)
+        tgt = torch.cat([load_image(targets[i]) for i in idx]).to(device)
+        cam0 = {k: v.expand(B, 4, 4).contiguous() for k, v in cam.items()}
+        cam1 = dict(cam0, P=torch.cat([poses[direction_ids[i]][1] for i in idx]), Pinv=torch.cat([poses[direction_ids[i]][0] for i in idx]))
+        loss, outputs = model.forward_validation({"images": [src, tgt], "cameras": [cam0, cam1], "depths": [syn.depth_from_image(src)]})
+        tables.append(loss["ar_frames"])
+        if out_dir:
+            for b, i in enumerate(idx):
+                save_png(os.path.join(out_dir, "pred", f"{i}.png"), outputs["PredImg"][b])
+                save_png(os.path.join(out_dir, "gt", f"{i}.png"), outputs["OutputImg"][b])
+    return torch.cat(tables)
+
+
 _SIDE = {}
 
 
@@ -321,7 +419,10 @@ def main(argv=None):
     ap.add_argument("--sequential", action="store_true", help="--scene: sequential_outpainting")
     ap.add_argument("--frames", type=int, default=64)
     ap.add_argument("--batch", type=int, default=16, help="views (or, with several images, chained scenes) rendered together per rank")
-    ap.add_argument("--out", default="results")
+    ap.add_argument("--out", default=None, help="output directory (default: results; with --validate: no images unless given)")
+    ap.add_argument("--validate", metavar="OUT.json", help="teacher-forced validation of (source, target) pairs: the likelihood of every "
+                                                          "target's codes under the PixelCNN, as JSON")
+    ap.add_argument("--target-dir", help="--validate: a directory of target images, target i (sorted order) for source i")
     ap.add_argument("--pixelcnn", help="state_dict of the reference's OurPixelCNN (torch.save)")
     ap.add_argument("--vqvae", help="state_dict of the reference's VQVAETop (torch.save)")
     ap.add_argument("--num-samples", type=int, default=1, metavar="N", help="--scene / --pairs: outpaintings per frame, the best by "
@@ -333,6 +434,13 @@ def main(argv=None):
         ap.error("--num-samples must be >= 1")
     if args.num_samples > 1 and not (args.discriminator and args.classifier):
         ap.error("--num-samples > 1 ranks candidates with two scorers: give --discriminator PATH and --classifier PATH")
+    if args.target_dir and not args.validate:
+        ap.error("--target-dir goes with --validate OUT.json")
+    if args.validate:
+        sources, targets, ids = validation_setup(args, ap.error)
+        return validate_main(args, sources, targets, ids)
+    if args.out is None:
+        args.out = "results"
     sources = source_images(args.image, args.image_dir)
     many = args.image_dir is not None or len(sources) > 1 or args.pairs is not None
     if many and not (args.scene or args.pairs):
@@ -418,6 +526,25 @@ def main(argv=None):
         print(f"wrote {len(poses) + 1} frames to {vid}/%d.png  (ffmpeg -i {vid}/%d.png ... as create_vid.py does)")
     if world > 1:
         torch.distributed.destroy_process_group()
+
+
+def validate_main(args, sources, targets, ids):
+    """--validate: one GPU, forward_validation over the pairs, OUT.json (and the images under --out)"""
+    import json
+    torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", 0)))
+    device = torch.device("cuda", torch.cuda.current_device())
+    model = build_model(device, args.pixelcnn, args.vqvae)
+    model.opt.model_setting = "gen_paired_img"       # (get_rt_from_rot: the direction at opt.rotation, not a step of a sweep)
+    cam = {k: torch.from_numpy(np.ascontiguousarray(v)).to(device) for k, v in syn.demo_cameras(1).items()}
+    frames = run_validation(model, sources, targets, ids, cam, args.batch, args.out)
+    report = validation_report(frames, sources, targets, ids)
+    folder = os.path.dirname(os.path.abspath(args.validate))
+    os.makedirs(folder, exist_ok=True)
+    with open(args.validate, "w") as fh:
+        json.dump(report, fh, indent=1)
+    m = report["mean"]
+    print(f"{report['count']} pairs: autoreg_loss {m['autoreg_loss']:.4f} nats, {m['ar_bits_per_code']:.4f} bits per code -> {args.validate}"
+          + (f"; teacher-forced predictions -> {args.out}/pred, targets -> {args.out}/gt" if args.out else ""))
 
 
 if __name__ == "__main__":

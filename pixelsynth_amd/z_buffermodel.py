@@ -546,6 +546,58 @@ class ZbufferModelPts(nn.Module):
             outputs["PredImg"] = self._decode_checked(gen_fs, background_mask, codes.to(torch.int64))
         return None, outputs
 
+    # ---------------------------------------------------------------- the likelihood of given codes (z_buffermodel.py:351-381, :398)
+    @torch.no_grad()
+    def autoreg_score(self, plan_or_masks, target_codes, temperature=1.0):
+        """The likelihood the PixelCNN gives to target_codes (B,32,32) in the generation order of plan_or_masks (the compact ARPlan, or
+        the three masks as get_masks_for_batch returns them) -> likelihood.CodeNLL: likelihood.score_codes, the method form."""
+        from .likelihood import score_codes
+        return score_codes(self, target_codes.reshape(-1, self.obs[1], self.obs[2]), plan_or_masks, temperature=temperature)
+
+    @torch.no_grad()
+    def forward_validation(self, batch):
+        """The reference's TEACHER-FORCED forward (z_buffermodel.py:351-381, the 'train' branch of forward_image) without gradients, for
+        a batch that carries the target view as gen_paired_img batches do: images [source, ..., target], cameras [source, ..., target],
+        optional "depths", and "codes" (B,32,32) -- the target's codes -- when the model has no VQ-VAE.  Depth, reprojection + splat and
+        the generation order as forward_image; the target's codes (vqvae.encode_codes(target)) are scored under the PixelCNN in that
+        order (autoreg_score: :358-362), and the decoder sees the reprojected features where visible and the decoded TARGET codes in
+        the background, as a stand-in for the AR output (:372-380).  opt.model_setting is not read.
+        -> (loss, outputs).  outputs: the keys of forward_image -- PredImg is the teacher-forced prediction (with a VQ-VAE), OutputImg
+        the target -- and NLLMap, EntropyMap (B,1,32,32), nats at T = 1, PredCodes the target's codes.  loss, 0-dim fp64 device
+        tensors: autoreg_loss, the mean nats over all B * 1024 locations at T = 1 -- what nn.CrossEntropyLoss() returns at :362 --,
+        ar_bits_per_code, ar_bits_sampled, ar_bits_observed (/ ln 2; NaN for a group without a location), ar_accuracy_sampled; and
+        ar_frames, the (B,2,4) fp64 table of likelihood.CodeNLL.frames, for callers that report per pair."""
+        if len(batch["images"]) < 2 or len(batch["cameras"]) < 2:
+            raise ValueError("forward_validation: the batch carries the target view, images [source, target] and cameras [source, target]")
+        dev = next(self.parameters()).device
+        input_img, output_img = batch["images"][0].to(dev), batch["images"][-1].to(dev)
+        cam = {k: v.to(dev) for k, v in batch["cameras"][0].items() if torch.is_tensor(v)}
+        K, K_inv, input_RT, input_RTinv = cam["K"], cam["Kinv"], cam["P"], cam["Pinv"]
+        output_RT, output_RTinv = batch["cameras"][-1]["P"].to(dev), batch["cameras"][-1]["Pinv"].to(dev)
+        regressed_pts = self.regress_depth(input_img, batch["depths"][0].to(dev) if "depths" in batch else None)
+        fs = input_img if getattr(self.opt, "use_rgb_features", True) else self.encoder(input_img)
+        gen_fs, background_mask = self.pts_transformer.forward_justpts(fs, regressed_pts, K, K_inv, input_RT, input_RTinv, output_RT,
+                                                                      output_RTinv)
+        plan = self.get_masks_for_batch(output_RT, input_RTinv, background_mask, compact=True)
+        if self.vqvae is not None:
+            target_codes = self.vqvae.encode_codes(output_img)
+        elif "codes" in batch:
+            target_codes = batch["codes"].to(dev)
+        else:
+            raise ValueError("forward_validation: no VQ-VAE: the batch must carry the target's codes")
+        B, G = input_img.shape[0], self.obs[1]
+        target_codes = target_codes.reshape(B, G, self.obs[2])
+        score = self.autoreg_score(plan, target_codes)    # (a whole-grid pass alone: no column launch whose status would need reading)
+        outputs = {"InputImg": input_img, "OutputImg": output_img, "PredDepthImg": regressed_pts / 5 - 1,
+                   "ForegroundImg": (~background_mask).repeat(B, 1, 1, 1).float(), "FeaturesImg": gen_fs, "PredCodes": target_codes,
+                   "NLLMap": score.nll.view(B, 1, G, self.obs[2]), "EntropyMap": score.entropy.view(B, 1, G, self.obs[2])}
+        if self.vqvae is not None:
+            outputs["PredImg"] = self._decode_checked(gen_fs, background_mask, target_codes.to(torch.int64))
+        loss = {"autoreg_loss": score.mean_nll("all"), "ar_bits_per_code": score.bits_per_code("all"),
+                "ar_bits_sampled": score.bits_per_code("sampled"), "ar_bits_observed": score.bits_per_code("observed"),
+                "ar_accuracy_sampled": score.accuracy("sampled"), "ar_frames": score.frames}
+        return loss, outputs
+
     # ---------------------------------------------------------------- sample ranking (8f.3, host logic)
     def _entropy_score(self, gen_img):
         """Entropy of the scene classifier on the candidate, including the reference's reinterpretation of the
