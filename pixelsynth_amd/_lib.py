@@ -164,9 +164,17 @@ NLL_PROTOS = {
     "ps_code_nll_f32": (RC, [c_void_p, c_int, c_void_p, c_void_p, c_double, c_int, c_int] + [c_void_p] * 4 + [STREAM]),
 }
 
+# libpixelsynth_lmconv_bwd.so (include/pixelsynth_lmconv_bwd.h): the backward pass of the locally masked convolution
+LMCONV_BWD_PROTOS = {
+    "ps_lmconv_bwd_last_error": (ctypes.c_char_p, []),
+    "ps_lmconv_bwd_workspace_bytes": (c_size_t, [c_int] * 5),
+    "ps_lmconv_grad_weight_f32": (RC, [c_void_p, c_void_p, c_void_p, c_size_t] + [c_int] * 6 + [c_void_p, c_void_p, c_void_p, c_size_t, STREAM]),
+    "ps_lmconv_adjoint_mask_f32": (RC, [c_void_p] + [c_int] * 4 + [c_void_p, STREAM]),
+}
+
 # short name of _libraries.LIBRARIES -> its prototype table; _OWNER: entry point -> the table entry of its library, built once
 PROTOS = {"hip": _PROTOS, "percsim": PERCSIM_PROTOS, "consistency": CONSISTENCY_PROTOS, "fid": FID_PROTOS, "scene": SCENE_PROTOS,
-          "plan": PLAN_PROTOS, "rank": RANK_PROTOS, "rank_groups": RANK_GROUPS_PROTOS, "nll": NLL_PROTOS}
+          "plan": PLAN_PROTOS, "rank": RANK_PROTOS, "rank_groups": RANK_GROUPS_PROTOS, "nll": NLL_PROTOS, "lmconv_bwd": LMCONV_BWD_PROTOS}
 _ENTRIES = {e.name: e for e in _libraries.LIBRARIES}
 assert set(PROTOS) == set(_ENTRIES)
 _OWNER = {fn: _ENTRIES[name] for name, table in PROTOS.items() for fn in table}

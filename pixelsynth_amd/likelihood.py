@@ -1,10 +1,13 @@
 """The likelihood the PixelCNN gives to GIVEN codes (csrc/code_nll.hip behind include/pixelsynth_nll.h): what the reference reports on
 every validation pass -- autoreg_loss = CrossEntropyLoss()(outpaint2(one_hot(gt_codes), masks), gt_codes), models/z_buffermodel.py:351-381
-and :398; train_lmconv.py:406 and :584-587 report the same quantity in bits -- without gradients, on the device.
+and :398; train_lmconv.py:406 and :584-587 report the same quantity in bits -- on the device; without gradients from the fused engine
+(score_codes), and as a loss to differentiate from the layer-by-layer network (ar_loss).
 
     code_nll      logits + target codes -> per location nll, entropy, hit; per frame their fp64 sums per group (observed / sampled)
     score_codes   ONE whole-grid forward of the engine on the given codes with a plan's masks, then code_nll: the masks made from an
                   order admit only predecessors and mask_init is type A, so one pass gives every conditional at once
+    ar_loss       the same mean cross entropy as a differentiable loss: OurPixelCNN's layers on the one-hot codes, every masked convolution
+                  and its backward a HIP kernel (csrc/lmconv_bwd.hip) -- what train_lmconv.py minimises
 
 Nothing comes down to the host: every field of the result is a device tensor, and so is what its methods return.
 """
@@ -106,12 +109,8 @@ def _engine_of(model_or_engine, H, W, F_):
     return net
 
 
-def score_codes(model_or_engine, codes, plan_or_masks, region=None, temperature=1.0):
-    """The likelihood of `codes` (F,H,W) -- or (F,L) with a plan, whose grid it is -- under the PixelCNN in the generation order of
-    `plan_or_masks`: the compact ARPlan, or the three masks (mask_init, mask_undilated, mask_dilated) as get_masks_for_batch returns them
-    -- (F*513,9,L), (F*160,9,L), (F*80,9,L) -- or one copy per frame, (F|1,9,L).  One PixelCNNEngine.forward on the codes (every
-    location's logits are conditioned on its predecessors' codes alone), then code_nll on its logits.  region: None takes the plan's
-    sampled region (every location observed where only masks are given) -> CodeNLL."""
+def _plan_args(who, codes, plan_or_masks, region):
+    """-> (H, W, the three masks one copy per frame, region) of the arguments score_codes and ar_loss share"""
     F_ = codes.shape[0]
     if isinstance(plan_or_masks, ARPlan):
         plan = plan_or_masks
@@ -121,14 +120,52 @@ def score_codes(model_or_engine, codes, plan_or_masks, region=None, temperature=
             region = plan.region
     else:
         if len(plan_or_masks) != 3:
-            raise ValueError("score_codes: an ARPlan or the three masks (mask_init, mask_undilated, mask_dilated) expected")
+            raise ValueError(f"{who}: an ARPlan or the three masks (mask_init, mask_undilated, mask_dilated) expected")
         if codes.dim() != 3:
-            raise ValueError(f"score_codes: with masks the codes carry the grid, (F,H,W); got {tuple(codes.shape)}")
+            raise ValueError(f"{who}: with masks the codes carry the grid, (F,H,W); got {tuple(codes.shape)}")
         H, W = codes.shape[1:]
         masks = tuple(compact_mask(m.to(codes.device), F_, c) for m, c in zip(plan_or_masks, (CLASSES + 1, 160, 80)))
     if codes.numel() != F_ * H * W:
-        raise ValueError(f"score_codes: codes of shape {tuple(codes.shape)} for a {H} x {W} grid")
+        raise ValueError(f"{who}: codes of shape {tuple(codes.shape)} for a {H} x {W} grid")
     _lib.require_cuda(codes)
+    return H, W, masks, region
+
+
+def score_codes(model_or_engine, codes, plan_or_masks, region=None, temperature=1.0):
+    """The likelihood of `codes` (F,H,W) -- or (F,L) with a plan, whose grid it is -- under the PixelCNN in the generation order of
+    `plan_or_masks`: the compact ARPlan, or the three masks (mask_init, mask_undilated, mask_dilated) as get_masks_for_batch returns them
+    -- (F*513,9,L), (F*160,9,L), (F*80,9,L) -- or one copy per frame, (F|1,9,L).  One PixelCNNEngine.forward on the codes (every
+    location's logits are conditioned on its predecessors' codes alone), then code_nll on its logits.  region: None takes the plan's
+    sampled region (every location observed where only masks are given) -> CodeNLL."""
+    F_ = codes.shape[0]
+    H, W, masks, region = _plan_args("score_codes", codes, plan_or_masks, region)
     with torch.cuda.device(codes.device):
         logits = _engine_of(model_or_engine, H, W, F_).forward(codes, *masks)
     return code_nll(logits, codes, region, temperature, "chw")
+
+
+def ar_loss(model, codes, plan_or_masks, region=None, group="sampled", temperature=1.0):
+    """The mean cross entropy in nats of `codes` over the locations of `group` ("all", "sampled", "observed") as a DIFFERENTIABLE 0-dim
+    fp32 loss -- the quantity score_codes(...).mean_nll(group) reports from the fused engine, here from OurPixelCNN._forward_layers on
+    the one-hot codes: plain torch but for the masked convolutions, whose forward and backward are HIP kernels.  Arguments as
+    score_codes; model: ZbufferModelPts (its outpaint2) or OurPixelCNN.  After optimizer.step() the model's engine rebuilds itself
+    (it is keyed on the parameters' versions), so sampling and scoring use the tuned weights.  A group without a location: NaN."""
+    if group not in GROUPS:
+        raise ValueError(f"ar_loss: group is {group!r}, expected one of {GROUPS}")
+    if not temperature > 0:
+        raise ValueError(f"ar_loss: temperature = {temperature}, expected > 0")
+    net = getattr(model, "outpaint2", model)
+    if not hasattr(net, "_forward_layers"):
+        raise TypeError(f"ar_loss: {type(model).__name__} is not a model with the PixelCNN's layers (an engine holds no parameters to tune)")
+    F_ = codes.shape[0]
+    H, W, masks, region = _plan_args("ar_loss", codes, plan_or_masks, region)
+    targets = codes.reshape(F_, H * W).long()
+    x = torch.nn.functional.one_hot(targets.view(F_, H, W), CLASSES).permute(0, 3, 1, 2).float()
+    with torch.cuda.device(codes.device):
+        logits = net._forward_layers(x, True, *masks).reshape(F_, CLASSES, H * W)
+        nll = torch.nn.functional.cross_entropy(logits / float(temperature), targets, reduction="none")
+        if group == "all":
+            return nll.mean()
+        sampled = torch.zeros_like(nll, dtype=torch.bool) if region is None else region.reshape(F_, H * W) != 0
+        take = sampled if group == "sampled" else ~sampled
+        return torch.where(take, nll, torch.zeros_like(nll)).sum() / take.sum()

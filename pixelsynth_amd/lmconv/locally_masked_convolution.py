@@ -1,14 +1,18 @@
 """Locally masked convolution on MI355X -- drop-in for the reference's
-models/lmconv/locally_masked_convolution.py (forward only; the custom backward :52-93 is training code).
+models/lmconv/locally_masked_convolution.py: the forward (:11-50) and the custom backward (:52-93).
 
 The reference builds im2col (F.unfold), multiplies by the per-location 3x3 mask and calls matmul
 (:25-42).  Here one C-ABI call (ps_lmconv_forward_f32 -> csrc/lmconv.hip:k_gemm) gathers the masked
-taps straight from a channels-last copy of x into v_mfma_f32_16x16x4_f32 tiles.  No CPU fallback.
+taps straight from a channels-last copy of x into v_mfma_f32_16x16x4_f32 tiles.  The backward is HIP as well
+(csrc/lmconv_bwd.hip behind include/pixelsynth_lmconv_bwd.h): grad_weight and grad_bias are one GEMM over the
+B*L locations on the same MFMA, and grad_input is the forward kernel itself on the adjoint mask and the flipped,
+transposed weight.  No CPU fallback, no atomics: a backward pass gives the same bits every time.
 """
 import math
 
 import torch
 import torch.nn as nn
+from torch.autograd.function import once_differentiable
 from torch.nn.parameter import Parameter
 
 from .. import _lib
@@ -58,16 +62,59 @@ def lmconv_forward(x, mask, weight, bias=None, dilation=1):
     return y
 
 
-class _locally_masked_conv2d:
-    """Same call surface as the reference autograd.Function (inference only)."""
+def adjoint_mask(m, H, W, dilation=1):
+    """m (B|1,9,L) contiguous f32 on the device -> m'[b,t,p] = m[b,8-t,p+off(t)] inside the grid, 0 outside: the mask with which
+    grad_x = lmconv_forward(grad_y, m', weight.flip(2, 3).transpose(0, 1))."""
+    out = torch.empty_like(m)
+    _lib.call("ps_lmconv_adjoint_mask_f32", m, m.size(0), H, W, int(dilation), out)
+    return out
+
+
+def lmconv_backward(grad_y, x, mask, weight, dilation=1, need_x=True, need_weight=True, need_bias=False):
+    """The gradients of lmconv_forward for grad_y (B,Co,H,W): -> (grad_x (B,Ci,H,W), grad_weight (Co,Ci,3,3) summed over the batch,
+    grad_bias (Co)), None for what is not asked for.  mask in any form compact_mask accepts."""
+    _lib.require_cuda(grad_y, x, mask, weight)
+    B, Ci, H, W = x.shape
+    Co = weight.size(0)
+    if tuple(weight.shape[1:]) != (Ci, 3, 3) or tuple(grad_y.shape) != (B, Co, H, W):
+        raise AssertionError(f"lmconv backward: grad_output {tuple(grad_y.shape)} / weight {tuple(weight.shape)} for an input {tuple(x.shape)}")
+    m = compact_mask(mask, B, Ci)
+    g = grad_y.float().contiguous()            # (y.sum().backward() hands over a stride-0 expansion)
+    gx = gw = gb = None
+    with torch.cuda.device(x.device):
+        if need_x:
+            gx = lmconv_forward(g, adjoint_mask(m, H, W, dilation), weight.detach().flip(2, 3).transpose(0, 1), None, dilation)
+        if need_weight or need_bias:
+            stride = 0 if m.size(0) == 1 and B > 1 else 9 * H * W
+            gw = torch.empty(Co, Ci, 3, 3, dtype=torch.float32, device=x.device) if need_weight else None
+            gb = torch.empty(Co, dtype=torch.float32, device=x.device) if need_bias else None
+            ws = _workspace(x.device, _lib.call("ps_lmconv_bwd_workspace_bytes", B, Ci, Co, H, W)) if need_weight else None
+            _lib.call("ps_lmconv_grad_weight_f32", x.detach().float().contiguous() if need_weight else None, g, m if need_weight else None,
+                      stride, B, Ci, Co, H, W, int(dilation), gw, gb, ws, ws.numel() if need_weight else 0)
+    return gx, gw, gb
+
+
+class _locally_masked_conv2d(torch.autograd.Function):
+    """Same call surface as the reference autograd.Function; forward is lmconv_forward, backward lmconv_backward."""
 
     @staticmethod
-    def apply(x, mask, weight, mask_weight=None, bias=None, dilation=1, padding=1):
+    def forward(ctx, x, mask, weight, mask_weight=None, bias=None, dilation=1, padding=1):
         if mask_weight is not None:
             raise NotImplementedError("conv_mask_weight=True is not used by PixelSynth (z_buffermodel.py:71)")
+        if ctx.needs_input_grad[1]:
+            raise AssertionError("lmconv: the mask takes no gradient (the reference's backward asserts it, :91)")
+        ctx.save_for_backward(x, mask, weight)
+        ctx.dilation, ctx.has_bias = dilation, bias is not None
         return lmconv_forward(x, mask, weight, bias, dilation)
 
-    forward = apply
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_output):
+        x, mask, weight = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        gx, gw, gb = lmconv_backward(grad_output, x, mask, weight, ctx.dilation, need[0], need[2], ctx.has_bias and need[4])
+        cast = lambda g, like: g if g is None or g.dtype == like.dtype else g.to(like.dtype)
+        return cast(gx, x), None, cast(gw, weight), None, gb, None, None
 
 
 class locally_masked_conv2d(nn.Module):
