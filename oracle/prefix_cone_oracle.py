@@ -1,5 +1,5 @@
 """TEST INFRASTRUCTURE -- numpy restatement of which items of an AR run's observed prefix anybody reads (the
-dependency cone that k_prefix_starts in pixelsynth_amd/csrc/lmconv.hip keeps as one start rank per stage and frame).
+dependency cone that k_prefix_starts in pixelsynth_amd/csrc/lmconv_plan.hip keeps as one start rank per stage and frame).
 
 Not a restatement of reference code: the reference runs a full forward per sampled code (models/lmconv/sample.py:54-66)
 and has no prefix pass.  The graph walked here is the reference network's (models/lmconv/model.py:132-151: up pass u0..u8,

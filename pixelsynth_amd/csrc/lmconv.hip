@@ -274,23 +274,27 @@ int build_stage_table(ps_pixelcnn *h)
         h->wbytes_chain += 4.0 * Co * cin + (w_skip ? 4.0 * NF * 2 * NF : 0.0);
         st.push_back(d);
     };
+    constexpr StageGraph sg = stage_graph();
     auto gated = [&](int g) {
         const ps_pixelcnn::Gated &G = h->gated[g];
-        push(G.w_in, G.w_skip, h->E[G.node_in], 2 * NF, 10, NF, 1, 1, 4, 1, IN_CELU, G.node_skip >= 0 ? G.node_skip : -1);
-        prev = Prev{PRO_CONVIN, G.b_in, G.b_skip, G.node_skip >= 0, nullptr, nullptr, h->X[g], -1};
+        const int node_in = sg.g_in[g], node_skip = sg.g_skip[g], node_out = sg.g_out[g];
+        push(G.w_in, G.w_skip, h->E[node_in], 2 * NF, 10, NF, 1, 1, 4, 1, IN_CELU, node_skip >= 0 ? node_skip : -1);
+        prev = Prev{PRO_CONVIN, G.b_in, G.b_skip, node_skip >= 0, nullptr, nullptr, h->X[g], -1};
         push(G.w_out, nullptr, h->X[g], 2 * NF, 10, 2 * NF, 1, 1, 4, 1, IN_CELU, -1);
-        prev = Prev{PRO_GATE, G.b_out, nullptr, 0, h->R[G.node_out], h->E[G.node_out], nullptr, -1};
-        prev.save = (G.node_out >= 1 && G.node_out <= 7) ? G.node_out : -1;  // LDS slot k holds u_k
+        prev = Prev{PRO_GATE, G.b_out, nullptr, 0, h->R[node_out], h->E[node_out], nullptr, -1};
+        prev.save = (node_out >= 1 && node_out <= 7) ? node_out : -1;  // LDS slot k holds u_k
     };
     auto dilated = [&](int d) {
         const ps_pixelcnn::Dil &D = h->dil[d];
-        push(D.w, nullptr, h->R[D.node_in], R_LD, 5, NF, 2, 2, 4, 1, IN_RAW, -1);
-        prev = Prev{PRO_DIL, D.b, nullptr, 0, h->R[D.node_out], h->E[D.node_out], nullptr, -1};
-        prev.save = (D.node_out >= 1 && D.node_out <= 7) ? D.node_out : -1;
+        const int node_out = sg.d_out[d];
+        push(D.w, nullptr, h->R[sg.d_in[d]], R_LD, 5, NF, 2, 2, 4, 1, IN_RAW, -1);
+        prev = Prev{PRO_DIL, D.b, nullptr, 0, h->R[node_out], h->E[node_out], nullptr, -1};
+        prev.save = (node_out >= 1 && node_out <= 7) ? node_out : -1;
     };
-    gated(0); gated(1); dilated(0); gated(2); gated(3); dilated(1); gated(4); gated(5);
-    gated(6); gated(7); dilated(2); gated(8); gated(9); gated(10); dilated(3);
-    gated(11); gated(12); gated(13);
+    for (int e = 0; e < NBLOCK; ++e) {   // the blocks in execution order
+        if (sg.order[e] < NGATED) gated(sg.order[e]);
+        else dilated(sg.order[e] - NGATED);
+    }
     push(h->out_w, nullptr, nullptr, 0, 5, NCLS, 1, 1, 0, 0, IN_ELU, -1);  // nin_out(elu(u)), prologue = last gate
     if ((int)st.size() != NST) return ps::fail(PS_ERR_STATE, "stage table has %d entries, expected %d", (int)st.size(), NST);
     for (int k = 0; k < NST; ++k) {  // the centre taps again in the chain role's [step][chain][4] layout
@@ -439,16 +443,11 @@ int ps_pixelcnn_create(const float *const *params, int n_params, int H, int W, i
     int rc = PS_OK;
     auto fail_out = [&](int code) { ps_pixelcnn_destroy(h); return code; };
 
-    // ---- schedule: node numbering u0..u8 = 0..8, d0..d9 = 9..18 (model.py:132-151)
-    const int g_in[NGATED] = {0, 1, 3, 4, 6, 7, 8, 9, 11, 12, 13, 15, 16, 17};
-    const int g_out[NGATED] = {1, 2, 4, 5, 7, 8, 9, 10, 12, 13, 14, 16, 17, 18};
-    const int g_skip[NGATED] = {-1, -1, -1, -1, -1, -1, 7, 6, 5, 4, 3, 2, 1, 0};
-    // parameter indices in reference state_dict order
+    // ---- the blocks' parameters (their nodes and order: stage_graph(), lmconv_device.h); parameter indices in reference state_dict order
     auto down_base = [](int k) { return k * 7; };            // 8 down blocks x 7 tensors
     auto up_base = [](int k) { return 56 + k * 4; };         // 6 up blocks x 4 tensors
     for (int g = 0; g < NGATED; ++g) {
         ps_pixelcnn::Gated &G = h->gated[g];
-        G.node_in = g_in[g]; G.node_out = g_out[g]; G.node_skip = g_skip[g];
         G.w_skip = G.b_skip = nullptr;
         const float *w_in, *b_in, *w_out, *b_out;
         if (g < 6) {
@@ -467,10 +466,8 @@ int ps_pixelcnn_create(const float *const *params, int n_params, int H, int W, i
         if ((rc = upload(h, &G.w_out, po.data(), po.size()))) return fail_out(rc);
         if ((rc = upload(h, &G.b_out, b_out, 2 * NF))) return fail_out(rc);
     }
-    const int d_in[4] = {2, 5, 10, 14}, d_out[4] = {3, 6, 11, 15};
-    for (int d = 0; d < 4; ++d) {
+    for (int d = 0; d < NDIL; ++d) {
         const int b = 82 + d * 2;  // downsize_u_stream.{0,1}, upsize_u_stream.{0,1}
-        h->dil[d].node_in = d_in[d]; h->dil[d].node_out = d_out[d];
         std::vector<float> pw = pack_conv_host(params[b], NF, NF);
         if ((rc = upload(h, &h->dil[d].w, pw.data(), pw.size()))) return fail_out(rc);
         if ((rc = upload(h, &h->dil[d].b, params[b + 1], NF))) return fail_out(rc);
@@ -505,16 +502,7 @@ int ps_pixelcnn_create(const float *const *params, int n_params, int H, int W, i
         return fail_out(PS_ERR_HIP);
     }
     if ((rc = dev_alloc(h, &h->ctx, locs))) return fail_out(rc);
-    if ((rc = dev_alloc(h, &h->pstart, (size_t)N_EVAL * max_frames))) return fail_out(rc);
-    if ((rc = dev_alloc(h, &h->perm, 2 * locs))) return fail_out(rc);
-    if ((rc = dev_alloc(h, &h->permq, 2 * locs))) return fail_out(rc);
-    if ((rc = dev_alloc(h, &h->perm_sorted, 2 * locs))) return fail_out(rc);
-    if ((rc = dev_alloc(h, &h->perm_cnt, (size_t)2 * 512 * max_frames))) return fail_out(rc);
-    if ((rc = dev_alloc(h, &h->perm_tsum, (size_t)2 * max_frames))) return fail_out(rc);
-    // the exact cone and the stages' own item lists (lmconv_grid.hip): 33 x 128 B and 32 x 8 KB per frame of a 32 x 32 grid (34 MB at 128 frames)
-    if ((rc = dev_alloc(h, &h->pbits, (size_t)N_EVAL * max_frames * ((h->L + 31) / 32)))) return fail_out(rc);
-    if ((rc = dev_alloc(h, &h->cperm, (size_t)(N_EVAL - 1) * locs))) return fail_out(rc);
-    if ((rc = dev_alloc(h, &h->cperm_cnt, (size_t)(N_EVAL - 1) * max_frames))) return fail_out(rc);
+    if ((rc = plan_scratch_alloc(h))) return fail_out(rc);
     if ((rc = dev_alloc(h, &h->taps, locs))) return fail_out(rc);
     if ((rc = dev_alloc(h, &h->nbr_tp, (size_t)2 * NST * 2 * TP_COL_CAP * NBR_LD))) return fail_out(rc);
     if ((rc = dev_alloc(h, &h->cnt_tp, 2 * tp_cnt_index(NST, 0)))) return fail_out(rc);
@@ -824,11 +812,11 @@ void *ps_pixelcnn_debug_cache(ps_pixelcnn *h, int what, int idx)
     if (what == 2 && idx >= 0 && idx < NGATED) return h->X[idx];
     if (what == 8) return h->done_col; // tuning: the latency form's `done` counters [NST][CNT_PAD] (dword 1 of a row: look-ahead waits that had to wait)
     if (what == 3) return h->nbr_tp;   // neighbour slots of the last throughput launch [NST][2][1024][160]
-    if (what == 5) return h->pstart;   // (33, F) int32 of the last AR run's prefix pass: first rank evaluated per stage and frame
+    if (what == 5) return h->plan.pstart;   // (33, F) int32 of the last AR run's prefix pass: first rank evaluated per stage and frame
     // the same pass's exact cone and the stages' own item lists -- idx 0: (33, F, ceil(L / 32)) uint32 bit sets by rank; 1: (32, maxF) int32
     // entries per (product stage, share), a frame range's shares from its first frame on; 2: (32, maxF * L) int2 the lists, share s of a
     // range at (f0 * L + s * frames per share * npre); 3: (2, maxF * L) int2 the sorted lists they were taken from
-    if (what == 10) return idx == 0 ? (void *)h->pbits : idx == 1 ? (void *)h->cperm_cnt : idx == 2 ? (void *)h->cperm : idx == 3 ? (void *)h->permq : nullptr;
+    if (what == 10) return idx == 0 ? (void *)h->plan.pbits : idx == 1 ? (void *)h->plan.cperm_cnt : idx == 2 ? (void *)h->plan.cperm : idx == 3 ? (void *)h->plan.permq : nullptr;
 #ifdef PS_WG_TRACE_BUILD
     if (what == 6 || what == 7 || what == 9) return wg_trace_symbol(what);   // (lmconv_grid.hip)
 #endif

@@ -1,5 +1,5 @@
 // lmconv_device.h -- device-side vocabulary shared by the translation units of the locally-masked PixelCNN engine
-// (lmconv_grid.hip: whole-grid pass; lmconv_column.hip: latency form of the column launch; lmconv_tp.hip: throughput form;
+// (lmconv_plan.hip, lmconv_grid.hip: whole-grid pass, planned and run; lmconv_column.hip: latency form of the column launch; lmconv_tp.hip: throughput form;
 // lmconv.hip: the handle and the C ABI).  The canonical arithmetic lives here: every kernel walks taps, 80-channel chunks and
 // accumulation chains in ONE order and reduces PONO's statistics in ONE association order, so whole-grid and column evaluation
 // agree bit for bit.
@@ -32,7 +32,54 @@ constexpr int R_LD = 96;      // row stride of the raw-u caches R[node]: 80 chan
 constexpr int NGATED = 14;
 constexpr int MAX_TAPS = 10;  // 9 conv taps + 1 nin_skip slot
 constexpr int N_XCD = 8;      // gfx950: 8 XCDs, workgroup ids are dealt round-robin over them
-constexpr int N_EVAL = 1 + 2 * NGATED + 4;   // stages of the whole-grid pass that have a prefix start rank (k_prefix_starts): 33
+constexpr int NDIL = 4;
+constexpr int NBLOCK = NGATED + NDIL;
+constexpr int N_EVAL = 1 + 2 * NGATED + NDIL;   // stages of the whole-grid pass that have a prefix start rank (k_prefix_starts): 33
+
+// The stage graph of the network, stated once (model.py:132-151).  Nodes: u0..u8 = 0..8 (up pass), d0..d9 = 9..18 (down pass); node 0
+// is written by u_init.  Gated block g reads node g_in[g] (+ node g_skip[g] through nin_skip, -1 = none) and writes g_out[g]; dilated
+// conv d reads d_in[d] and writes d_out[d].  order[]: the 18 blocks as they run, gated block g as g, dilated conv d as NGATED + d.
+// A kernel takes a copy (`constexpr StageGraph sg = stage_graph();`): a namespace-scope table has no device definition.
+struct StageGraph {
+    int g_in[NGATED], g_out[NGATED], g_skip[NGATED], d_in[NDIL], d_out[NDIL], order[NBLOCK];
+};
+constexpr __host__ __device__ StageGraph stage_graph()
+{
+    constexpr int D = NGATED;
+    return StageGraph{{0, 1, 3, 4, 6, 7, 8, 9, 11, 12, 13, 15, 16, 17},
+                      {1, 2, 4, 5, 7, 8, 9, 10, 12, 13, 14, 16, 17, 18},
+                      {-1, -1, -1, -1, -1, -1, 7, 6, 5, 4, 3, 2, 1, 0},
+                      {2, 5, 10, 14},
+                      {3, 6, 11, 15},
+                      {0, 1, D + 0, 2, 3, D + 1, 4, 5,                  // up pass
+                       6, 7, D + 2, 8, 9, 10, D + 3, 11, 12, 13}};      // down pass
+}
+// Evaluation stages of the whole-grid pass, the index of every per-stage table of its plan (starts, bit sets, item lists): 0 = u_init +
+// norm_init, then the convs.  Mask kind of a conv's stage: 0 = type B dilation 1, 1 = type B dilation 2.
+constexpr __host__ __device__ int eval_conv_in(int g) { return 1 + g; }                   // conv_input (+ nin_skip) of gated block g
+constexpr __host__ __device__ int eval_conv_out(int g) { return 1 + NGATED + g; }         // its conv_out + gate
+constexpr __host__ __device__ int eval_dil(int d) { return 1 + 2 * NGATED + d; }          // dilated conv d
+constexpr __host__ __device__ int eval_mask_kind(int stage) { return stage >= eval_dil(0) ? 1 : 0; }
+
+// -> 0, or which of the three properties below does not hold (an index outside a table does not compile)
+constexpr int stage_graph_fault()
+{
+    constexpr StageGraph sg = stage_graph();
+    bool ran[NBLOCK] = {}, written[NNODE] = {true}, id[N_EVAL] = {true};   // (node 0 and stage 0: u_init)
+    auto taken = [](bool &slot) { const bool was = slot; slot = true; return was; };
+    for (int e = 0; e < NBLOCK; ++e) {
+        const int b = sg.order[e], g = b < NGATED ? b : 0, d = b < NGATED ? 0 : b - NGATED;
+        if (taken(ran[b])) return 1;
+        const int in = b < NGATED ? sg.g_in[g] : sg.d_in[d], skip = b < NGATED ? sg.g_skip[g] : -1, out = b < NGATED ? sg.g_out[g] : sg.d_out[d];
+        if (!written[in] || (skip >= 0 && !written[skip]) || taken(written[out])) return 2;
+        if (b < NGATED ? taken(id[eval_conv_in(g)]) || taken(id[eval_conv_out(g)]) : taken(id[eval_dil(d)])) return 3;
+    }
+    return 0;   // (NBLOCK distinct blocks, each with a node and ids of its own: all NNODE nodes are written, all N_EVAL ids taken)
+}
+static_assert(N_EVAL == 1 + 2 * NGATED + NDIL && NNODE == 1 + NBLOCK, "one id per conv and one node per block, + u_init");
+static_assert(stage_graph_fault() != 1, "every block appears once in the execution order");
+static_assert(stage_graph_fault() != 2, "every node is written once, before it is read");
+static_assert(stage_graph_fault() != 3, "the evaluation-stage ids cover [1, N_EVAL) exactly");
 
 // Split-K slots of a masked 3x3 conv.  Every consumer adds them in this order:
 //   y = ((bias + NA) + C) + NB          (+ SKIP after the norm, layers.py:155-156)

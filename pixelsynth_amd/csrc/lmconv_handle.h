@@ -2,6 +2,7 @@
 // owns, its tuning values, and the launchers each unit exports to the C ABI in lmconv.hip.
 #pragma once
 #include "lmconv_device.h"
+#include "lmconv_items.h"
 #include "../../include/pixelsynth_hip_debug.h"
 
 namespace pslm {
@@ -117,6 +118,21 @@ struct Tuning {
     int column_debug = 0;        // settable in tuning builds only (-DPS_TUNING_BUILD): timing experiments whose results are INVALID
 };
 
+// Device tables of the planning of a whole-grid pass (lmconv_plan.hip: plan_scratch_alloc, plan_grid); a pass over frames [f0, f0 + nf)
+// uses its own part of each, so passes over disjoint frame ranges may be planned and run side by side.
+struct PlanScratch {
+    int32_t *pstart = nullptr;      // (N_EVAL, F) first rank of the prefix anyone reads, per stage and frame (k_prefix_starts)
+    uint32_t *pbits = nullptr;      // (N_EVAL, F, ceil(L / 32)) the exact set of ranks evaluated per stage and frame, a bit per rank (k_prefix_sets)
+    // items of a pass grouped by open-tap set (k_perm_*): [2 mask kinds][maxF * L] each
+    int32_t *perm = nullptr;        // position -> natural item index (frame-local: fl * npre + rank)
+    int2 *permq = nullptr;          // the same as (item, location) pairs
+    uint32_t *perm_sorted = nullptr;   // scratch: (key << 12 | rank) of every frame, sorted
+    int32_t *perm_cnt = nullptr;    // scratch: [2][512 * maxF] run lengths -> first positions
+    int32_t *perm_tsum = nullptr;   // scratch: [2][maxF] totals of that table's tiles of 1024 entries
+    int2 *cperm = nullptr;          // [N_EVAL - 1][maxF * L] the product stages' own item lists: the evaluated entries of permq (k_perm_compact)
+    int32_t *cperm_cnt = nullptr;   // [N_EVAL - 1][maxF] their lengths, per share (a frame range's shares at its first frame on)
+};
+
 }  // namespace pslm
 
 // ------------------------------------------------------------------------------------------
@@ -125,27 +141,15 @@ struct Tuning {
 struct ps_pixelcnn {
     int H = 0, W = 0, L = 0, maxF = 0;
     std::vector<void *> allocs;
-    struct Gated {
-        float *w_in, *b_in, *w_out, *b_out, *w_skip, *b_skip;
-        int node_in, node_skip, node_out;
-    } gated[pslm::NGATED];
-    struct Dil { float *w, *b; int node_in, node_out; } dil[4];
+    struct Gated { float *w_in, *b_in, *w_out, *b_out, *w_skip, *b_skip; } gated[pslm::NGATED];   // (their nodes: pslm::stage_graph())
+    struct Dil { float *w, *b; } dil[pslm::NDIL];
     float *uinit_w = nullptr, *uinit_b = nullptr, *out_w = nullptr, *out_b = nullptr;
     float *R[pslm::NNODE], *E[pslm::NNODE], *X[pslm::NGATED];
     float *partial = nullptr;       // whole-grid slots [4][maxF*L][160]
     float *nbr = nullptr;           // column mode: neighbour slots [2][NST][2][COL_CAP][160]
     float *col_logits = nullptr;
     pslm::StepCtx *ctx = nullptr;   // column records of a run, [maxF * L]
-    int32_t *pstart = nullptr;      // (N_EVAL, F) first rank of the prefix anyone reads, per stage and frame (k_prefix_starts)
-    // items of a whole-grid pass grouped by open-tap set (k_perm_*, lmconv_grid.hip): [2 mask kinds][maxF * L] each
-    int32_t *perm = nullptr;        // position -> natural item index (frame-local: fl * npre + rank)
-    int2 *permq = nullptr;          // the same as (item, location) pairs
-    uint32_t *perm_sorted = nullptr;   // scratch: (key << 12 | rank) of every frame, sorted
-    int32_t *perm_cnt = nullptr;    // scratch: [2][512 * maxF] run lengths -> first positions
-    int32_t *perm_tsum = nullptr;   // scratch: [2][maxF] totals of that table's tiles of 1024 entries
-    uint32_t *pbits = nullptr;      // (N_EVAL, F, ceil(L / 32)) the exact set of ranks evaluated per stage and frame, a bit per rank (k_prefix_sets)
-    int2 *cperm = nullptr;          // [N_EVAL - 1][maxF * L] the product stages' own item lists: the evaluated entries of permq (k_perm_compact)
-    int32_t *cperm_cnt = nullptr;   // [N_EVAL - 1][maxF] their lengths, per share (a frame range's shares at its first frame on)
+    pslm::PlanScratch plan;         // the whole-grid pass's item planning (lmconv_plan.hip)
     int *ctl1 = nullptr;            // the chain roles' control records
     unsigned *cnt = nullptr;        // [2][NST][MAX_TILES] padded completion counters of the neighbour role, never reset
     int *err = nullptr;             // device flags [2]: a bounded wait of a column launch ran out; k_ctx_build's refusals (CTX_ERR_*, lmconv.hip)
@@ -240,6 +244,26 @@ inline void timed(ps_pixelcnn *h, hipStream_t st, int tag, int kind, Fn &&launch
 inline int pad16(int v) { return (v + 15) / 16 * 16; }
 
 // ---- what the translation units export to each other (all in namespace pslm) ----
+// lmconv_plan.hip: which items every stage of a whole-grid pass evaluates, and in which order.  plan_grid enqueues the planning launches
+// of the pass run_grid describes below (dependency cone, sorted item lists, the stages' own lists -- as the handle's tuning values say)
+// on `st` and returns where their tables lie; want_logits: the caller reads the logits of every item, so every item is evaluated.
+struct GridPlan {
+    ItemMap all;                        // what every stage shares: order, npre, f0, end, bw, cshare, cparts
+    int nitems, F;                      // nitems = nf * npre; <= 0: there is nothing to run (and nothing was enqueued)
+    const int32_t *start;               // (N_EVAL, F) the cone as start ranks, or null
+    const uint32_t *bits;               // (N_EVAL, F, bw) the cone as exact sets, or null
+    const int32_t *perm[2];             // the sorted item list per mask kind, or null
+    const int2 *permq[2];
+    const int2 *cq;                     // the product stages' own lists, stage by stage `cq_stride` / `ccnt_stride` apart, or null
+    const int32_t *ccnt;
+    size_t cq_stride, ccnt_stride;
+    ItemMap walk(int eval_stage) const;       // the items as they are, those of the stage wanted: k_uinit_grid / k_post_grid / nin_out / k_logits_grid
+    ItemMap products(int eval_stage) const;   // for the conv of that stage: + the sorted list of ITS mask kind and the stage's own list
+};
+GridPlan plan_grid(ps_pixelcnn *h, int F, const Masks &m, const int32_t *order, int npre, int f0, int nf, const int32_t *pend,
+                   bool want_logits, hipStream_t st);
+ItemMap all_locations(int L);          // every location of every frame in raster order, no plan (the generic lmconv entry point)
+int plan_scratch_alloc(ps_pixelcnn *h);   // the tables of h->plan, for h->maxF frames (ps_pixelcnn_create)
 // lmconv_grid.hip: whole-grid evaluation (reference-faithful forward; cache build before the column steps).  logits: null (caches only),
 // (F,512,H,W) when nchw, else (F*L,512) by location.  With an order the pass covers ranks [0, npre) of frames [f0, f0 + nf) -- with
 // pend (device, (F)) ranks [0, pend[f]) of frame f, pend[f] <= npre (per-frame prefixes).

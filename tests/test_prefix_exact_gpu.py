@@ -1,5 +1,5 @@
 """GPU: the prefix pass with the dependency cone as EXACT sets (k_prefix_sets, tuning value prefix_exact) and with every product
-stage walking a list of its own evaluated items (k_perm_compact, prefix_compact) -- lmconv_grid.hip.
+stage walking a list of its own evaluated items (k_perm_compact, prefix_compact) -- lmconv_plan.hip.
 
 What is pinned: (a) the device's bit sets equal oracle/prefix_cone_oracle.exact_need_sets for every stage and frame, with per-frame
 prefix ends; (b) the per-(stage, share) lists are the sorted lists filtered in order and their lengths are the sets' popcounts;
