@@ -172,9 +172,17 @@ LMCONV_BWD_PROTOS = {
     "ps_lmconv_adjoint_mask_f32": (RC, [c_void_p] + [c_int] * 4 + [c_void_p, STREAM]),
 }
 
+# libpixelsynth_splat_bwd.so (include/pixelsynth_splat_bwd.h): the backward pass of the soft z-buffer splat and of the reprojection
+SPLAT_BWD_PROTOS = {
+    "ps_splat_bwd_last_error": (ctypes.c_char_p, []),
+    "ps_splat_bwd_workspace_bytes": (c_size_t, [c_int] * 3),
+    "ps_splat_backward_f32": (RC, [c_void_p] * 5 + [c_int] * 4 + [c_double, c_int, c_float, c_int, c_int] + [c_void_p] * 3 + [c_size_t, STREAM]),
+    "ps_project_pts_backward_f32": (RC, [c_void_p] * 6 + [c_int, c_int, c_void_p, STREAM]),
+}
+
 # short name of _libraries.LIBRARIES -> its prototype table; _OWNER: entry point -> the table entry of its library, built once
 PROTOS = {"hip": _PROTOS, "percsim": PERCSIM_PROTOS, "consistency": CONSISTENCY_PROTOS, "fid": FID_PROTOS, "scene": SCENE_PROTOS,
-          "plan": PLAN_PROTOS, "rank": RANK_PROTOS, "rank_groups": RANK_GROUPS_PROTOS, "nll": NLL_PROTOS, "lmconv_bwd": LMCONV_BWD_PROTOS}
+          "plan": PLAN_PROTOS, "rank": RANK_PROTOS, "rank_groups": RANK_GROUPS_PROTOS, "nll": NLL_PROTOS, "lmconv_bwd": LMCONV_BWD_PROTOS, "splat_bwd": SPLAT_BWD_PROTOS}
 _ENTRIES = {e.name: e for e in _libraries.LIBRARIES}
 assert set(PROTOS) == set(_ENTRIES)
 _OWNER = {fn: _ENTRIES[name] for name, table in PROTOS.items() for fn in table}

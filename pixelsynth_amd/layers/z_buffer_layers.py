@@ -5,6 +5,9 @@ The reference rasterizes with PyTorch3D (rasterize_points + compositing.*, z_buf
 112-129) and materialises (B,S,S,K) idx/dist/alpha tensors; here one C-ABI call
 (ps_splat_f32 -> pixelsynth_amd/csrc/splat.hip) bins, sorts and composites on the fly.
 There is no CPU fallback: tensors must live on the ROCm device.
+
+Under autograd (grad mode on, pts3D or src requires grad) forward goes through _SplatFunction: the list-emitting route of ps_splat_f32
+forward, ps_splat_backward_f32 (csrc/splat_bwd.hip, include/pixelsynth_splat_bwd.h) backward.
 """
 import os
 
@@ -40,11 +43,70 @@ def splat_workspace(device, B, N, S, radius_px):
     return _WS.get(device, n)
 
 
+_WS_BWD = _Workspace()     # the backward pass' two coefficient planes: kept apart, so that a forward between never regrows either
+
+
+def splat_bwd_workspace(device, B, S, K):
+    n = _lib.call("ps_splat_bwd_workspace_bytes", B, S, K)
+    if n == 0:
+        raise RuntimeError("ps_splat_bwd_workspace_bytes: invalid sizes")
+    return _WS_BWD.get(device, n)
+
+
+class _SplatFunction(torch.autograd.Function):
+    """(pts (B,N,3) f32 contiguous, feat (B,C,N) f32 contiguous, S, radius, K, tau, rad_pow, accumulation, bg_ksize) ->
+    (features (B,C,S,S), background mask (B,S,S) uint8, not differentiable).  The caller's pts is left as it is: the negation is applied
+    to a copy, which is saved with the K-nearest lists (idx int32 and dist f32, (B,S,S,K) each)."""
+
+    @staticmethod
+    def forward(ctx, pts, feat, S, radius, K, tau, rad_pow, accumulation, bg_ksize):
+        B, N, C = pts.size(0), pts.size(1), feat.size(1)
+        neg = pts.detach().clone()
+        feat = feat.detach()
+        out = torch.empty(B, C, S, S, dtype=torch.float32, device=pts.device)
+        bg = torch.empty(B, S, S, dtype=torch.uint8, device=pts.device)
+        idx = torch.empty(B, S, S, K, dtype=torch.int32, device=pts.device)
+        dist = torch.empty(B, S, S, K, dtype=torch.float32, device=pts.device)
+        ws = splat_workspace(pts.device, B, N, S, radius)
+        _lib.call("ps_splat_f32", neg, feat, B, N, C, S, float(radius), K, float(tau), int(rad_pow), accumulation, int(bg_ksize),
+                  out, bg, idx, None, dist, ws, ws.numel())
+        ctx.save_for_backward(neg, feat, idx, dist)
+        ctx.args = (B, N, C, S, float(radius), K, float(tau), int(rad_pow), accumulation)
+        ctx.mark_non_differentiable(bg)
+        return out, bg
+
+    @staticmethod
+    def backward(ctx, grad_out, _grad_bg):
+        neg, feat, idx, dist = ctx.saved_tensors
+        B, N, C, S, radius, K, tau, rad_pow, accumulation = ctx.args
+        want_pts, want_feat = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not (want_pts or want_feat):
+            return (None,) * 9
+        g = grad_out.float().contiguous()
+        grad_pts = torch.empty_like(neg) if want_pts else None
+        grad_feat = torch.empty_like(feat) if want_feat else None
+        ws = splat_bwd_workspace(neg.device, B, S, K)
+        _lib.call("ps_splat_backward_f32", neg, feat, idx, dist, g, B, N, C, S, radius, K, tau, rad_pow, accumulation,
+                  grad_pts, grad_feat, ws, ws.numel())
+        return (grad_pts, grad_feat) + (None,) * 7
+
+
 class RasterizePointsXYsBlending(nn.Module):
     """Same inputs/outputs as the reference class (z_buffer_layers.py:12-131).
 
     forward(pts3D (B,N,3), src (B,C,N)) -> (features (B,C,S,S) f32, background_mask (B,S,S) bool).
-    Like the reference, x and y of the caller's pts3D are negated in place (:71-72)."""
+    Like the reference, x and y of the caller's pts3D are negated in place (:71-72).
+
+    The differentiable route.  With grad mode on and pts3D or src requiring grad (and return_debug False), the features carry a grad_fn
+    and backward() gives gradients to src and to x and y of pts3D (z gets exact zeros: the z order is piecewise constant, as in
+    PyTorch3D); background_mask is marked non-differentiable.  Its forward is the list-emitting route of ps_splat_f32: all K hits of
+    every pixel, bit-exact lists -- so its features are those of return_debug=True, not the early-out product route's (which stops a
+    pixel's walk once its transmittance is below 2^-23 and fuses the sum).  It saves the K-nearest lists for the backward pass: an
+    int32 index and an fp32 distance per hit, 8 K bytes per pixel -- 67 MB per 256 x 256 frame at K = 128.  On this route the
+    caller's pts3D is NOT negated in place, the one deviation from the reference's side effect: an in-place write into a tensor
+    autograd tracks either raises (a leaf that requires grad) or invalidates what upstream nodes saved.  A call in which nothing
+    requires grad, or one under torch.no_grad(), takes the route it always took, side effect included.  At the clamp of
+    dist / r^rad_pow to [1e-3, 1] the gradient with respect to the points is exactly 0 where the clamp holds (bounds included)."""
 
     def __init__(self, C=64, learn_feature=True, radius=1.5, size=256, points_per_pixel=8, opts=None):
         super().__init__()
@@ -73,6 +135,12 @@ class RasterizePointsXYsBlending(nn.Module):
         os.environ.get("DEBUG")  # the reference reads os.environ["DEBUG"] (KeyError if unset); tolerated here
 
         B, N, C = bs, pts3D.size(1), src.size(1)
+        if not return_debug and torch.is_grad_enabled() and (pts3D.requires_grad or src.requires_grad):
+            out, bg = _SplatFunction.apply(pts3D.float().contiguous(), src.float().contiguous(), int(image_size), self.radius,
+                                           int(self.points_per_pixel), self._opt("tau", 1.0), self._opt("rad_pow", 2),
+                                           ACCUMULATION[self._opt("accumulation", "alphacomposite")],
+                                           self._opt("background_smoothing_kernel_size", 13))
+            return out, bg.view(torch.bool)
         caller_pts = pts3D
         pts = pts3D if (pts3D.is_contiguous() and pts3D.dtype == torch.float32) else pts3D.float().contiguous()
         feat = src.float().contiguous()

@@ -5,6 +5,11 @@ project_pts / project_pts_cumulative run in csrc/splat.hip:k_project through the
 (ps_project_pts_f32, ps_project_pts_cumulative_f32); forward_justpts uses the fused
 ps_project_splat_f32 so the (B,N,3) cloud never leaves the scratch buffer.
 
+Under autograd (grad mode on and the depth or the features requiring grad) project_pts is differentiable in the depth
+(ps_project_pts_backward_f32, csrc/splat_bwd.hip) and forward_justpts in src and pred_pts: it then takes the unfused route, project_pts
+and the splatter's differentiable route.  No gradient is produced for the camera matrices.  forward_justpts_cumulative /
+project_pts_cumulative and forward_scene_step stay forward-only.
+
 forward_scene_step advances B independent chained scenes by one frame on a SceneState -- per-scene clouds of different lengths that
 stay on the device between frames (csrc/scene.hip through ps_scene_step_f32, include/pixelsynth_scene.h).
 """
@@ -27,6 +32,27 @@ def get_splatter(name, depth_values, opt=None, size=256, C=64, points_per_pixel=
 
 def _f32c(t):
     return t if (t.dtype == torch.float32 and t.is_contiguous()) else t.float().contiguous()
+
+
+class _ProjectFunction(torch.autograd.Function):
+    """depth (B,N) f32 contiguous, cameras (B,4,4) f32 contiguous -> sampler (B,3,N); differentiable in the depth alone"""
+
+    @staticmethod
+    def forward(ctx, depth, K, K_inv, RTinv_cam1, RT_cam2, W):
+        B = depth.size(0)
+        out = torch.empty(B, 3, W * W, dtype=torch.float32, device=depth.device)
+        _lib.call("ps_project_pts_f32", depth, K, K_inv, RTinv_cam1, RT_cam2, B, W, out)
+        ctx.save_for_backward(depth, K, K_inv, RTinv_cam1, RT_cam2)
+        ctx.W = W
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_sampler):
+        depth, K, K_inv, RTinv_cam1, RT_cam2 = ctx.saved_tensors
+        grad_depth = torch.empty_like(depth)
+        _lib.call("ps_project_pts_backward_f32", depth, K, K_inv, RTinv_cam1, RT_cam2, grad_sampler.float().contiguous(),
+                  depth.size(0), ctx.W, grad_depth)
+        return grad_depth, None, None, None, None, None     # (no gradient for the camera matrices)
 
 
 class SceneState:
@@ -94,10 +120,13 @@ class PtsManipulator(nn.Module):
 
     # ------------------------------------------------------------------ a2
     def project_pts(self, pts3D, K, K_inv, RT_cam1, RTinv_cam1, RT_cam2, RTinv_cam2):
-        """Reference :50-83.  pts3D (B,1,N) depth -> sampler (B,3,N)."""
+        """Reference :50-83.  pts3D (B,1,N) depth -> sampler (B,3,N); differentiable in the depth (not in the cameras)."""
         B = pts3D.size(0)
         N = self.W * self.W
         assert pts3D.numel() == B * N, "project_pts expects one depth per grid point"
+        if torch.is_grad_enabled() and pts3D.requires_grad:
+            return _ProjectFunction.apply(pts3D.float().contiguous().view(B, N), _f32c(K).detach(), _f32c(K_inv).detach(),
+                                          _f32c(RTinv_cam1).detach(), _f32c(RT_cam2).detach(), self.W)
         depth = _f32c(pts3D)
         out = torch.empty(B, 3, N, dtype=torch.float32, device=depth.device)
         _lib.call("ps_project_pts_f32", depth, _f32c(K), _f32c(K_inv), _f32c(RTinv_cam1), _f32c(RT_cam2), B, self.W, out)
@@ -105,9 +134,11 @@ class PtsManipulator(nn.Module):
 
     # ------------------------------------------------------------------ a3
     def forward_justpts(self, src, pred_pts, K, K_inv, RT_cam1, RTinv_cam1, RT_cam2, RTinv_cam2):
-        """Reference :85-107 -> (features (B,C,W,W), background_mask (B,W,W) bool)."""
+        """Reference :85-107 -> (features (B,C,W,W), background_mask (B,W,W) bool).  With grad mode on and src or pred_pts requiring
+        grad: the unfused route (project_pts, then the splatter), differentiable in both; else the fused call, as ever."""
         bs, c, w, h = src.size()
-        if len(pred_pts.size()) > 3 and w == self.W and h == self.W:
+        differentiable = torch.is_grad_enabled() and (src.requires_grad or pred_pts.requires_grad)
+        if len(pred_pts.size()) > 3 and w == self.W and h == self.W and not differentiable:
             sp = self.splatter
             S = self.W
             out = torch.empty(bs, c, S, S, dtype=torch.float32, device=src.device)

@@ -1,0 +1,167 @@
+"""Measurement: the backward pass of the soft z-buffer splat (csrc/splat_bwd.hip through ps_splat_backward_f32) for B = 16 frames of
+256 x 256, one point per pixel (N = 256^2) reprojected under a yaw of 0.4, r = 4 px, at C = 3 and C = 64 and K = 8 and K = 128 --
+against torch autograd of the gather formula (distances recomputed from the points, alphas, the compositing, a gather of the features)
+on the same saved lists on the device.
+
+    python tools/splat_bwd_time.py [--frames 16] [--rounds 5] [--calls 5]
+
+Both routes compute grad_pts and grad_feat for the same grad_out; the forward passes (and torch's graph) are made outside the timed
+part.  The two routes alternate call by call in one process, each call between two device events on a synchronised device; after WARM
+calls of each, a round is CALLS calls per route and gives one median per route; the range of the rounds' medians is reported.  The HIP
+route's kernels (pixels, points) and the backward of the projection are reported separately, as the medians of their device times under
+torch's profiler in a run of their own.  Where the torch formula's tensors of B x C x S x S x K elements do not fit the device's free
+memory it is not timed, and the line says so.  One JSON line per shape."""
+import argparse
+import json
+import os
+import sys
+import types
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from pixelsynth_amd import _lib, synthetic as syn  # noqa: E402
+from pixelsynth_amd.layers.z_buffer_layers import splat_bwd_workspace, splat_workspace  # noqa: E402
+from pixelsynth_amd.projection.z_buffer_manipulator import PtsManipulator  # noqa: E402
+
+WARM = 2
+S, RADIUS, TAU, RAD_POW, ACC = 256, 4.0, 1.0, 2, 0
+SHAPES = ((3, 8), (64, 8), (3, 128), (64, 128))       # (C, K)
+KERNELS = ("k_splat_bwd_pixels", "k_splat_bwd_points", "k_project_bwd")
+
+
+def gather_formula(pts, feat, idx, N):
+    """Alpha compositing at tau = 1, rad_pow = 2 on the saved lists: pts (B,N,3) the caller's points, feat (B,C,N), idx (B,S,S,K)"""
+    B, C = feat.shape[:2]
+    hit = idx >= 0
+    n = torch.where(hit, idx.long() % N, torch.zeros_like(idx, dtype=torch.long))
+    flat = n.reshape(B, -1)
+    centre = -1.0 + (2.0 * (S - 1 - torch.arange(S, dtype=torch.float32, device=pts.device)) + 1.0) / S
+    dx = torch.gather(-pts[..., 0], 1, flat).reshape(n.shape) - centre.view(1, 1, S, 1)
+    dy = torch.gather(-pts[..., 1], 1, flat).reshape(n.shape) - centre.view(1, S, 1, 1)
+    r = (dx * dx + dy * dy) / float(np.float32((RADIUS / S * 2.0) ** RAD_POW))
+    d = torch.where((r > 1e-3) & (r < 1.0), r, r.detach().clamp(1e-3, 1.0))
+    a = torch.where(hit, 1.0 - torch.sqrt(d), torch.zeros_like(d))
+    w = a * torch.cat([torch.ones_like(a[..., :1]), torch.cumprod(1.0 - a, dim=-1)[..., :-1]], dim=-1)
+    f = torch.gather(feat, 2, flat.unsqueeze(1).expand(B, C, -1)).reshape(B, C, *n.shape[1:])
+    return (w.unsqueeze(1) * f).sum(-1)
+
+
+def one(fn):
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    fn()
+    e1.record()
+    e1.synchronize()
+    return e0.elapsed_time(e1)
+
+
+def alternate(routes, rounds, calls):
+    """routes {name: callable}; -> {name: the medians of `rounds` rounds of `calls` event-timed calls, in ms}, the routes taking turns"""
+    for _ in range(WARM):
+        for fn in routes.values():
+            one(fn)
+    medians = {name: [] for name in routes}
+    for _ in range(rounds):
+        times = {name: [] for name in routes}
+        for _ in range(calls):
+            for name, fn in routes.items():
+                times[name].append(one(fn))
+        for name in routes:
+            medians[name].append(float(np.median(times[name])))
+    return medians
+
+
+def kernel_medians(fn, calls):
+    """{kernel: median device time in ms} of the kernels of KERNELS that fn launches, under torch's profiler; {} where it records none"""
+    from torch.profiler import ProfilerActivity, profile
+    with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
+        for _ in range(calls):
+            fn()
+        torch.cuda.synchronize()
+    times = {}
+    for ev in prof.events():
+        for k in KERNELS:
+            if k in ev.name and ev.device_time > 0:
+                times.setdefault(k, []).append(ev.device_time / 1e3)
+    return {k: round(float(np.median(v)), 4) for k, v in times.items()}
+
+
+def span(v):
+    return [round(min(v), 4), round(max(v), 4)]
+
+
+def main(argv):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--frames", type=int, default=16)
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--calls", type=int, default=5)
+    args = ap.parse_args(argv)
+    dev = torch.device("cuda", 0)
+    B, N = args.frames, S * S
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    cam = syn.demo_cameras(B)
+    RT2inv, RT2 = syn.yaw_pose(cam["P"], 0.4)
+    cams = [t(cam[k]) for k in ("K", "Kinv", "P", "Pinv")] + [t(RT2), t(RT2inv)]
+    depth = t(syn.depth_smooth(2, B, S, 1.0, 100.0))
+    opt = types.SimpleNamespace(splatter="xyblending", learn_default_feature=False, radius=RADIUS, pp_pixel=8, tau=TAU, rad_pow=RAD_POW,
+                                accumulation="alphacomposite", background_smoothing_kernel_size=13)
+    pm = PtsManipulator(S, C=3, opt=opt).to(dev)
+    with torch.no_grad():
+        sampler = pm.project_pts(depth.view(B, 1, -1), *cams)
+    pts = sampler.permute(0, 2, 1).contiguous()
+    g_sampler = torch.randn(B, 3, N, device=dev)
+    g_depth = torch.empty(B, N, device=dev)
+    project = lambda: _lib.call("ps_project_pts_backward_f32", depth, cams[0], cams[1], cams[3], cams[4], g_sampler, B, S, g_depth)
+    gen = torch.Generator(device="cpu").manual_seed(0)
+    for C, K in SHAPES:
+        feat = (torch.rand(B, C, N, generator=gen) * 2 - 1).to(dev)
+        g = torch.randn(B, C, S, S, generator=gen).to(dev)
+        neg = pts.clone()
+        out = torch.empty(B, C, S, S, device=dev)
+        bg = torch.empty(B, S, S, dtype=torch.uint8, device=dev)
+        idx = torch.empty(B, S, S, K, dtype=torch.int32, device=dev)
+        dist = torch.empty(B, S, S, K, device=dev)
+        ws = splat_workspace(dev, B, N, S, RADIUS)
+        _lib.call("ps_splat_f32", neg, feat, B, N, C, S, RADIUS, K, TAU, RAD_POW, ACC, 13, out, bg, idx, None, dist, ws, ws.numel())
+        gp, gf = torch.empty_like(neg), torch.empty_like(feat)
+        wb = splat_bwd_workspace(dev, B, S, K)
+        hip = lambda gp_=gp, gf_=gf: _lib.call("ps_splat_backward_f32", neg, feat, idx, dist, g, B, N, C, S, RADIUS, K, TAU, RAD_POW, ACC,
+                                               gp_, gf_, wb, wb.numel())
+        routes = {"hip": hip, "hip_grad_feat": lambda: hip(None, gf), "hip_grad_pts": lambda: hip(gp, None), "project_bwd": project}
+        hits = float((idx >= 0).sum()) / (B * S * S)
+        # the torch formula: about (3 C + 12) tensors of B S S K floats stay alive between its forward and the end of its backward
+        need = (3 * C + 12) * B * S * S * K * 4
+        free = torch.cuda.mem_get_info(dev)[0]
+        note, diff = None, None
+        if need > 0.8 * free:
+            note = f"torch formula not timed: about {need / 2**30:.0f} GiB of (B,C,S,S,K) tensors against {free / 2**30:.0f} GiB free"
+        else:
+            p_t, f_t = pts.clone().requires_grad_(), feat.clone().requires_grad_()
+            y = gather_formula(p_t, f_t, idx, N)
+            routes["torch"] = lambda: torch.autograd.grad(y, (p_t, f_t), g, retain_graph=True)
+        med = alternate(routes, args.rounds, args.calls)
+        if "torch" in routes:
+            hip()
+            ref = routes["torch"]()
+            diff = {"grad_pts": float((gp - ref[0]).abs().max()), "grad_feat": float((gf - ref[1]).abs().max())}
+            del y, ref
+        kern = kernel_medians(lambda: (hip(), project()), args.calls)
+        rec = dict(what="splat_backward", frames=B, S=S, N=N, C=C, K=K, radius_px=RADIUS, hits_per_pixel=round(hits, 2), rounds=args.rounds,
+                   calls=args.calls, kernel_ms_median=kern, max_abs_diff=diff, note=note,
+                   **{f"{k}_ms_median_range": span(v) for k, v in med.items()})
+        torch_txt = "%.3f .. %.3f ms" % tuple(span(med["torch"])) if "torch" in med else note
+        print("splat backward C = %d, K = %d, %d frames of %d x %d, %.1f hits per pixel: medians of %d rounds of %d calls: HIP %.3f .. %.3f ms "
+              "(grad_feat alone %.3f .. %.3f, grad_pts alone %.3f .. %.3f), project_pts backward %.3f .. %.3f ms; torch autograd of the "
+              "gather formula: %s; kernels %s; largest differences %s"
+              % (C, K, B, S, S, hits, args.rounds, args.calls, *span(med["hip"]), *span(med["hip_grad_feat"]), *span(med["hip_grad_pts"]),
+                 *span(med["project_bwd"]), torch_txt, kern or "not recorded by the profiler", diff))
+        print(json.dumps(rec), flush=True)
+        del feat, g, idx, dist, gp, gf, neg
+        torch.cuda.empty_cache()
+
+
+if __name__ == "__main__":
+    main(sys.argv[1:])
