@@ -4,7 +4,7 @@
 
 One object per translation unit of csrc/, linked into the library the table names for it: libpixelsynth_hip.so and, beside it,
 libpixelsynth_percsim.so, libpixelsynth_consistency.so, libpixelsynth_fid.so, libpixelsynth_scene.so (scene.hip includes splat.hip
-for its kernels), libpixelsynth_plan.so, libpixelsynth_rank.so, libpixelsynth_rank_groups.so, libpixelsynth_nll.so, libpixelsynth_lmconv_bwd.so and libpixelsynth_splat_bwd.so.  The HIP units are built with -ffp-contract=off: splat.hip because its index paths must be bit-exact against the
+for its kernels), libpixelsynth_plan.so, libpixelsynth_rank.so, libpixelsynth_rank_groups.so, libpixelsynth_nll.so, libpixelsynth_lmconv_bwd.so, libpixelsynth_splat_bwd.so and libpixelsynth_vq_train.so.  The HIP units are built with -ffp-contract=off: splat.hip because its index paths must be bit-exact against the
 oracle, the lmconv*.hip units (lmconv_plan.hip, the planning of the whole-grid pass, with them: it shares their headers) so that the post ops inlined into different kernels (whole-grid vs column step) round identically, the
 metric units because their fp32 steps restate the reference's in its order; the matrix products are explicit MFMA intrinsics and are
 not affected.  With PS_HIP_LIB set (tuning builds, with PS_OBJ_SUFFIX and PS_EXTRA_HIPCC_FLAGS) only the main library is built, there.

@@ -198,3 +198,19 @@ def gather_rows(local, n, force_collective=False):
     dist.all_gather(bufs, block)
     stacked = torch.stack([b.cpu() for b in bufs], 2)            # (k, per, W): item j * W + r
     return stacked.reshape(k, -1)[:, :n].numpy().copy()
+
+
+def sum_over_ranks(*tensors):
+    """Sum each tensor over the ranks, in place (the VQ-VAE quantiser's per-code statistics in training: the reference's
+    dist_fn.all_reduce, models/vqvae2/vqvae.py:57-58).  With one rank -- or no process group -- nothing is touched and no collective
+    is called.  -> the tensors"""
+    if world()[1] > 1:
+        gloo = dist.get_backend() == "gloo"
+        for t in tensors:
+            if gloo and t.is_cuda:                              # gloo has no device all_reduce: host staging (tests / dry runs only)
+                staged = t.cpu()
+                dist.all_reduce(staged)
+                t.copy_(staged)
+            else:
+                dist.all_reduce(t)
+    return tensors

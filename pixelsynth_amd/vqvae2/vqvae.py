@@ -14,7 +14,11 @@ tail (ReLU, 1 x 1, + the ReLU'd input) is one launch of csrc/conv1x1.hip; the 3-
 A module whose layers break one of the kernels' rules goes through torch.  Each call of ``encode_codes`` / ``decode_code`` is one scope of
 the split-fp16 overflow guard (networks/f16x3.py: checked once, rerun in fp32 if an activation left fp16's range).
 PS_VQVAE_CONV=fp32 (or networks.f16x3.decoder_conv("fp32") in effect) sends everything through torch (MIOpen).
-Training (the EMA codebook update, :53-70) is out of scope.
+Training: in ``train()`` mode ``Quantize.forward`` is the reference's (:41-74) on csrc/vq_train.hip -- the straight-through output and the
+commitment term, the per-code counts and sums (a product with the one-hot matrix on the fp32 MFMA, built in registers from the int32
+codes), their sum over the ranks, the EMA update of ``cluster_size`` / ``embed_avg`` / ``embed`` in place, and a backward pass that
+keeps the codes and the codebook as it was (never an (N, dim) residual).  The convolutions of ``forward`` run through torch whenever grad
+mode is on or the module trains; vqvae2/train.py has the training step.
 
 One reference quirk is part of the numerics: ResBlock starts with an *in-place* ReLU, so the residual it adds is
 relu(x), not x (:93-95).
@@ -212,6 +216,54 @@ class _FastPath:
         return F.conv_transpose2d(F.relu(h), dc[6].weight, dc[6].bias, 2, 1).contiguous()
 
 
+class _QuantizeTraining(torch.autograd.Function):
+    """Quantize.forward in training mode on flat (N, dim) float32 CUDA latents -> (quantize (N, dim), diff (), codes (N,) int32);
+    updates the module's buffers.  Once differentiable."""
+
+    @staticmethod
+    def forward(ctx, flat, module):
+        from ..distributed import sum_over_ranks
+        N, D, K = flat.size(0), module.dim, module.n_embed
+        dev = flat.device
+        idx = module.nearest(flat, 0)
+        rows = module.embed.t().contiguous()                       # (K, D): the codebook BEFORE the update, one code per row
+        need = _lib.call("ps_vq_train_workspace_bytes", N, D, K)
+        if not need:
+            raise RuntimeError(f"Quantize.forward (training mode): {N} vectors of {D} channels, {K} codes are sizes the kernels refuse")
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        quantize, diff = torch.empty_like(flat), torch.empty(1, dtype=torch.float32, device=dev)
+        _lib.call("ps_vq_train_quantize_f32", flat, idx, rows, N, D, K, quantize, diff, ws, need)
+        counts = torch.empty(K, dtype=torch.int32, device=dev)
+        sums = torch.empty(D, K, dtype=torch.float32, device=dev)
+        _lib.call("ps_vq_train_stats_f32", flat, idx, N, D, K, counts, sums, ws, need)
+        sum_over_ranks(counts, sums)
+        embed = torch.empty_like(module.embed)
+        _lib.call("ps_vq_train_update_f32", counts, sums, D, K, float(module.decay), 1 - float(module.decay), float(module.eps),
+                  module.cluster_size, module.embed_avg, embed, ws, need)
+        # the kernel wrote two buffers through raw pointers; the codebook goes through copy_ so that its version counter moves
+        # (_FastPath.key_of reads it), and the other two are bumped for whoever saved them
+        module.embed.copy_(embed)
+        for b in (module.cluster_size, module.embed_avg):
+            torch.autograd.graph.increment_version(b)
+        ctx.save_for_backward(flat, idx, rows)
+        ctx.mark_non_differentiable(idx)
+        ctx.set_materialize_grads(False)                           # (an output nobody used: None, not a tensor of zeros to read)
+        return quantize, diff.reshape(()), idx
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_quantize, grad_diff, _grad_idx):
+        flat, idx, rows = ctx.saved_tensors
+        if grad_quantize is None and grad_diff is None:
+            return None, None
+        N, D = flat.shape
+        gq = None if grad_quantize is None else grad_quantize.contiguous().float()
+        gd = None if grad_diff is None else grad_diff.reshape(1).contiguous().float()
+        grad = torch.empty_like(flat)
+        _lib.call("ps_vq_train_backward_f32", flat, idx, rows, gq, gd, N, D, rows.size(0), grad)
+        return grad, None
+
+
 class Quantize(nn.Module):
     def __init__(self, dim, n_embed, decay=0.99, eps=1e-5):
         super().__init__()
@@ -230,14 +282,29 @@ class Quantize(nn.Module):
         return idx
 
     def forward(self, input):
-        """input (..., dim) -> (quantize, diff, embed_ind) like the reference (inference)."""
+        """input (..., dim) -> (quantize, diff, embed_ind) like the reference; in train() mode the codebook's EMA update happens on
+        the way (also under torch.no_grad()), and quantize / diff carry the straight-through / commitment gradients."""
         if self.training:
-            raise RuntimeError("Quantize: the EMA codebook update (training) is not part of the novel-view path")
+            return self._forward_training(input)
         flat = input.reshape(-1, self.dim).float()
         ind = self.nearest(flat, 0).to(torch.int64).view(*input.shape[:-1])
         quantize = self.embed_code(ind)
         diff = (quantize - input).pow(2).mean()
         return quantize, diff, ind
+
+    def _forward_training(self, input):
+        if not input.is_cuda:
+            raise RuntimeError("Quantize.forward (training mode) needs its input on the ROCm device (got a CPU tensor; there is no "
+                               "CPU fallback for the HIP path)")
+        if input.dtype != torch.float32:
+            raise TypeError(f"Quantize.forward (training mode): input is {input.dtype}, expected torch.float32")
+        for name in ("embed", "cluster_size", "embed_avg"):
+            b = getattr(self, name)
+            if b.device != input.device or b.dtype != torch.float32 or not b.is_contiguous():
+                raise RuntimeError(f"Quantize.forward (training mode): the buffer {name} must be contiguous float32 on {input.device}")
+        flat = input.reshape(-1, self.dim).contiguous()
+        quantize, diff, ind = _QuantizeTraining.apply(flat, self)
+        return quantize.view(input.shape), diff, ind.to(torch.int64).view(*input.shape[:-1])
 
     def embed_code(self, embed_id):
         return F.embedding(embed_id.to(torch.int64), self.embed.transpose(0, 1))
