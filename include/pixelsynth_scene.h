@@ -1,6 +1,6 @@
 /* pixelsynth_scene.h -- the C ABI of libpixelsynth_scene.so: one frame of B independent chained trajectories
  * (ZbufferModelPts.forward_scene, model settings gen_scene / gen_two_imgs) per call, over accumulated point clouds of DIFFERENT lengths
- * (csrc/scene.hip, which builds on the kernels of csrc/splat.hip).  A library of its own next to libpixelsynth_hip.so, whose ABI (version 2)
+ * (csrc/scene.hip, which builds on the kernels of csrc/splat_pipeline.h, the ones csrc/splat.hip launches).  A library of its own next to libpixelsynth_hip.so, whose ABI (version 2)
  * it leaves as it is.  Same conventions as include/pixelsynth_hip.h: int status, 0 = success, ps_scene_last_error() says why not; every
  * buffer is the caller's; the last parameter is the stream; no allocation, no synchronisation, no device-to-host copy.
  *

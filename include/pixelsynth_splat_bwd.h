@@ -41,7 +41,7 @@ size_t ps_splat_bwd_workspace_bytes(int B, int S, int K);
  * element of an output is written: exact zeros for points that are culled, hit no pixel or lie behind a pixel's K-th hit.
  * k_splat_bwd_pixels: one lane per pixel (8 x 8 tiles), front to back for a_k, cum_k, q_k, back to front for R; writes the two planes.
  * k_splat_bwd_points: one wave per point, a gather over the pixels of the point's conservative box (the forward's bounding-box
- * arithmetic) in row-major order, 64 pixels a round; per channel the hits are added in that order, the two coordinates lane by lane in
+ * arithmetic, csrc/splat_math.h: one definition for both) in row-major order, 64 pixels a round; per channel the hits are added in that order, the two coordinates lane by lane in
  * that order and then through a fixed butterfly. */
 int ps_splat_backward_f32(const float *pts_negated, const float *feat, const int32_t *idx, const float *dist, const float *grad_out,
                           int B, int N, int C, int S, double radius_px, int K, float tau, int rad_pow, int accumulation,

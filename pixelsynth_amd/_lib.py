@@ -286,6 +286,28 @@ def call(name, *args, stream=None):
     return rc
 
 
+class Workspace:
+    """Scratch owned by PyTorch (the library never allocates); grown on demand, kept per device.  One instance per user whose sizes
+    alternate, so that none regrows the other's."""
+
+    def __init__(self):
+        self.buf = {}
+
+    def get(self, device, nbytes):
+        t = self.buf.get(device)
+        if t is None or t.numel() < nbytes:
+            t = torch.empty(int(nbytes), dtype=torch.uint8, device=device)
+            self.buf[device] = t
+        return t
+
+    def query(self, device, name, *sizes):
+        """get() of what the entry point `name` asks for on `sizes`; an answer of 0 is its refusal of them"""
+        n = call(name, *sizes)
+        if n == 0:
+            raise RuntimeError(f"{name}: invalid sizes")
+        return self.get(device, n)
+
+
 def ptr(t):
     """Device (or host) pointer of a contiguous torch tensor / numpy array, or None."""
     if t is None:

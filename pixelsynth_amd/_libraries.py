@@ -17,7 +17,7 @@ Library = namedtuple("Library", "name so units headers last_error")
 
 LIBRARIES = (
     Library("hip", "libpixelsynth_hip.so",
-            [("splat.hip", NO_CONTRACT), ("lmconv.hip", NO_CONTRACT), ("lmconv_grid.hip", NO_CONTRACT),
+            [("splat.hip", NO_CONTRACT), ("zbuffer.hip", NO_CONTRACT), ("lmconv.hip", NO_CONTRACT), ("lmconv_grid.hip", NO_CONTRACT),
              ("lmconv_plan.hip", NO_CONTRACT), ("lmconv_column.hip", NO_CONTRACT), ("lmconv_tp.hip", NO_CONTRACT), ("vq.hip", NO_CONTRACT), ("nets.hip", NO_CONTRACT),
              ("conv_f16x3.hip", NO_CONTRACT + ["-Wno-inline-asm"]), ("conv_thin.hip", NO_CONTRACT), ("conv1x1.hip", NO_CONTRACT),
              ("vq_ends.hip", NO_CONTRACT), ("metrics.hip", NO_CONTRACT), ("host_order.cpp", [])],

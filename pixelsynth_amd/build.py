@@ -3,8 +3,9 @@
     python -m pixelsynth_amd.build [--force]
 
 One object per translation unit of csrc/, linked into the library the table names for it: libpixelsynth_hip.so and, beside it,
-libpixelsynth_percsim.so, libpixelsynth_consistency.so, libpixelsynth_fid.so, libpixelsynth_scene.so (scene.hip includes splat.hip
-for its kernels), libpixelsynth_plan.so, libpixelsynth_rank.so, libpixelsynth_rank_groups.so, libpixelsynth_nll.so, libpixelsynth_lmconv_bwd.so, libpixelsynth_splat_bwd.so and libpixelsynth_vq_train.so.  The HIP units are built with -ffp-contract=off: splat.hip because its index paths must be bit-exact against the
+libpixelsynth_percsim.so, libpixelsynth_consistency.so, libpixelsynth_fid.so, libpixelsynth_scene.so (scene.hip and splat.hip share
+the splat's kernels through the header splat_pipeline.h), libpixelsynth_plan.so, libpixelsynth_rank.so, libpixelsynth_rank_groups.so, libpixelsynth_nll.so, libpixelsynth_lmconv_bwd.so, libpixelsynth_splat_bwd.so and libpixelsynth_vq_train.so.  The HIP units are built with -ffp-contract=off: the splat family
+(splat.hip, zbuffer.hip, scene.hip, splat_bwd.hip, which share splat_math.h) because its index paths must be bit-exact against the
 oracle, the lmconv*.hip units (lmconv_plan.hip, the planning of the whole-grid pass, with them: it shares their headers) so that the post ops inlined into different kernels (whole-grid vs column step) round identically, the
 metric units because their fp32 steps restate the reference's in its order; the matrix products are explicit MFMA intrinsics and are
 not affected.  With PS_HIP_LIB set (tuning builds, with PS_OBJ_SUFFIX and PS_EXTRA_HIPCC_FLAGS) only the main library is built, there.
@@ -29,9 +30,8 @@ if EXTRA:   # ps_build_info() (csrc/host_order.cpp) names them: a number measure
 
 
 def _deps():
-    """What every unit is rebuilt after: the headers of csrc/ and include/, and splat.hip (scene.hip includes it)"""
-    return glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(os.path.dirname(HERE), "include", "*.h")) + [
-        os.path.join(CSRC, "splat.hip")]
+    """What every unit is rebuilt after: the headers of csrc/ and include/"""
+    return glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(os.path.dirname(HERE), "include", "*.h"))
 
 
 def build(force=False, verbose=True):

@@ -8,47 +8,28 @@
 // frame's new points with boolean gathers and a view(bs, 1, -1), which needs equal counts per image and a device-to-host round trip per
 // gather; here the selection is an ordered compaction on the device and the splat runs with per-cloud counts.
 //
-// The kernels of the splat are the ones of csrc/splat.hip, included below without its C ABI: k_bin_count / k_bin_fill with per-cloud
-// counts, k_scan, k_sort_*, k_composite and k_dilate* as they are -- one source, no second composite.
+// The kernels of the splat and their host core are csrc/splat_pipeline.h, which csrc/splat.hip includes as well: k_bin_count / k_bin_fill
+// with per-cloud counts, k_scan, k_sort_*, k_composite and k_dilate* as they are -- one source, no second composite.
 //
 // Pipeline of ps_scene_step_f32 (all on the caller's stream, no host sync, no allocation):
 //   k_scene_count   per scene and block of 256 pixels: how many pixels of last_background_mask are set
-//   k_scan          exclusive scan of each scene's block sums (splat.hip's scan, key slice 0): the block's first output slot and,
+//   k_scan          exclusive scan of each scene's block sums (splat_pipeline.h's scan, key slice 0): the block's first output slot and,
 //                   behind the last block, the scene's number of new points.  A scan, never an atomic: slot = rank in row-major order.
 //   k_scene_prior   every prior point t of scene b: X = K (RT2 RT3inv) p (:244-247) -> slot n_new[b] + t of the next cloud, its features
 //                   moved along
 //   k_scene_new     every kept pixel: p = grid * depth, X = K (RT2 RT1inv) Kinv p (:229-243) -> slot rank of the next cloud, its features
 //                   from the frame; block (0, b) then publishes count[b] += n_new[b]
 //   splat_core      with counts: the points at or past count[b] do not exist
-// The arithmetic of a point is k_project's (same helpers, same association order, -ffp-contract=off), and a point's slot is the index
+// The arithmetic of a point is k_project's (the helpers of csrc/splat_math.h, -ffp-contract=off), and a point's slot is the index
 // the B = 1 route gives it (new points first in row-major order of the mask, then the prior cloud in its order, :248-266): the
 // rasterizer breaks z ties by point index, so the results are the B = 1 route's bit for bit.
-#define PS_SPLAT_KERNELS_ONLY
-#include "splat.hip"
+#include "splat_pipeline.h"
 
 #include "../../include/pixelsynth_scene.h"
 
 namespace {
 
 constexpr int SB = 256;   // pixels per block of the compaction
-
-// RT = A B of scene b's (4,4) poses, K and Kinv into LDS: k_project's prologue
-__device__ __forceinline__ void scene_cams(const float *__restrict__ K, const float *__restrict__ Kinv, const float *__restrict__ RTa_inv,
-                                           const float *__restrict__ RT2, int b, float *sRT, float *sK, float *sKinv)
-{
-    if (threadIdx.x < 16) {
-        const int i = threadIdx.x >> 2, j = threadIdx.x & 3;
-        const float *A = RT2 + b * 16, *Bm = RTa_inv + b * 16;
-        float acc = A[i * 4 + 0] * Bm[0 * 4 + j];
-        acc = acc + A[i * 4 + 1] * Bm[1 * 4 + j];
-        acc = acc + A[i * 4 + 2] * Bm[2 * 4 + j];
-        acc = acc + A[i * 4 + 3] * Bm[3 * 4 + j];
-        sRT[threadIdx.x] = acc;
-        sK[threadIdx.x] = K[b * 16 + threadIdx.x];
-        if (Kinv) sKinv[threadIdx.x] = Kinv[b * 16 + threadIdx.x];
-    }
-    __syncthreads();
-}
 
 // a projected point into slot o (< cap, checked by the caller) of scene b: the homogeneous cloud (B,4,cap) and the rasterizer's
 // (B,cap,3) with x, y negated (what z_buffer_layers.py:71-72 hands PyTorch3D)
@@ -82,7 +63,7 @@ __global__ __launch_bounds__(SB) void k_scene_new(const float *__restrict__ dept
     __shared__ float sRT[16], sK[16], sKinv[16];
     __shared__ uint32_t wave_n[SB / 64];
     const int b = blockIdx.y, N = W * W;
-    scene_cams(K, Kinv, RT1inv, RT2, b, sRT, sK, sKinv);
+    load_cams(K, Kinv, RT1inv, RT2, b, sRT, sK, sKinv);
     const int t = blockIdx.x * SB + threadIdx.x;
     const bool keep = t < N && (!mask || mask[(size_t)b * N + t] != 0);
     // rank of a kept pixel inside the block, in thread (= row-major) order
@@ -98,13 +79,8 @@ __global__ __launch_bounds__(SB) void k_scene_new(const float *__restrict__ dept
         count[b] = (int32_t)(n < cap ? n : cap);   // (the host refused a step that does not fit; the clamp keeps a misuse inside the rows)
     }
     if (!keep || o >= (uint32_t)cap) return;
-    const int gx = t % W, gy = t / W;
-    const float den = (float)(W - 1);
-    const float xs = (float)gx / den * 2.0f - 1.0f;
-    const float ys = (float)gy / den * 2.0f - 1.0f;
-    const float d = depth[(size_t)b * N + t];
-    float p[4] = {xs * d, (-ys) * d, -1.0f * d, 1.0f};
-    float c[4], w[4], X[4];
+    float p[4], c[4], w[4], X[4];
+    GridPixel(t, W).point(depth[(size_t)b * N + t], p);
     mat4_vec(sKinv, p, c);
     mat4_vec(sRT, c, w);
     mat4_vec(sK, w, X);
@@ -120,7 +96,7 @@ __global__ __launch_bounds__(SB) void k_scene_prior(const float *__restrict__ cl
 {
     __shared__ float sRT[16], sK[16];
     const int b = blockIdx.y;
-    scene_cams(K, nullptr, RT3inv, RT2, b, sRT, sK, nullptr);
+    load_cams(K, nullptr, RT3inv, RT2, b, sRT, sK, nullptr);
     const int t = blockIdx.x * SB + threadIdx.x;
     if (t >= min(count[b], cap)) return;
     const size_t o = (size_t)blk[(size_t)b * (nblk + 1) + nblk] + (size_t)t;   // behind the scene's new points

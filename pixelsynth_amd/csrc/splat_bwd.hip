@@ -8,46 +8,21 @@
 //                        for ALL channels (q_k = <g, f_{n_k}> needs every one, so channel groups are not split over the grid), walks
 //                        front to back for a_k, cum_k, q_k and back to front for the recurrence R; writes the per-hit coefficients
 //                        w[p,k] and gd2[p,k] = dL/dd2 into the workspace (the two planes are its scratch on the way).
-//   k_splat_bwd_points   1 wave / point, a GATHER: walks the pixels of the point's conservative box (point_bbox's arithmetic of
-//                        splat.hip, restated) in row-major order, 64 pixels a round, one per lane; a lane runs the forward's exact
+//   k_splat_bwd_points   1 wave / point, a GATHER: walks the pixels of the point's conservative box (axis_range of splat_math.h,
+//                        the one the forward bins with) in row-major order, 64 pixels a round, one per lane; a lane runs the forward's exact
 //                        disc test and looks for the point's packed index among the K entries of its pixel.  Features: lane c owns
 //                        channel c and adds the round's hits in lane (= row-major pixel) order.  Coordinates: every lane adds its own
 //                        pixels round by round, then a fixed xor butterfly.  No atomics anywhere: two runs give the same bits, and a
 //                        cloud's gradients do not depend on what else is in the batch.  A box of thousands of pixels (large radii)
 //                        is walked the same way: correct, not fast.
 //   k_project_bwd        1 thread / point: the projected point is affine in the depth, so the gradient is closed form.
-// Built with -ffp-contract=off like splat.hip: the disc test and the distances must be the forward's, bit for bit.
-#include <cmath>
-
-#include "ps_common.h"
+// Built with -ffp-contract=off like splat.hip: the disc test and the distances must be the forward's, bit for bit -- the pixel and box
+// arithmetic, the projection's helpers and the constants are csrc/splat_math.h's, the forward's own.
+#include "splat_math.h"
 
 #include "../../include/pixelsynth_splat_bwd.h"
 
 namespace {
-
-constexpr int TILE = 8;                  // pixels per tile edge: 64 pixels = one wave64 (splat.hip)
-constexpr float PS_EPS = 1e-2f;          // z_buffer_manipulator.py:8
-constexpr float D_LO = 1e-3f;            // the clamp of dist^2 / denom (z_buffer_layers.py:89-91)
-constexpr float T_MIN = 1e-4f;           // the floor of wsumnorm's denominator (PyTorch3D's kEpsilon)
-
-// ------------------------------------------------------------------------------------------
-// the forward's pixel and box arithmetic (splat.hip: pix_to_ndc, axis_range, point_bbox), per pixel instead of per tile
-// ------------------------------------------------------------------------------------------
-__device__ __forceinline__ float pix_to_ndc(int i, int S) { return -1.0f + (2 * i + 1.0f) / S; }
-
-__device__ __forceinline__ bool axis_range(float p, int S, float hw, int &lo_px, int &hi_px)
-{
-    const float c = ((p + 1.0f) * S - 1.0f) * 0.5f;
-    float lo = c - hw, hi = c + hw;
-    if (!(hi >= 0.0f) || !(lo <= (float)(S - 1))) return false;  // also rejects NaN / inf
-    lo = fmaxf(lo, 0.0f);
-    hi = fminf(hi, (float)(S - 1));
-    const int ilo = (int)ceilf(lo), ihi = (int)floorf(hi);
-    if (ilo > ihi) return false;
-    lo_px = S - 1 - ihi;
-    hi_px = S - 1 - ilo;
-    return true;
-}
 
 // alpha of a hit from its squared distance, as k_composite's list-emitting route computes it (sqrtf is correctly rounded, as its
 // sqrt_rn_unit); root: sqrt(d); inside: the quotient lies strictly between the clamp bounds
@@ -151,11 +126,6 @@ __global__ __launch_bounds__(64) void k_splat_bwd_pixels(const int32_t *__restri
 // ------------------------------------------------------------------------------------------
 // per point: gather over the pixels of its box
 // ------------------------------------------------------------------------------------------
-__device__ __forceinline__ float bcast(float v, int lane)
-{
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane));
-}
-
 constexpr int PWAVES = 4;   // points (waves) per workgroup; the waves never synchronise
 
 __global__ __launch_bounds__(64 * PWAVES) void k_splat_bwd_points(const float *__restrict__ pts, const int32_t *__restrict__ idx,
@@ -236,49 +206,22 @@ __global__ __launch_bounds__(64 * PWAVES) void k_splat_bwd_points(const float *_
 }
 
 // ------------------------------------------------------------------------------------------
-// projection (splat.hip: mat4_vec, k_project, finish_point)
+// projection (the backward of splat.hip's k_project)
 // ------------------------------------------------------------------------------------------
-__device__ __forceinline__ void mat4_vec(const float *M, const float *v, float *o)
-{
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        float acc = M[i * 4 + 0] * v[0];
-        acc = acc + M[i * 4 + 1] * v[1];
-        acc = acc + M[i * 4 + 2] * v[2];
-        acc = acc + M[i * 4 + 3] * v[3];
-        o[i] = acc;
-    }
-}
-
 __global__ __launch_bounds__(256) void k_project_bwd(const float *__restrict__ depth, const float *__restrict__ K,
-                                                     const float *__restrict__ Kinv, const float *__restrict__ RT1inv,
+                                                     const float *__restrict__ Kinv __attribute__((nonnull)), const float *__restrict__ RT1inv,
                                                      const float *__restrict__ RT2, const float *__restrict__ grad_sampler, int W, int n,
                                                      float *__restrict__ grad_depth)
 {
     __shared__ float sRT[16], sK[16], sKinv[16];
     const int b = blockIdx.y;
-    if (threadIdx.x < 16) {
-        const int i = threadIdx.x >> 2, j = threadIdx.x & 3;
-        const float *A = RT2 + b * 16, *Bm = RT1inv + b * 16;
-        float acc = A[i * 4 + 0] * Bm[0 * 4 + j];
-        acc = acc + A[i * 4 + 1] * Bm[1 * 4 + j];
-        acc = acc + A[i * 4 + 2] * Bm[2 * 4 + j];
-        acc = acc + A[i * 4 + 3] * Bm[3 * 4 + j];
-        sRT[threadIdx.x] = acc;
-        sK[threadIdx.x] = K[b * 16 + threadIdx.x];
-        sKinv[threadIdx.x] = Kinv[b * 16 + threadIdx.x];
-    }
-    __syncthreads();
+    load_cams(K, Kinv, RT1inv, RT2, b, sRT, sK, sKinv);
     const int t = blockIdx.x * 256 + threadIdx.x;
     if (t >= n) return;
-    const int gx = t % W, gy = t / W;
-    const float den = (float)(W - 1);
-    const float xs = (float)gx / den * 2.0f - 1.0f;
-    const float ys = (float)gy / den * 2.0f - 1.0f;
-    const float d = depth[(size_t)b * n + t];
-    const float p[4] = {xs * d, (-ys) * d, -1.0f * d, 1.0f};   // the forward's point
-    const float dp[4] = {xs, -ys, -1.0f, 0.0f};                // its derivative with respect to the depth
-    float c[4], w[4], X[4], m1[4];
+    float p[4], dp[4], c[4], w[4], X[4], m1[4];
+    const GridPixel g(t, W);
+    g.point(depth[(size_t)b * n + t], p);                      // the forward's point
+    g.d_point(dp);                                             // its derivative with respect to the depth
     mat4_vec(sKinv, p, c);
     mat4_vec(sRT, c, w);
     mat4_vec(sK, w, X);
@@ -328,13 +271,9 @@ int ps_splat_backward_f32(const float *pts_negated, const float *feat, const int
     PS_REQUIRE((uintptr_t)workspace % 4 == 0, "splat_backward: the workspace must be aligned to 4 bytes");
     hipStream_t st = (hipStream_t)stream;
     float *plane_w = (float *)workspace, *plane_g = (float *)((char *)workspace + plane_bytes(B, S, K));
-    // radius and denominator exactly as the forward computes them (splat_core)
-    const double radius = radius_px / (double)S * 2.0;
-    const float rf = (float)radius;
-    const float r2 = rf * rf;
-    const float denom = (float)pow(radius, (double)rad_pow);
-    const float hw = (float)(radius_px * 1.0001 + 0.01);
-    const int tilesX = (S + TILE - 1) / TILE;
+    const SplatGeom geom(S, radius_px, rad_pow);               // the forward's radius, denominator and box (splat_core takes them from here too)
+    const float r2 = geom.r2, denom = geom.denom, hw = geom.hw;
+    const int tilesX = geom.tilesX;
     const dim3 gp(tilesX * tilesX, B);
     const int need_pts = grad_pts != nullptr;
 #define PS_BWD_PIXELS(MODE)                                                                                                     \

@@ -3,13 +3,14 @@ models/layers/z_buffer_layers.py:RasterizePointsXYsBlending (same constructor, s
 
 The reference rasterizes with PyTorch3D (rasterize_points + compositing.*, z_buffer_layers.py:81-84,
 112-129) and materialises (B,S,S,K) idx/dist/alpha tensors; here one C-ABI call
-(ps_splat_f32 -> pixelsynth_amd/csrc/splat.hip) bins, sorts and composites on the fly.
+(ps_splat_f32 -> pixelsynth_amd/csrc/splat.hip, its kernels in csrc/splat_pipeline.h) bins, sorts and composites on the fly.
 There is no CPU fallback: tensors must live on the ROCm device.
 
 Under autograd (grad mode on, pts3D or src requires grad) forward goes through _SplatFunction: the list-emitting route of ps_splat_f32
 forward, ps_splat_backward_f32 (csrc/splat_bwd.hip, include/pixelsynth_splat_bwd.h) backward.
 """
 import os
+from collections import namedtuple
 
 import torch
 from torch import nn
@@ -19,38 +20,23 @@ from .. import _lib
 ACCUMULATION = {"alphacomposite": 0, "wsum": 1, "wsumnorm": 2}
 
 
-class _Workspace:
-    """Scratch owned by PyTorch (the library never allocates); grown on demand, kept per device."""
+# radius_px, K, tau, rad_pow, accumulation, bg_ksize: the run of arguments every splat entry point takes, in the C ABI's order and types
+SplatSettings = namedtuple("SplatSettings", "radius_px K tau rad_pow accumulation bg_ksize")
 
-    def __init__(self):
-        self.buf = {}
-
-    def get(self, device, nbytes):
-        t = self.buf.get(device)
-        if t is None or t.numel() < nbytes:
-            t = torch.empty(int(nbytes), dtype=torch.uint8, device=device)
-            self.buf[device] = t
-        return t
-
-
-_WS = _Workspace()
+_WS = _lib.Workspace()         # the forward's scratch (the scene step's too: it is the forward's plus its block sums)
+_WS_BWD = _lib.Workspace()     # the backward pass' two coefficient planes: kept apart, so that a forward between never regrows either
 
 
 def splat_workspace(device, B, N, S, radius_px):
-    n = _lib.call("ps_splat_workspace_bytes", B, N, S, float(radius_px))
-    if n == 0:
-        raise RuntimeError("ps_splat_workspace_bytes: invalid sizes")
-    return _WS.get(device, n)
+    return _WS.query(device, "ps_splat_workspace_bytes", B, N, S, float(radius_px))
 
 
-_WS_BWD = _Workspace()     # the backward pass' two coefficient planes: kept apart, so that a forward between never regrows either
+def scene_workspace(device, B, cap, S, radius_px):
+    return _WS.get(device, _lib.call("ps_scene_workspace_bytes", B, cap, S, float(radius_px)))
 
 
 def splat_bwd_workspace(device, B, S, K):
-    n = _lib.call("ps_splat_bwd_workspace_bytes", B, S, K)
-    if n == 0:
-        raise RuntimeError("ps_splat_bwd_workspace_bytes: invalid sizes")
-    return _WS_BWD.get(device, n)
+    return _WS_BWD.query(device, "ps_splat_bwd_workspace_bytes", B, S, K)
 
 
 class _SplatFunction(torch.autograd.Function):
@@ -121,6 +107,12 @@ class RasterizePointsXYsBlending(nn.Module):
     def _opt(self, name, default):
         return getattr(self.opts, name, default) if self.opts is not None else default
 
+    def kernel_settings(self):
+        """What the kernels take from this module and its opts, with the reference's defaults (z_buffer_layers.py:12-53)"""
+        return SplatSettings(float(self.radius), int(self.points_per_pixel), float(self._opt("tau", 1.0)), int(self._opt("rad_pow", 2)),
+                             ACCUMULATION[self._opt("accumulation", "alphacomposite")],
+                             int(self._opt("background_smoothing_kernel_size", 13)))
+
     def forward(self, pts3D, src, return_debug=False):
         if src.dim() > 3:    # image-shaped input: (B,C,w,w) features with a (B,3,N) cloud, one row of points per w
             bs, c, w = src.shape[:3]
@@ -136,10 +128,7 @@ class RasterizePointsXYsBlending(nn.Module):
 
         B, N, C = bs, pts3D.size(1), src.size(1)
         if not return_debug and torch.is_grad_enabled() and (pts3D.requires_grad or src.requires_grad):
-            out, bg = _SplatFunction.apply(pts3D.float().contiguous(), src.float().contiguous(), int(image_size), self.radius,
-                                           int(self.points_per_pixel), self._opt("tau", 1.0), self._opt("rad_pow", 2),
-                                           ACCUMULATION[self._opt("accumulation", "alphacomposite")],
-                                           self._opt("background_smoothing_kernel_size", 13))
+            out, bg = _SplatFunction.apply(pts3D.float().contiguous(), src.float().contiguous(), int(image_size), *self.kernel_settings())
             return out, bg.view(torch.bool)
         caller_pts = pts3D
         pts = pts3D if (pts3D.is_contiguous() and pts3D.dtype == torch.float32) else pts3D.float().contiguous()
@@ -154,9 +143,7 @@ class RasterizePointsXYsBlending(nn.Module):
             zbuf = torch.empty(B, S, S, K, dtype=torch.float32, device=pts.device)
             dist = torch.empty(B, S, S, K, dtype=torch.float32, device=pts.device)
         ws = splat_workspace(pts.device, B, N, S, self.radius)
-        _lib.call("ps_splat_f32", pts, feat, B, N, C, S, float(self.radius), K, float(self._opt("tau", 1.0)), int(self._opt("rad_pow", 2)),
-                  ACCUMULATION[self._opt("accumulation", "alphacomposite")], int(self._opt("background_smoothing_kernel_size", 13)),
-                  out, bg, idx, zbuf, dist, ws, ws.numel())
+        _lib.call("ps_splat_f32", pts, feat, B, N, C, S, *self.kernel_settings(), out, bg, idx, zbuf, dist, ws, ws.numel())
         if pts is not caller_pts:  # keep the reference's visible side effect on the caller's tensor
             caller_pts[:, :, 0:2] = pts[:, :, 0:2].to(caller_pts.dtype)
         background_mask = bg.view(torch.bool)    # (k_dilate writes 0 / 1: the same bytes are the boolean mask)

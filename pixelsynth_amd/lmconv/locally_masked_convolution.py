@@ -17,15 +17,7 @@ from torch.nn.parameter import Parameter
 
 from .. import _lib
 
-_WS = {}
-
-
-def _workspace(device, nbytes):
-    t = _WS.get(device)
-    if t is None or t.numel() < nbytes:
-        t = torch.empty(int(nbytes), dtype=torch.uint8, device=device)
-        _WS[device] = t
-    return t
+_WS = _lib.Workspace()     # lmconv's own: the forward's and the backward's scratch, whichever is larger
 
 
 def compact_mask(mask, B, C_in):
@@ -57,7 +49,7 @@ def lmconv_forward(x, mask, weight, bias=None, dilation=1):
     wc = weight.float().contiguous()
     bc = None if bias is None else bias.float().contiguous()
     y = torch.empty(B, out_channels, H, W, dtype=torch.float32, device=x.device)
-    ws = _workspace(x.device, _lib.call("ps_lmconv_workspace_bytes", B, in_channels, out_channels, H, W))
+    ws = _WS.get(x.device, _lib.call("ps_lmconv_workspace_bytes", B, in_channels, out_channels, H, W))
     _lib.call("ps_lmconv_forward_f32", xc, m, stride, wc, bc, B, in_channels, out_channels, H, W, int(dilation), y, ws, ws.numel())
     return y
 
@@ -88,7 +80,7 @@ def lmconv_backward(grad_y, x, mask, weight, dilation=1, need_x=True, need_weigh
             stride = 0 if m.size(0) == 1 and B > 1 else 9 * H * W
             gw = torch.empty(Co, Ci, 3, 3, dtype=torch.float32, device=x.device) if need_weight else None
             gb = torch.empty(Co, dtype=torch.float32, device=x.device) if need_bias else None
-            ws = _workspace(x.device, _lib.call("ps_lmconv_bwd_workspace_bytes", B, Ci, Co, H, W)) if need_weight else None
+            ws = _WS.get(x.device, _lib.call("ps_lmconv_bwd_workspace_bytes", B, Ci, Co, H, W)) if need_weight else None
             _lib.call("ps_lmconv_grad_weight_f32", x.detach().float().contiguous() if need_weight else None, g, m if need_weight else None,
                       stride, B, Ci, Co, H, W, int(dilation), gw, gb, ws, ws.numel() if need_weight else 0)
     return gx, gw, gb

@@ -17,7 +17,7 @@ import torch
 import torch.nn as nn
 
 from .. import _lib
-from ..layers.z_buffer_layers import _WS, ACCUMULATION, RasterizePointsXYsBlending, splat_workspace
+from ..layers.z_buffer_layers import RasterizePointsXYsBlending, scene_workspace, splat_workspace
 
 EPS = 1e-2
 
@@ -145,9 +145,7 @@ class PtsManipulator(nn.Module):
             bg = torch.empty(bs, S, S, dtype=torch.uint8, device=src.device)
             ws = splat_workspace(src.device, bs, S * S, S, sp.radius)
             _lib.call("ps_project_splat_f32", _f32c(pred_pts), _f32c(src), _f32c(K), _f32c(K_inv), _f32c(RTinv_cam1), _f32c(RT_cam2), bs, c, S,
-                      float(sp.radius), int(sp.points_per_pixel), float(sp._opt("tau", 1.0)), int(sp._opt("rad_pow", 2)),
-                      ACCUMULATION[sp._opt("accumulation", "alphacomposite")], int(sp._opt("background_smoothing_kernel_size", 13)),
-                      out, bg, ws, ws.numel())
+                      *sp.kernel_settings(), out, bg, ws, ws.numel())
             return out, bg.view(torch.bool)    # (k_dilate writes 0 / 1: the same bytes are the boolean mask -- no conversion pass)
         if len(pred_pts.size()) > 3:
             pred_pts = pred_pts.view(bs, 1, -1)
@@ -243,13 +241,10 @@ class PtsManipulator(nn.Module):
                                f"state was created with cap = {state.cap}" + (f" (also scenes {over[1:]})" if over[1:] else ""))
         out = torch.empty(B, C, S, S, dtype=torch.float32, device=src.device)
         bg = torch.empty(B, S, S, dtype=torch.uint8, device=src.device)
-        nbytes = _lib.call("ps_scene_workspace_bytes", B, state.cap, S, float(sp.radius))
-        ws = _WS.get(src.device, nbytes)
+        ws = scene_workspace(src.device, B, state.cap, S, sp.radius)
         cur, other = state._cur, 1 - state._cur
         _lib.call("ps_scene_step_f32", _f32c(pred_pts), _f32c(src), mask, state._cloud[cur], state._feat[cur], state._cloud[other],
                   state._feat[other], state.count, _f32c(K), _f32c(K_inv), _f32c(RTinv_cam1), _f32c(RT_cam2), rt3, B, C, S, state.cap,
-                  max(prior), max(nxt), float(sp.radius), int(sp.points_per_pixel), float(sp._opt("tau", 1.0)), int(sp._opt("rad_pow", 2)),
-                  ACCUMULATION[sp._opt("accumulation", "alphacomposite")], int(sp._opt("background_smoothing_kernel_size", 13)),
-                  out, bg, ws, ws.numel())
+                  max(prior), max(nxt), *sp.kernel_settings(), out, bg, ws, ws.numel())
         state._cur, state.counts = other, nxt
         return out, bg.view(torch.bool)

@@ -1,5 +1,5 @@
 """Shared by tests/test_splat_routes_cpu.py and tests/test_splat_routes_gpu.py: a numpy mirror of the binning arithmetic of
-pixelsynth_amd/csrc/splat.hip, the compositing in float64 from the oracle's hit lists, and the table of cases the two tests walk.
+pixelsynth_amd/csrc/splat_math.h and splat_pipeline.h, the compositing in float64 from the oracle's hit lists, and the table of cases the two tests walk.
 No test in here, and nothing of the library is imported.
 
 Why a mirror.  Which kernel, and which branch of it, a call of the splat takes is decided by integers: tiles per frame, tiles per
@@ -18,16 +18,16 @@ from collections import namedtuple
 
 import numpy as np
 
-# --- constants of pixelsynth_amd/csrc/splat.hip, restated (line numbers of that file)
-TILE = 8                 # :30   pixels per tile edge
-SORT_SMALL_CAP = 512     # :33   keys one wave sorts in registers (k_sort_small); 64 / 128 / 256 / 512 pick 1 / 2 / 4 / 8 keys per lane (:437-440)
-SORT_BIG_CAP = 8192      # :34   keys a workgroup of k_sort_big sorts in LDS; longer lists are sorted in global memory (:452)
-LDS_TILES = 4096         # :180  tiles per frame up to which k_bin_count / k_bin_fill aggregate in LDS
-MAX_TPP = 9              # :181  tiles per point up to which k_bin_fill keeps LDS ranks
-BIN_THREADS = 256        # :188, :254  points per workgroup of k_bin_count / k_bin_fill
-SCAN_THREADS = 1024      # :226  threads of k_scan's one workgroup per frame: (NT + 1023) / 1024 counters each (:232)
-SORT_BIG_WGS = 128       # :857  workgroups of k_sort_big, grid-striding over the worklist (:449)
-DB_MAXW = 2048 // 64     # :734  words per row of k_dilate_bits (sizes that are a multiple of 64, :874)
+# --- constants of pixelsynth_amd/csrc/, restated (by name: splat_math.h's TILE, the others splat_pipeline.h's)
+TILE = 8                 # TILE            pixels per tile edge
+SORT_SMALL_CAP = 512     # SORT_SMALL_CAP  keys one wave sorts in registers (k_sort_small); 64 / 128 / 256 / 512 pick 1 / 2 / 4 / 8 keys per lane
+SORT_BIG_CAP = 8192      # SORT_BIG_CAP    keys a workgroup of k_sort_big sorts in LDS; longer lists are sorted in global memory
+LDS_TILES = 4096         # LDS_TILES       tiles per frame up to which k_bin_count / k_bin_fill aggregate in LDS
+MAX_TPP = 9              # MAX_TPP         tiles per point up to which k_bin_fill keeps LDS ranks
+BIN_THREADS = 256        # __launch_bounds__ of k_bin_count / k_bin_fill: points per workgroup
+SCAN_THREADS = 1024      # __launch_bounds__ of k_scan: threads of its one workgroup per frame, (NT + 1023) / 1024 counters each
+SORT_BIG_WGS = 128       # splat_core's launch of k_sort_big: its workgroups, grid-striding over the worklist
+DB_MAXW = 2048 // 64     # DB_MAXW         words per row of k_dilate_bits (splat_core takes it for sizes that are a multiple of 64)
 SORT_REG_CAPS = (64, 128, 256, SORT_SMALL_CAP)
 
 # --- tolerances (none of them measured on the kernels under test)
@@ -38,19 +38,19 @@ Bins = namedtuple("Bins", "tilesX NT hw max_tiles_pp counts foot")
 
 
 def plan_hw(radius_px):
-    """make_plan's hw (:780): the half width in pixels of the conservative box of a disc"""
+    """SplatGeom's hw (splat_math.h), which make_plan takes: the half width in pixels of the conservative box of a disc"""
     return np.float32(radius_px * 1.0001 + 0.01)
 
 
 def plan_max_tiles_pp(radius_px):
-    """make_plan's max_tiles_pp (:781-783): the slots per point of the key array"""
+    """SplatGeom's max_tiles_pp (splat_math.h), which make_plan takes: the slots per point of the key array"""
     span_px = int(2.0 * float(plan_hw(radius_px))) + 2
     span_t = (span_px + TILE - 2) // TILE + 1
     return span_t * span_t
 
 
 def _axis_range(p, S, hw):
-    """axis_range (:153-165) on an array of coordinates: (ok, lo_px, hi_px), fp32 throughout"""
+    """splat_math.h's axis_range on an array of coordinates: (ok, lo_px, hi_px), fp32 throughout"""
     f = np.float32
     with np.errstate(invalid="ignore", over="ignore"):
         c = ((p + f(1.0)) * f(S) - f(1.0)) * f(0.5)
@@ -64,9 +64,9 @@ def _axis_range(p, S, hw):
 
 
 def bins(pts, S, radius_px):
-    """pts (B,N,3) float32 AS THE CALLER HANDS THEM to the splat; the kernels bin them with x and y negated (k_negate_xy, :138), and so
+    """pts (B,N,3) float32 AS THE CALLER HANDS THEM to the splat; the kernels bin them with x and y negated (splat.hip's k_negate_xy), and so
     does this.  Returns Bins: tilesX, NT, hw, max_tiles_pp as make_plan has them, counts (B,NT) the length of every tile list, foot (B,N)
-    the tiles each point's box covers (0: culled) -- point_bbox (:167-175) and k_bin_count's loop (:208-213)."""
+    the tiles each point's box covers (0: culled) -- splat_math.h's point_bbox and the tile loop of splat_pipeline.h's k_bin_count."""
     pts = np.asarray(pts, np.float32)
     B, N, _ = pts.shape
     tilesX = (S + TILE - 1) // TILE
@@ -92,7 +92,7 @@ def bins(pts, S, radius_px):
 
 
 def fill_workgroups(b):
-    """Per workgroup of k_bin_fill (256 consecutive points of a cloud): does it take the direct path (:270-271, :278)?  (B, ceil(N/256))"""
+    """Per workgroup of k_bin_fill (256 consecutive points of a cloud): does it take the direct path (k_bin_fill's `fits` / `agg`)?  (B, ceil(N/256))"""
     B, N = b.foot.shape
     pad = (-N) % BIN_THREADS
     big = np.pad(b.foot > MAX_TPP, ((0, 0), (0, pad))).reshape(B, -1, BIN_THREADS).any(-1)
@@ -100,13 +100,13 @@ def fill_workgroups(b):
 
 
 def denom64(S, radius_px, rad_pow):
-    """pow(radius, rad_pow) as splat_core (:839-842) and the oracle round it: double, then float"""
+    """pow(radius, rad_pow) as SplatGeom (splat_math.h: denom) and the oracle round it: double, then float"""
     radius = radius_px / float(S) * 2.0
     return np.float64(np.float32(radius ** rad_pow))
 
 
 def recip_route(S, radius_px, rad_pow):
-    """splat_core's pow2 (:844): the kernels multiply by 1 / denom instead of dividing (RECIP)"""
+    """SplatGeom's pow2 (splat_math.h): the kernels multiply by 1 / denom instead of dividing (RECIP)"""
     return float(np.frexp(np.float32(denom64(S, radius_px, rad_pow)))[0]) == 0.5
 
 

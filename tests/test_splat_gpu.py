@@ -106,7 +106,7 @@ def test_degenerate_pileup_exercises_big_sort(N):
 @pytest.mark.parametrize("scale", [1.0, 50.0])
 def test_product_route_stops_a_walk_below_2_to_the_minus_23_transmittance(scale):
     """The product route (no idx / zbuf / dist asked for) stops a pixel's front-to-back walk once its transmittance is below 2^-23:
-    the hits behind can add at most that times max |feature| (csrc/splat.hip: k_composite).  A pile-up -- thousands of points in
+    the hits behind can add at most that times max |feature| (csrc/splat_pipeline.h: k_composite).  A pile-up -- thousands of points in
     one tile, far more than K = 128 hits per pixel, every walk cut short -- against the oracle, which walks all K: the error stays
     below 4e-7 x max |feature| whatever the features' magnitude (the route also takes the hardware's 1-ulp square root and fuses the
     accumulation's multiply-add: 1.5-2.7e-7 measured), and the background mask (one hit suffices) is the same bits."""
@@ -228,7 +228,7 @@ def test_forward_justpts_matterport_shaped_vs_oracle(golden_dir):
         s = pm.project_pts(tt(depth).view(B, 1, -1), *args)
         f2, bg2, idx, zbuf, dist = pm.splatter(s.permute(0, 2, 1).contiguous(), tt(img).view(B, 3, -1), return_debug=True)
         # (the route that emits idx / zbuf / dist walks EVERY hit; the product route stops a pixel's walk once its transmittance is below
-        # 2^-23, csrc/splat.hip: what is left can add less than that times max |feature| -- the mask is the same bits)
+        # 2^-23, csrc/splat_pipeline.h: what is left can add less than that times max |feature| -- the mask is the same bits)
         assert torch.allclose(f2, feat, rtol=0, atol=4e-7) and torch.equal(bg2, bg)
         assert np.array_equal(idx.cpu().numpy(), ref["idx"]) and np.array_equal(dist.cpu().numpy(), ref["dist"])
     assert 0.02 < ref["bg"].mean()

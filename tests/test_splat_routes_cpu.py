@@ -1,4 +1,4 @@
-"""The cases of tests/_splat_ref.py, checked without a GPU: every case reaches the branch of pixelsynth_amd/csrc/splat.hip it is there for
+"""The cases of tests/_splat_ref.py, checked without a GPU: every case reaches the branch of pixelsynth_amd/csrc/splat_pipeline.h it is there for
 (asserted with the numpy mirror of the binning, _splat_ref.bins), and its reference is usable -- the oracle's fp32 features lie within
 2e-6 x max |feature| of the float64 compositing of the oracle's own hit lists (5e-8 ... 1.0e-6 here, the largest at tau = 0.5), the mask
 has hit and missed pixels where the case looks at it, and pixels with K hits exist where the case is about the K cap.

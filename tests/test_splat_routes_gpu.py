@@ -1,4 +1,4 @@
-"""GPU: the binning, sort and composite routes of pixelsynth_amd/csrc/splat.hip that the parity tests of test_splat_gpu.py never take, on
+"""GPU: the binning, sort and composite routes of pixelsynth_amd/csrc/splat_pipeline.h that the parity tests of test_splat_gpu.py never take, on
 the cases of tests/_splat_ref.py (tests/test_splat_routes_cpu.py asserts, without a GPU, that every case reaches its branch).
 
 Debug route (return_debug=True): idx, zbuf, dist, the background mask and the negated points bit-exact against the C oracle, features at

@@ -1,18 +1,12 @@
-// Exhaustive check that the compositor's short square root (csrc/splat.hip: sqrt_rn_unit) equals sqrtf bit for bit on every float
-// in [2^-20, 2] (it is applied to values clamped to [1e-3, 1]).   hipcc --offload-arch=gfx950 -O3 -ffp-contract=off tools/sqrt_probe.hip -o tools/sqrt_probe.bin
+// Exhaustive check that the compositor's short square root (csrc/splat_math.h: sqrt_rn_unit, included here: the probe tests the compositor's own) equals sqrtf bit for bit on every float
+// in [2^-20, 2] (it is applied to values clamped to [1e-3, 1]).   hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -Ipixelsynth_amd/csrc tools/sqrt_probe.hip -o tools/sqrt_probe.bin
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdint>
 #include <cstring>
-__device__ __forceinline__ float sqrt_rn_unit(float x)
-{
-    const float s = __builtin_amdgcn_sqrtf(x);
-    const float sm = __uint_as_float(__float_as_uint(s) - 1u), sp = __uint_as_float(__float_as_uint(s) + 1u);
-    const float em = __builtin_fmaf(-sm, s, x), ep = __builtin_fmaf(-sp, s, x);
-    float r = em <= 0.0f ? sm : s;
-    r = ep > 0.0f ? sp : r;
-    return r;
-}
+
+#include "splat_math.h"
+
 __global__ void k(uint32_t lo, uint32_t n, unsigned long long *bad, uint32_t *first)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
