@@ -350,7 +350,9 @@ int ps_zbuffer_scatter_sorted_f32(const int64_t *order, const int32_t *ys, const
  * nearest codebook column.  z: layout 0 = (N,D) row-major (the reference's `flatten`), layout 1 = (B,D,HW) as the
  * 1x1 conv in front of it leaves it (row n = b*HW + p; HW given, N = B*HW); embed (D,K) f32 (the reference's
  * `embed` buffer); idx (N) int32; mindist (N) f32 or NULL.  D <= 64.
- *   dist[n][k] = (|z_n|^2 - 2 z_n.e_k) + |e_k|^2, sums in ascending d (fused multiply-adds); ties -> smallest k. */
+ *   dist[n][k] = (|z_n|^2 - 2 z_n.e_k) + |e_k|^2, sums in ascending d (fused multiply-adds); ties -> smallest k.
+ *   idx[n] is always in [0, K); a row with no distance below +inf (a NaN or +-inf in z_n, |z_n|^2 beyond fp32) gives 0, as the
+ *   reference's `max` does for an all-NaN row, and mindist[n] = +inf. */
 int ps_vq_nearest_f32(const float *z, int layout, const float *embed, int N, int D, int K, int HW,
                       int32_t *idx, float *mindist, void *stream);
 

@@ -166,3 +166,15 @@ def masks_for_background(bg, obs=32):
                 mask_init=unfolded_masks(order, obs, obs, 3, 1, "A"),
                 mask_undilated=unfolded_masks(order, obs, obs, 3, 1, "B"),
                 mask_dilated=unfolded_masks(order, obs, obs, 3, 2, "B"))
+
+
+def vq_nearest(z, embed):
+    """ps_vq_nearest_f32's definition (include/pixelsynth_hip.h) in plain C: z (N,D) f32, embed (D,K) f32 ->
+    (idx (N,) int32 in [0, K), mindist (N,) f32); a row with no distance below +inf gives (0, +inf)."""
+    z, embed = _f32(z), _f32(embed)
+    (N, D), K = z.shape, embed.shape[1]
+    assert embed.shape[0] == D and K > 0
+    idx = np.empty(N, np.int32)
+    mindist = np.empty(N, np.float32)
+    lib().ps_oracle_vq_nearest(_p(z), _p(embed), ctypes.c_int(N), ctypes.c_int(D), ctypes.c_int(K), _p(idx), _p(mindist))
+    return idx, mindist

@@ -10,6 +10,8 @@
 // Definition of the distance (the reference leaves the summation order to the BLAS it runs on):
 //   dist[n][k] = (zz[n] - 2 * dot[n][k]) + ee[k],  zz / ee / dot accumulated in ascending d with fused multiply-adds,
 //   idx[n] = the smallest k among the minimisers of dist[n][.]   (torch.max returns the first maximum of -dist)
+//   idx[n] is always in [0, K); a row with no distance below +inf gives 0, as the reference's `max` does for an all-NaN row
+//   (its mindist is +inf).  Consumers index with the code unguarded (the PixelCNN engine's uinit_from_codes, F.embedding).
 #include "ps_common.h"
 
 namespace {
@@ -83,7 +85,7 @@ __global__ __launch_bounds__(VQ_THREADS) void k_vq_nearest(const float *z, int l
             const int ok = sBestK[t][w];
             if (od < bd || (od == bd && ok < bk)) { bd = od; bk = ok; }
         }
-        idx[n0 + t] = bk;
+        idx[n0 + t] = (unsigned)bk < (unsigned)K ? bk : 0;   // nothing compared below +inf (NaN, +-inf, |z|^2 beyond fp32): code 0
         if (mindist) mindist[n0 + t] = bd;
     }
 }
