@@ -1,11 +1,12 @@
 // zbuffer.hip -- the hard z-buffer of DepthManipulator for gfx950 (MI355X), and ps_read_status, behind the C ABI of
-// include/pixelsynth_hip.h (libpixelsynth_hip.so).  It shares the projection's products and camera prologue with the soft splat
-// (csrc/splat_math.h) and nothing else.  The tail of k_zb_project is its own on purpose: no EPS overwrite of X[2], literal pixels.
+// include/pixelsynth_hip.h (libpixelsynth_hip.so).  It shares the camera prologue with the soft splat (csrc/splat_math.h) and
+// nothing else.  The rest of k_zb_project is its own on purpose: fused matrix-vector products, no EPS overwrite of X[2], literal pixels.
 //
 // Hard z-buffer of DepthManipulator.project_zbuffer (models/projection/depth_manipulator.py:37-104).
 //   k_zb_project   :43-66 -- one thread per source pixel: p = grid * depth (w = 1), X = K (RT2 RT1inv) Kinv p in the
-//                  association order of the reference's products (mul, add, ascending k: mat4_vec and load_cams of csrc/splat_math.h; this unit is built with
-//                  -ffp-contract=off), EPS rule, the literal (sampler + 1) * 128 pixel mapping, .long().clamp(0, 255) and the
+//                  association order of the reference's products, ascending k (RT: mul, add, load_cams of csrc/splat_math.h; the
+//                  three matrix-vector products: mat4_vec_fma below; this unit is built with -ffp-contract=off, so the only fused
+//                  operations are the ones written out), EPS rule, the literal (sampler + 1) * 128 pixel mapping, .long().clamp(0, 255) and the
 //                  out-of-range flag (:86-87).  Everything by ORIGINAL point position; the sort by z stays with the caller.
 //   k_zb_test / k_zb_write   the z-test: the reference scatters the sorted points with an indexed assignment, so that of
 //                  several points on one pixel the LAST one in sorted order stays (sequential semantics of torch's CPU
@@ -20,6 +21,22 @@
 extern "C" {
 
 namespace {
+// One row of the reference's bmm as a BLAS sgemm runs it on the CPU: a product and three fused multiply-adds, ascending k.  With
+// splat_math.h's mat4_vec (every multiply and add rounded) the projected z of every third or fourth point is a last bit off the
+// reference's, and where two points of one pixel lie that close in z the sort puts them the other way round and the wrong one stays:
+// 12 sampler entries of the fixture (tests/golden/zbuffer.npz, whole arrays).  With this chain none differs (tests/_zbuffer_ref.py).
+__device__ __forceinline__ void mat4_vec_fma(const float *M, const float *v, float *o)
+{
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        float acc = M[i * 4 + 0] * v[0];
+        acc = __builtin_fmaf(M[i * 4 + 1], v[1], acc);
+        acc = __builtin_fmaf(M[i * 4 + 2], v[2], acc);
+        acc = __builtin_fmaf(M[i * 4 + 3], v[3], acc);
+        o[i] = acc;
+    }
+}
+
 __global__ __launch_bounds__(256) void k_zb_project(const float *__restrict__ depth, const float *__restrict__ grid,
                                                     const float *__restrict__ K, const float *__restrict__ Kinv __attribute__((nonnull)),
                                                     const float *__restrict__ RT1inv, const float *__restrict__ RT2, int N,
@@ -33,15 +50,18 @@ __global__ __launch_bounds__(256) void k_zb_project(const float *__restrict__ de
     if (n >= N) return;
     const float d = depth[(size_t)b * N + n];
     float p[4] = {grid[n] * d, grid[N + n] * d, grid[2 * (size_t)N + n] * d, 1.0f}, c[4], w[4], X[4];
-    mat4_vec(sKinv, p, c);
-    mat4_vec(sRT, c, w);
-    mat4_vec(sK, w, X);
+    mat4_vec_fma(sKinv, p, c);
+    mat4_vec_fma(sRT, c, w);
+    mat4_vec_fma(sK, w, X);
     const bool bad = fabsf(X[2]) < PS_EPS;
     float sx = X[0] / -X[2], sy = X[1] / -X[2];
     if (bad) { sx = -10.0f; sy = -10.0f; }
     sy = -sy;
     const float tx = (sx + 1.0f) * 128.0f, ty = (sy + 1.0f) * 128.0f;
-    // .long() truncates towards zero, then clamp(0, 255); NaN -> 0 like the reference's LONG_MIN
+    // .long() truncates towards zero, then clamp(0, 255), written so that no cast is undefined: not t > 0 (NaN included) -> 0,
+    // t >= 255 -> 255 (saturating: +inf and every finite t beyond int64 too), else (int)t.  Where the reference's cast is defined this
+    // is its value.  Where it is not -- NaN, +-inf, |t| >= 2^63 -- x86 hands back LONG_MIN, which clamps to 0: NaN and the negative
+    // side agree with that, +inf and t >= 2^63 do not (the reference lands them on pixel 0, this on 255; both flag them out of range).
     auto pixel = [](float t) { return !(t > 0.0f) ? 0 : t >= 255.0f ? 255 : (int)t; };
     const size_t o = (size_t)b * N + n;
     zproj[o] = X[2];
