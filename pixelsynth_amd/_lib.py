@@ -190,10 +190,20 @@ VQ_TRAIN_PROTOS = {
     "ps_vq_train_backward_f32": (RC, [c_void_p] * 5 + [c_int] * 3 + [c_void_p, STREAM]),
 }
 
+# libpixelsynth_conv_bwd.so (include/pixelsynth_conv_bwd.h): the backward pass of the split-fp16 3 x 3 convolution
+CONV_BWD_PROTOS = {
+    "ps_conv_bwd_last_error": (ctypes.c_char_p, []),
+    "ps_conv3x3_bwd_workspace_bytes": (c_size_t, [c_int] * 5),
+    "ps_conv3x3_bwd_parts": (c_int, [c_int] * 5),
+    "ps_conv3x3_bwd_prepare_f32": (RC, [c_void_p] + [c_int] * 4 + [c_void_p] * 4 + [c_size_t, STREAM]),
+    "ps_conv3x3_grad_weight_f16x3": (RC, [c_void_p] * 3 + [c_int] * 5 + [c_void_p] * 3 + [c_size_t, STREAM]),
+    "ps_conv3x3_bwd_unscale_f32": (RC, [c_void_p, c_size_t, c_void_p, STREAM]),
+}
+
 # short name of _libraries.LIBRARIES -> its prototype table; _OWNER: entry point -> the table entry of its library, built once
 PROTOS = {"hip": _PROTOS, "percsim": PERCSIM_PROTOS, "consistency": CONSISTENCY_PROTOS, "fid": FID_PROTOS, "scene": SCENE_PROTOS,
           "plan": PLAN_PROTOS, "rank": RANK_PROTOS, "rank_groups": RANK_GROUPS_PROTOS, "nll": NLL_PROTOS, "lmconv_bwd": LMCONV_BWD_PROTOS, "splat_bwd": SPLAT_BWD_PROTOS,
-          "vq_train": VQ_TRAIN_PROTOS}
+          "vq_train": VQ_TRAIN_PROTOS, "conv_bwd": CONV_BWD_PROTOS}
 _ENTRIES = {e.name: e for e in _libraries.LIBRARIES}
 assert set(PROTOS) == set(_ENTRIES)
 _OWNER = {fn: _ENTRIES[name] for name, table in PROTOS.items() for fn in table}

@@ -28,7 +28,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import f16x3
-from .f16x3 import _FORCED_CONV, check_f16x3_overflow, decoder_conv, flag as _overflow_flag  # noqa: F401  (the names bench.py and the tests use)
+from .f16x3 import _FORCED_CONV, check_f16x3_overflow, decoder_conv, decoder_conv_train, flag as _overflow_flag  # noqa: F401  (the names bench.py and the tests use)
 
 NOISE_SZ = 20
 
@@ -273,15 +273,19 @@ def conv1x1(conv, x):
     return y
 
 
-def _conv_split(conv, x, mode=None):
+def _conv_split(conv, x, mode=None, opt=None):
     """conv(x) as (output WITHOUT the bias, bias) on the inference GPU path -- torch adds a convolution's bias in a pass
     of its own; here the per-channel constant rides along in whatever pass consumes the output (csrc/nets.hip).  Elsewhere
     (CPU, autograd, channel counts the kernels do not take): (conv(x), None).  mode "f16x3": a 1 x 1 convolution through
-    csrc/conv1x1.hip instead of torch (MIOpen)."""
+    csrc/conv1x1.hip instead of torch (MIOpen).  In grad mode with the training opt-in of `opt` (f16x3.train_mode) a wide 3 x 3
+    convolution goes through f16x3.conv3x3_train (_f16x3_train_conv)."""
     if mode == "f16x3":
         y = conv1x1(conv, x)
         if y is not None:
             return y, conv.bias
+    y = _f16x3_train_conv(conv, x, opt)
+    if y is not None:
+        return y, None
     if conv.bias is None or torch.is_grad_enabled() or not _is_nhwc_cuda(x) or conv.out_channels % 4:
         return _conv2d_batches(conv, x, conv.out_channels, conv.stride[0]), None
     weight = _plain_conv_weight(conv, x)
@@ -305,6 +309,27 @@ def _f16x3_takes(conv, x):
             and conv.groups == 1 and conv.in_channels % 32 == 0 and conv.out_channels % 64 == 0
             and _is_nhwc_cuda(x) and x.size(2) % 16 == 0 and x.size(3) % 16 == 0 and x.size(2) * x.size(3) * x.size(1) < 2 ** 31
             and not torch.is_grad_enabled())
+
+
+def _f16x3_train_conv(conv, x, opt=None):
+    """conv(x) WITH its bias through f16x3.conv3x3_train -- forward and backward pass on the fp16 matrix pipe -- or None: only in grad mode,
+    only under the opt-in (decoder_conv_train("f16x3") / opt.decoder_conv_train / PS_DECODER_CONV_TRAIN; the default is "fp32"), not where
+    decoder_conv("fp32") or the options send the decoder's convolutions through torch, and only for a convolution _f16x3_takes would
+    take without autograd whose Ci is a multiple of 64 as well.  The weight is the module's own (with spectral norm: as its pre-hook
+    leaves it, which is differentiable in training mode) and is packed at every call: training weights change every step."""
+    if not (torch.is_grad_enabled() and f16x3.train_mode(opt) == "f16x3" and _conv_mode(opt) == "f16x3" and type(conv) is nn.Conv2d
+            and conv.kernel_size == (3, 3) and conv.stride == (1, 1) and conv.padding == (1, 1) and conv.dilation == (1, 1)
+            and conv.groups == 1 and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4
+            and f16x3.train_takes(conv.in_channels, conv.out_channels, x.size(2), x.size(3))):
+        return None
+    weight = _plain_conv_weight(conv, x)
+    if weight is None or weight.dtype != torch.float32 or weight.device != x.device:
+        return None
+    x = x.contiguous(memory_format=torch.channels_last)      # (what torch's norm + ReLU in front hands over usually is already)
+    try:
+        return f16x3.conv3x3_train(x, weight, conv.bias)
+    except ValueError:      # a weight fp16 cannot hold: torch, on the weight already normalised (the pre-hook has run once)
+        return F.conv2d(x, weight, conv.bias, 1, 1)
 
 
 def _thin_conv(conv, x, scale=None, shift=None):
@@ -372,9 +397,11 @@ def _resample_sum(kind, a, b, bias=None, post=None):
     """_resample(kind, a + bias) + _resample(kind, b) -- blocks.py:61-73 -- as ONE pass through csrc/nets.hip on the GPU
     (`bias`: per-channel constant still missing from the inputs, see _conv_split).  b = None: a alone -- resampling is linear, so
     a caller that already holds the SUM of the two branches resamples once.  post ('Down' only): a tensor of the output's shape added
-    after the pooling."""
+    after the pooling.  Through torch where autograd follows an operand."""
     from .. import _lib
-    if (not (_is_nhwc_cuda(a) if b is None else _is_nhwc_cuda(a, b)) or (b is not None and a.shape != b.shape)
+    # (an operand that autograd follows goes through torch: the HIP passes are forward-only and would cut the graph)
+    graph = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (a, b, bias, post))
+    if (graph or not (_is_nhwc_cuda(a) if b is None else _is_nhwc_cuda(a, b)) or (b is not None and a.shape != b.shape)
             or (kind and kind != "Up" and (a.size(2) % 2 or a.size(3) % 2)) or (b is None and not kind)):
         if bias is not None:
             a = a + bias.view(1, -1, 1, 1)
@@ -459,7 +486,7 @@ class ResNet_Block(nn.Module):
             if y is not None:
                 return y, conv.bias, False
             return _conv_split(conv, self._noise_affine(layer, x, None, None, affine=(scale, shift))) + (False,)
-        return _conv_split(conv, self._noise_affine(layer, x, noise, bias)) + (False,)
+        return _conv_split(conv, self._noise_affine(layer, x, noise, bias), opt=self.opt) + (False,)
 
     def forward(self, x, noise=(None, None)):
         a, ba, _ = self._norm_relu_conv(self.ch_a[0], self.ch_a[2], x, noise[0])

@@ -4,7 +4,13 @@ gives a wrong output and sets a per-device flag (csrc/conv_thin.hip's 4 -> 64 la
 outermost scope clears the flag (an earlier, unchecked pass's is not this pass's), runs fn, synchronises, and if the flag is set warns and
 runs fn again under decoder_conv("fp32"), every convolution through torch.  Inner scopes do nothing, so a pass made of guarded calls is
 checked once.  A scope must not enclose a collective: a rerun on one rank would run it twice.
+
+Training (csrc/conv_bwd.hip, libpixelsynth_conv_bwd.so): conv3x3_train(x, weight, bias) is the plain convolution as a
+torch.autograd.Function whose backward pass runs on the same matrix pipe -- grad_y scaled by a power of two on the device, grad_weight
+as a GEMM over the pixels, grad_input as the forward kernel on the flipped, transposed weight.  It is opt-in for the decoder's blocks:
+decoder_conv_train("f16x3"), opt.decoder_conv_train or PS_DECODER_CONV_TRAIN; the default "fp32" leaves every call where it is.
 """
+import os
 import warnings
 
 import torch
@@ -37,6 +43,39 @@ class decoder_conv:
     def __exit__(self, *exc):
         _FORCED_CONV.pop()
         return False
+
+
+def _env_train_mode(environ=None):
+    """PS_DECODER_CONV_TRAIN of `environ` (the process's): "fp32" unless set"""
+    return (os.environ if environ is None else environ).get("PS_DECODER_CONV_TRAIN", "fp32")
+
+
+_FORCED_TRAIN = []  # decoder_conv_train(mode) in effect, innermost last
+DECODER_CONV_TRAIN = _env_train_mode()   # "fp32" (training convolutions through torch autograd) | "f16x3" (conv3x3_train)
+
+
+class decoder_conv_train:
+    """with decoder_conv_train("f16x3"): ... -- in grad mode the decoder blocks' wide 3 x 3 convolutions (Ci and Co multiples of 64, H and
+    W multiples of 16) inside go through conv3x3_train; "fp32": through torch autograd, whatever the options say."""
+
+    def __init__(self, mode):
+        if mode not in ("f16x3", "fp32"):
+            raise ValueError("decoder_conv_train: 'f16x3' or 'fp32'")
+        self.mode = mode
+
+    def __enter__(self):
+        _FORCED_TRAIN.append(self.mode)
+        return self
+
+    def __exit__(self, *exc):
+        _FORCED_TRAIN.pop()
+        return False
+
+
+def train_mode(opt=None):
+    """Which route a decoder block's 3 x 3 convolution takes in grad mode: decoder_conv_train(...) in effect, else opt.decoder_conv_train,
+    else PS_DECODER_CONV_TRAIN ("fp32")."""
+    return _FORCED_TRAIN[-1] if _FORCED_TRAIN else (getattr(opt, "decoder_conv_train", None) or DECODER_CONV_TRAIN)
 
 
 def flag(device):
@@ -81,10 +120,11 @@ def checked(device, fn, check=True):
         _open.discard(key)
 
 
-def pack3x3(weight, bias=None, s2d=False, d2s=False):
+def pack3x3(weight, bias=None, s2d=False, d2s=False, check=True):
     """A (Co, Ci, 3, 3) fp32 CUDA weight (and (Co) bias) packed for conv3x3, Co padded to a multiple of 64 (the first `live` channels are
     the layer's); s2d / d2s: for a space-to-depth input (Ci / 4 a multiple of 32) / a depth-to-space output (Co / 4 a multiple of 64).
-    ValueError for a shape the kernel does not take or a weight fp16 cannot hold (synchronises to find out): the caller goes through torch."""
+    ValueError for a shape the kernel does not take or a weight fp16 cannot hold (synchronises to find out): the caller goes through torch.
+    check=False: values that were looked at before (the backward pass packs the forward's weight flipped): nothing is read back."""
     Co, Ci = weight.shape[:2]
     if Ci % 32 or (s2d and Ci % 128) or (d2s and Co % 256):
         raise ValueError(f"split-fp16 convolution: {Co} x {Ci} channels (s2d {s2d}, d2s {d2s})")
@@ -92,9 +132,10 @@ def pack3x3(weight, bias=None, s2d=False, d2s=False):
     if Cop != Co:
         weight = torch.cat([weight, weight.new_zeros(Cop - Co, Ci, 3, 3)])
     wl = weight.permute(0, 2, 3, 1).contiguous()       # (Co, 3, 3, Ci): no copy for a channels_last weight
-    top = float(wl.abs().max())
-    if not (top == top and top < 6.0e4):
-        raise ValueError("split-fp16 convolution: a weight fp16 cannot hold")
+    if check:
+        top = float(wl.abs().max())
+        if not (top == top and top < 6.0e4):
+            raise ValueError("split-fp16 convolution: a weight fp16 cannot hold")
     packed = torch.empty(_lib.call("ps_conv3x3_f16x3_packed_bytes", Cop, Ci), dtype=torch.uint8, device=weight.device)
     _lib.call("ps_conv3x3_f16x3_pack", wl, Cop, Ci, packed)
     if bias is not None:
@@ -102,10 +143,10 @@ def pack3x3(weight, bias=None, s2d=False, d2s=False):
     return dict(packed=packed, Ci=Ci, Co=Cop, live=Co, bias=bias, s2d=s2d, d2s=d2s)
 
 
-def conv3x3(x, p, scale=None, shift=None, bias=None, res=None):
+def conv3x3(x, p, scale=None, shift=None, bias=None, res=None, overflow=None):
     """conv3x3(act(x)) + bias + res (ps_conv3x3_f16x3_ex_nhwc) of a pack3x3 layer on x (B, Ci, H, W) channels_last fp32 -- (B, Ci / 4, 2 H,
     2 W) for s2d --, act(x) = max(x * scale - shift, 0) (scale / shift (B, Ci)) or x; bias (Co) defaults to the layer's, res is NHWC.
-    -> y (B, Co, H, W) channels_last, (B, Co / 4, 2 H, 2 W) for d2s."""
+    -> y (B, Co, H, W) channels_last, (B, Co / 4, 2 H, 2 W) for d2s.  overflow: the int32 (1,) word the kernel raises instead of flag(x.device)."""
     B, C, H, W = x.shape
     if p["s2d"]:
         C, H, W = 4 * C, H // 2, W // 2
@@ -114,5 +155,75 @@ def conv3x3(x, p, scale=None, shift=None, bias=None, res=None):
     y = torch.empty(shape, dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
     bias = p["bias"] if bias is None else bias
     _lib.call("ps_conv3x3_f16x3_ex_nhwc", x, scale, shift, p["packed"], bias, res, B, H, W, C, p["Co"], p["live"], int(p["s2d"]),
-              int(p["d2s"]), y, flag(x.device))
+              int(p["d2s"]), y, flag(x.device) if overflow is None else overflow)
     return y
+
+
+# ---- training: the plain convolution with its backward pass (csrc/conv_bwd.hip) ------------------------------------------------------------
+_WS = _lib.Workspace()
+_grad_flags = {}    # str(device) -> int32 (1,): what the forward kernel raises while it convolves a GRADIENT (never read: see _Conv3x3Train)
+
+
+def train_takes(Ci, Co, H, W):
+    """The sizes conv3x3_train takes: H and W multiples of 16, Ci and Co multiples of 64, a frame within 32-bit offsets"""
+    return Ci > 0 and Co > 0 and Ci % 64 == 0 and Co % 64 == 0 and H > 0 and W > 0 and H % 16 == 0 and W % 16 == 0 and H * W * max(Ci, Co) < 2 ** 31
+
+
+class _Conv3x3Train(torch.autograd.Function):
+    """The forward pass is pack3x3 + conv3x3: the bits of the no-grad route.  x and the weight are saved, no packed copy.  The backward
+    pass reads nothing back and does not synchronise: grad_y is scaled on the device by the power of two that brings its largest
+    magnitude into [2^14, 2^15) (gradients are far below the 2^-3 down to which the fp16 split keeps its 22 bits), the results are
+    multiplied by its inverse.  grad_input is the forward kernel on the scaled grad_y with W'[c, t, o] = W[o, 8 - t, c]; what that kernel
+    raises for a gradient that is not finite goes to a word of its own -- the outputs it reaches are not finite, which is there to see, and
+    flag(device) keeps speaking of activations alone (the grad_weight kernel raises it for an x beyond fp16's range, as the forward did)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        y = conv3x3(x, pack3x3(weight.detach()), bias=None if bias is None else bias.detach().contiguous())
+        ctx.save_for_backward(x, weight)
+        ctx.has_bias = bias is not None
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_y):
+        x, weight = ctx.saved_tensors
+        B, Ci, H, W = x.shape
+        Co, dev = weight.size(0), x.device
+        need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.has_bias and ctx.needs_input_grad[2]
+        g = grad_y.to(torch.float32).contiguous(memory_format=torch.channels_last)       # (a sliced or expanded grad_y: one copy)
+        ws = _WS.query(dev, "ps_conv3x3_bwd_workspace_bytes", B, H, W, Ci, Co)
+        gs = torch.empty_like(g)                                                          # (preserves channels_last)
+        scale2 = torch.empty(2, dtype=torch.float32, device=dev)
+        gb = torch.empty(Co, dtype=torch.float32, device=dev) if need_b else None
+        _lib.call("ps_conv3x3_bwd_prepare_f32", g, B, H, W, Co, gs, scale2, gb, ws, ws.numel())
+        gx = gw = None
+        if need_w:
+            gw = torch.empty((Co, 3, 3, Ci), dtype=torch.float32, device=dev)
+            _lib.call("ps_conv3x3_grad_weight_f16x3", x, gs, scale2, B, H, W, Ci, Co, gw, flag(dev), ws, ws.numel())
+            gw = gw.permute(0, 3, 1, 2)                                                   # (Co, Ci, 3, 3): a view
+        if need_x:
+            key = str(dev)
+            if key not in _grad_flags:
+                _grad_flags[key] = torch.zeros(1, dtype=torch.int32, device=dev)
+            flipped = pack3x3(weight.detach().flip(2, 3).transpose(0, 1), check=False)    # (the forward's pack3x3 looked at these values)
+            gx = conv3x3(gs, flipped, overflow=_grad_flags[key])
+            _lib.call("ps_conv3x3_bwd_unscale_f32", gx, gx.numel(), scale2)
+        return gx, gw, gb
+
+
+def conv3x3_train(x, weight, bias=None):
+    """conv2d(x, weight, bias, stride 1, padding 1) through the split-fp16 kernel, differentiable once in x, weight and bias.
+    x (B, Ci, H, W) channels_last fp32 on the device, weight (Co, Ci, 3, 3) in any memory format, bias (Co) or None; train_takes(Ci, Co,
+    H, W) sizes.  ValueError for anything else, or for a weight fp16 cannot hold (the forward's pack3x3 synchronises to find out): the
+    caller goes through torch.  An activation beyond fp16's range raises flag(x.device), as in the no-grad route: checked() or
+    check_f16x3_overflow() is the caller's."""
+    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.is_contiguous(memory_format=torch.channels_last)):
+        raise ValueError("conv3x3_train: x must be a channels_last fp32 tensor (B, Ci, H, W) on the device")
+    if not (weight.dim() == 4 and tuple(weight.shape[1:]) == (x.size(1), 3, 3) and weight.dtype == torch.float32 and weight.device == x.device
+            and train_takes(x.size(1), weight.size(0), x.size(2), x.size(3))):
+        raise ValueError(f"conv3x3_train: weight {tuple(weight.shape)} on x {tuple(x.shape)}: (Co, Ci, 3, 3) fp32 on x's device, Ci and Co "
+                         "multiples of 64, H and W multiples of 16 required")
+    if bias is not None and not (bias.shape == (weight.size(0),) and bias.dtype == torch.float32 and bias.device == x.device):
+        raise ValueError("conv3x3_train: bias must be (Co) fp32 on x's device")
+    return _Conv3x3Train.apply(x, weight, bias)
