@@ -200,10 +200,20 @@ CONV_BWD_PROTOS = {
     "ps_conv3x3_bwd_unscale_f32": (RC, [c_void_p, c_size_t, c_void_p, STREAM]),
 }
 
+# libpixelsynth_norm_train.so (include/pixelsynth_norm_train.h): the noise-conditioned batch norm in training mode
+NORM_TRAIN_PROTOS = {
+    "ps_norm_train_last_error": (ctypes.c_char_p, []),
+    "ps_norm_train_workspace_bytes": (c_size_t, [c_int] * 3),
+    "ps_norm_train_parts": (c_int, [c_int] * 3),
+    "ps_norm_train_stats_f32": (RC, [c_void_p, c_void_p] + [c_int] * 3 + [c_float] * 3 + [c_void_p] * 6 + [c_size_t, STREAM]),
+    "ps_norm_train_apply_f32": (RC, [c_void_p] * 5 + [c_int] * 4 + [c_void_p, STREAM]),
+    "ps_norm_train_backward_f32": (RC, [c_void_p] * 6 + [c_int] * 4 + [c_void_p] * 4 + [c_size_t, STREAM]),
+}
+
 # short name of _libraries.LIBRARIES -> its prototype table; _OWNER: entry point -> the table entry of its library, built once
 PROTOS = {"hip": _PROTOS, "percsim": PERCSIM_PROTOS, "consistency": CONSISTENCY_PROTOS, "fid": FID_PROTOS, "scene": SCENE_PROTOS,
           "plan": PLAN_PROTOS, "rank": RANK_PROTOS, "rank_groups": RANK_GROUPS_PROTOS, "nll": NLL_PROTOS, "lmconv_bwd": LMCONV_BWD_PROTOS, "splat_bwd": SPLAT_BWD_PROTOS,
-          "vq_train": VQ_TRAIN_PROTOS, "conv_bwd": CONV_BWD_PROTOS}
+          "vq_train": VQ_TRAIN_PROTOS, "conv_bwd": CONV_BWD_PROTOS, "norm_train": NORM_TRAIN_PROTOS}
 _ENTRIES = {e.name: e for e in _libraries.LIBRARIES}
 assert set(PROTOS) == set(_ENTRIES)
 _OWNER = {fn: _ENTRIES[name] for name, table in PROTOS.items() for fn in table}

@@ -18,8 +18,10 @@ Same constructor arguments, attribute / parameter names and shapes as the refere
   * `ResNetDecoder.forward(..., noise=)` takes the noise draws explicitly (a list of (B,20) tensors, two per block) so
     a run is reproducible and comparable with the reference; without it the draws come from torch.randn as there.
 
-Training-mode batch statistics are supported for the plain BatchNorm2d layers (torch's own); the noise-conditioned
-layers implement the stored-statistics (eval) form only -- this repository does not train.
+Training: the plain BatchNorm2d layers are torch's own.  The noise-conditioned layers in train() normalise on batch statistics and
+update the stored ones (the running average, or standing sums with bn.accumulate_standing) through norm_train.batch_norm_train:
+csrc/norm_train.hip -- statistics, norm + ReLU and their backward pass -- for channels-last fp32 activations on the GPU, the torch formula
+elsewhere or under decoder_norm_train("torch").  In eval() every path is the stored-statistics form above, untouched.
 """
 import os
 
@@ -27,7 +29,8 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import f16x3
+from . import f16x3, norm_train
+from .norm_train import decoder_norm_train  # noqa: F401
 from .f16x3 import _FORCED_CONV, check_f16x3_overflow, decoder_conv, decoder_conv_train, flag as _overflow_flag  # noqa: F401  (the names bench.py and the tests use)
 
 NOISE_SZ = 20
@@ -60,7 +63,8 @@ def _norm_layer(opt):
 
 
 class bn(nn.Module):
-    """Stored statistics of the BigGAN-style batch norm (normalization.py:117-166); buffers only."""
+    """The BigGAN-style batch norm (normalization.py:117-166); buffers only.  eval(): the stored statistics; train(): the batch's, the
+    stored ones updated (networks/norm_train.py)."""
 
     def __init__(self, num_channels, eps=1e-5, momentum=0.1):
         super().__init__()
@@ -69,17 +73,31 @@ class bn(nn.Module):
         self.register_buffer("stored_var", torch.ones(num_channels))
         self.register_buffer("accumulation_counter", torch.zeros(1))
 
-    def scale_shift(self, gain, bias):
-        """y = x * scale - shift with gain/bias (B or 1, C, 1, 1) folded in (fused_bn, normalization.py:170-184)."""
+    def reset_stats(self):
+        """Zero the standing statistics and their counter (before accumulate_standing passes)"""
+        with torch.no_grad():
+            self.stored_mean.zero_()
+            self.stored_var.zero_()
+            self.accumulation_counter.zero_()
+
+    def scale_shift(self, gain, bias, x=None, pend=None):
+        """y = x * scale - shift with gain/bias (B or 1, C, 1, 1) folded in (fused_bn, normalization.py:170-184).  In training mode the
+        statistics are those of the activation `x` (through torch; the stored ones move, `pend` -- a bias still missing from x -- going
+        into the stored mean), so x must be given."""
         if self.training:
-            raise RuntimeError("noise-conditioned batch norm: only the stored-statistics (eval) form is built here")
-        mean, var = self.stored_mean.view(1, -1, 1, 1), self.stored_var.view(1, -1, 1, 1)
-        if self.accumulate_standing:
-            mean, var = mean / self.accumulation_counter, var / self.accumulation_counter
+            if x is None:
+                raise RuntimeError("noise-conditioned batch norm in training mode: the batch statistics need the activation, scale_shift(gain, bias, x)")
+            mean, var = norm_train.batch_stats(x, self, pend)
+        else:
+            mean, var = self.stored_mean.view(1, -1, 1, 1), self.stored_var.view(1, -1, 1, 1)
+            if self.accumulate_standing:
+                mean, var = mean / self.accumulation_counter, var / self.accumulation_counter
         scale = torch.rsqrt(var + self.eps) * gain
         return scale, mean * scale - bias
 
     def forward(self, x, gain, bias):
+        if self.training:
+            return norm_train.batch_norm_train(x, gain, bias, self, relu=False)
         scale, shift = self.scale_shift(gain, bias)
         return x * scale - shift
 
@@ -107,11 +125,18 @@ class LinearNoiseLayer(nn.Module):
         self.bias = nn.utils.spectral_norm(lin()) if _spectral(opt) else lin()
         self.bn = bn(output_sz)
 
-    def affine(self, x, noise=None):
+    def gain_bias(self, x, noise=None):
+        """The gain and bias (B, C, 1, 1) this layer predicts from `noise` (drawn here when None); through torch, differentiable"""
         if noise is None:
             noise = torch.randn(x.size(0), self.noise_sz).to(x.device)
         B = noise.size(0)
-        return self.bn.scale_shift((1 + _sn_linear(self.gain, noise)).view(B, -1, 1, 1), _sn_linear(self.bias, noise).view(B, -1, 1, 1))
+        return (1 + _sn_linear(self.gain, noise)).view(B, -1, 1, 1), _sn_linear(self.bias, noise).view(B, -1, 1, 1)
+
+    def affine(self, x, noise=None, pend=None):
+        """(scale, shift) of the layer on x; in training mode from x's batch statistics (bn.scale_shift), where `pend` is a bias still
+        missing from x"""
+        gain, bias = self.gain_bias(x, noise)
+        return self.bn.scale_shift(gain, bias, x, pend) if self.bn.training else self.bn.scale_shift(gain, bias)
 
     def affine_bc(self, x, noise=None, pend=None):
         """affine() as contiguous (B, C) scale / shift -- what the HIP passes take -- with `pend` (C), a convolution bias still missing
@@ -143,13 +168,15 @@ class LinearNoiseLayer(nn.Module):
                 _lib.call("ps_noise_affine_f32", noise, ws[0], ws[1], self.bn.stored_mean, self.bn.stored_var, pend, float(self.bn.eps), B, C,
                           noise.size(1), scale, shift)
                 return scale, shift
-        scale, shift = self.affine(x, noise)
-        if pend is not None:
+        scale, shift = self.affine(x, noise, pend)
+        if pend is not None and not self.bn.training:     # (on batch statistics a constant missing from x cancels: nothing to fold)
             shift = shift - pend.view(1, -1, 1, 1) * scale
         Bx = x.size(0)
         return scale.reshape(-1, C).expand(Bx, C).contiguous(), shift.reshape(-1, C).expand(Bx, C).contiguous()
 
     def forward(self, x, noise=None):
+        if self.bn.training:
+            return self.bn(x, *self.gain_bias(x, noise))
         scale, shift = self.affine(x, noise)
         return x * scale - shift
 
@@ -433,6 +460,11 @@ def _resample(kind, x):
     return x
 
 
+def _on_batch_stats(layer):
+    """Whether `layer` is a LinearNoiseLayer whose batch norm is in training mode (anything else a caller hands in has an affine() alone)"""
+    return hasattr(layer, "gain_bias") and layer.bn.training
+
+
 class ResNet_Block(nn.Module):
     """(norm, relu, 3x3) x 2 (+ resample) on one branch, 1x1 (+ resample) or identity on the other (blocks.py:34-73)."""
 
@@ -449,7 +481,13 @@ class ResNet_Block(nn.Module):
     @staticmethod
     def _noise_affine(layer, x, noise, bias=None, affine=None):
         """norm + ReLU of (x + bias): y = max(x * scale[b][c] - shift[b][c], 0), a pending conv bias folded into shift --
-        one HIP pass on the GPU (ps_affine_relu_nhwc_f32)."""
+        one HIP pass on the GPU (ps_affine_relu_nhwc_f32).  A layer in training mode: on the batch statistics of x, the stored ones
+        updated (norm_train.batch_norm_train; the bias then only shifts the stored mean)."""
+        if affine is None and _on_batch_stats(layer):
+            gain, offset = layer.gain_bias(x, noise)
+            if x.is_cuda:      # (what the convolution or resampling in front hands over usually is already)
+                x = x.contiguous(memory_format=torch.channels_last)
+            return norm_train.batch_norm_train(x, gain, offset, layer.bn, True, bias)
         if affine is None and _is_nhwc_cuda(x) and not torch.is_grad_enabled() and hasattr(layer, "affine_bc"):
             affine = layer.affine_bc(x, noise, bias)
         if affine is not None:   # (bias already folded in; as (B, C) or broadcastable to (B, C, 1, 1))
@@ -474,6 +512,15 @@ class ResNet_Block(nn.Module):
         torch.  res / out_bias: the block's other branch and the biases still pending, which the split-fp16 kernel adds on its way out
         (`fused` says whether it did: the output is then conv + res + out_bias)."""
         mode = _conv_mode(self.opt)
+        if _on_batch_stats(layer):
+            # batch statistics: the norm + ReLU is a pass of its own (norm_train); without autograd -- how standing statistics are
+            # collected -- the decoder's own convolutions follow with the identity in front
+            y = self._noise_affine(layer, x, noise, bias)
+            if mode == "f16x3" and conv.bias is not None and y.is_cuda and not torch.is_grad_enabled():
+                out = _f16x3_conv(conv, y) if _f16x3_takes(conv, y) else _thin_conv(conv, y)
+                if out is not None:
+                    return out, conv.bias, False
+            return _conv_split(conv, y, opt=self.opt) + (False,)
         if mode == "f16x3" and conv.bias is not None and x.is_cuda and not torch.is_grad_enabled():
             scale, shift = layer.affine_bc(x, noise, bias)
             if _f16x3_takes(conv, x):
@@ -491,7 +538,8 @@ class ResNet_Block(nn.Module):
     def forward(self, x, noise=(None, None)):
         a, ba, _ = self._norm_relu_conv(self.ch_a[0], self.ch_a[2], x, noise[0])
         mode = _conv_mode(self.opt)
-        if (self.resample and self.resample != "Up" and mode == "f16x3" and _is_nhwc_cuda(x) and not torch.is_grad_enabled()
+        # (not in train(): the test of the 1 x 1 weight below would run its spectral norm's power iteration a second time)
+        if (self.resample and self.resample != "Up" and mode == "f16x3" and _is_nhwc_cuda(x) and not torch.is_grad_enabled() and not self.training
                 and x.size(2) % 2 == 0 and x.size(3) % 2 == 0 and self.ch_b[0].kernel_size == (1, 1) and self.ch_b[0].stride == (1, 1)
                 # (the 1 x 1 conv's bias must come back SEPARATE from _conv_split, to go through the pool's bias * inside / 9 term: a
                 # convolution that cannot be taken apart returns conv(x) + bias, whose border pixels would then differ from the reference's)
