@@ -210,10 +210,21 @@ NORM_TRAIN_PROTOS = {
     "ps_norm_train_backward_f32": (RC, [c_void_p] * 6 + [c_int] * 4 + [c_void_p] * 4 + [c_size_t, STREAM]),
 }
 
+# libpixelsynth_block_train.so (include/pixelsynth_block_train.h): a decoder block's 1 x 1 weight gradient and resampling adjoints
+BLOCK_TRAIN_PROTOS = {
+    "ps_block_train_last_error": (ctypes.c_char_p, []),
+    "ps_conv1x1_grad_weight_parts": (c_int, [c_size_t, c_int, c_int]),
+    "ps_conv1x1_grad_weight_workspace_bytes": (c_size_t, [c_size_t, c_int, c_int]),
+    "ps_conv1x1_grad_weight_f32": (RC, [c_void_p, c_void_p, c_size_t, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, STREAM]),
+    "ps_upsample_add_bwd_nhwc_f32": (RC, [c_void_p] + [c_int] * 4 + [c_void_p, STREAM]),
+    "ps_pool_add_bwd_nhwc_f32": (RC, [c_void_p] + [c_int] * 4 + [c_void_p, STREAM]),
+}
+
 # short name of _libraries.LIBRARIES -> its prototype table; _OWNER: entry point -> the table entry of its library, built once
 PROTOS = {"hip": _PROTOS, "percsim": PERCSIM_PROTOS, "consistency": CONSISTENCY_PROTOS, "fid": FID_PROTOS, "scene": SCENE_PROTOS,
           "plan": PLAN_PROTOS, "rank": RANK_PROTOS, "rank_groups": RANK_GROUPS_PROTOS, "nll": NLL_PROTOS, "lmconv_bwd": LMCONV_BWD_PROTOS, "splat_bwd": SPLAT_BWD_PROTOS,
-          "vq_train": VQ_TRAIN_PROTOS, "conv_bwd": CONV_BWD_PROTOS, "norm_train": NORM_TRAIN_PROTOS}
+          "vq_train": VQ_TRAIN_PROTOS, "conv_bwd": CONV_BWD_PROTOS, "norm_train": NORM_TRAIN_PROTOS,
+          "block_train": BLOCK_TRAIN_PROTOS}
 _ENTRIES = {e.name: e for e in _libraries.LIBRARIES}
 assert set(PROTOS) == set(_ENTRIES)
 _OWNER = {fn: _ENTRIES[name] for name, table in PROTOS.items() for fn in table}

@@ -21,7 +21,9 @@ Same constructor arguments, attribute / parameter names and shapes as the refere
 Training: the plain BatchNorm2d layers are torch's own.  The noise-conditioned layers in train() normalise on batch statistics and
 update the stored ones (the running average, or standing sums with bn.accumulate_standing) through norm_train.batch_norm_train:
 csrc/norm_train.hip -- statistics, norm + ReLU and their backward pass -- for channels-last fp32 activations on the GPU, the torch formula
-elsewhere or under decoder_norm_train("torch").  In eval() every path is the stored-statistics form above, untouched.
+elsewhere or under decoder_norm_train("torch").  In eval() every path is the stored-statistics form above, untouched.  Under
+decoder_block_train("hip") (block_train.py; the default is "torch") a block's wide 1 x 1 projection and its Up / Down join are
+differentiated by csrc/block_train.hip as well.
 """
 import os
 
@@ -29,7 +31,8 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import f16x3, norm_train
+from . import block_train, f16x3, norm_train
+from .block_train import decoder_block_train  # noqa: F401
 from .norm_train import decoder_norm_train  # noqa: F401
 from .f16x3 import _FORCED_CONV, check_f16x3_overflow, decoder_conv, decoder_conv_train, flag as _overflow_flag  # noqa: F401  (the names bench.py and the tests use)
 
@@ -305,12 +308,16 @@ def _conv_split(conv, x, mode=None, opt=None):
     of its own; here the per-channel constant rides along in whatever pass consumes the output (csrc/nets.hip).  Elsewhere
     (CPU, autograd, channel counts the kernels do not take): (conv(x), None).  mode "f16x3": a 1 x 1 convolution through
     csrc/conv1x1.hip instead of torch (MIOpen).  In grad mode with the training opt-in of `opt` (f16x3.train_mode) a wide 3 x 3
-    convolution goes through f16x3.conv3x3_train (_f16x3_train_conv)."""
+    convolution goes through f16x3.conv3x3_train (_f16x3_train_conv), and with the block opt-in (block_train.mode) a wide 1 x 1
+    convolution through block_train.conv1x1_train (_block_train_conv1x1)."""
     if mode == "f16x3":
         y = conv1x1(conv, x)
         if y is not None:
             return y, conv.bias
     y = _f16x3_train_conv(conv, x, opt)
+    if y is not None:
+        return y, None
+    y = _block_train_conv1x1(conv, x, opt)
     if y is not None:
         return y, None
     if conv.bias is None or torch.is_grad_enabled() or not _is_nhwc_cuda(x) or conv.out_channels % 4:
@@ -357,6 +364,26 @@ def _f16x3_train_conv(conv, x, opt=None):
         return f16x3.conv3x3_train(x, weight, conv.bias)
     except ValueError:      # a weight fp16 cannot hold: torch, on the weight already normalised (the pre-hook has run once)
         return F.conv2d(x, weight, conv.bias, 1, 1)
+
+
+def _block_train_conv1x1(conv, x, opt=None):
+    """conv(x) WITH its bias through block_train.conv1x1_train -- csrc/conv1x1.hip forward, csrc/block_train.hip and conv1x1.hip
+    backward -- or None: only in grad mode, only under the opt-in (decoder_block_train("hip") / opt.decoder_block_train /
+    PS_DECODER_BLOCK_TRAIN; the default is "torch"), not where decoder_conv("fp32") or the options send the decoder's convolutions through
+    torch, and only for a plain 1 x 1 convolution (stride 1, no padding, groups 1) on a CUDA fp32 input whose Ci and Co are multiples of 64
+    up to 256 (the projections of the decoder's four resampling blocks) and whose pixels are a multiple of 16.  The weight is the
+    module's own (with spectral norm: as its pre-hook leaves it, which is differentiable in training mode)."""
+    if not (torch.is_grad_enabled() and type(conv) is nn.Conv2d and conv.kernel_size == (1, 1) and conv.stride == (1, 1)
+            and conv.padding == (0, 0) and conv.dilation == (1, 1) and conv.groups == 1 and x.is_cuda and x.dtype == torch.float32
+            and x.dim() == 4 and conv.in_channels % 64 == 0 and conv.out_channels % 64 == 0
+            and max(conv.in_channels, conv.out_channels) <= block_train.MAX_CHANNELS
+            and block_train.mode(opt) == "hip" and _conv_mode(opt) == "f16x3"
+            and block_train.conv1x1_takes(conv.in_channels, conv.out_channels, x.size(0) * x.size(2) * x.size(3))):
+        return None
+    weight = _plain_conv_weight(conv, x)
+    if weight is None or weight.dtype != torch.float32 or weight.device != x.device:
+        return None
+    return block_train.conv1x1_train(x.contiguous(memory_format=torch.channels_last), weight, conv.bias)
 
 
 def _thin_conv(conv, x, scale=None, shift=None):
@@ -420,14 +447,17 @@ def _sum_bias(*bs):
     return None if not bs else bs[0] if len(bs) == 1 else (bs[0] + bs[1]).contiguous()
 
 
-def _resample_sum(kind, a, b, bias=None, post=None):
+def _resample_sum(kind, a, b, bias=None, post=None, opt=None):
     """_resample(kind, a + bias) + _resample(kind, b) -- blocks.py:61-73 -- as ONE pass through csrc/nets.hip on the GPU
     (`bias`: per-channel constant still missing from the inputs, see _conv_split).  b = None: a alone -- resampling is linear, so
     a caller that already holds the SUM of the two branches resamples once.  post ('Down' only): a tensor of the output's shape added
-    after the pooling.  Through torch where autograd follows an operand."""
+    after the pooling.  Where autograd follows an operand: through block_train.resample_sum_train under its opt-in (block_train.mode(opt)
+    "hip"; `bias` and `post` None, which they are in grad mode), else through torch."""
     from .. import _lib
     # (an operand that autograd follows goes through torch: the HIP passes are forward-only and would cut the graph)
     graph = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (a, b, bias, post))
+    if graph and bias is None and post is None and block_train.mode(opt) == "hip" and block_train.resample_takes(kind, a, b):
+        return block_train.resample_sum_train(kind, a, b)
     if (graph or not (_is_nhwc_cuda(a) if b is None else _is_nhwc_cuda(a, b)) or (b is not None and a.shape != b.shape)
             or (kind and kind != "Up" and (a.size(2) % 2 or a.size(3) % 2)) or (b is None and not kind)):
         if bias is not None:
@@ -549,7 +579,7 @@ class ResNet_Block(nn.Module):
             b, bb = _conv_split(self.ch_b[0], _resample_sum(self.resample, x, None), mode)
             a, ba2, _ = self._norm_relu_conv(self.ch_a[3], self.ch_a[5], a, noise[1], ba)
             return _resample_sum(self.resample, a, None, _sum_bias(ba2, bb), post=b)
-        b, bb = _conv_split(self.ch_b[0], x, mode) if self.projected else (x, None)
+        b, bb = _conv_split(self.ch_b[0], x, mode, self.opt) if self.projected else (x, None)
         # The second convolution adds the other branch on its way out where it can (resampling is linear: resample(a) + resample(b) =
         # resample(a + b)); without resampling the biases go in as well and its output is the block's.
         conv2 = self.ch_a[5]
@@ -557,8 +587,8 @@ class ResNet_Block(nn.Module):
         a, ba2, fused = self._norm_relu_conv(self.ch_a[3], conv2, a, noise[1], ba, res=b,
                                              out_bias=None if self.resample else _sum_bias(own, bb))
         if fused:
-            return a if not self.resample else _resample_sum(self.resample, a, None, _sum_bias(ba2, bb))
-        return _resample_sum(self.resample if self.projected else None, a, b, _sum_bias(ba2, bb))
+            return a if not self.resample else _resample_sum(self.resample, a, None, _sum_bias(ba2, bb), opt=self.opt)
+        return _resample_sum(self.resample if self.projected else None, a, b, _sum_bias(ba2, bb), opt=self.opt)
 
 
 class ResNetDecoder(nn.Module):
