@@ -24,7 +24,8 @@ int ps_fid_input(const void *img, const int64_t *strides, int dtype, int B, int 
  *   pixel, the first Ci read), y (N, Ho, Wo, ldy floats per pixel, channels coff .. coff + Co - 1 written and no other).  fp32
  *   operands on v_mfma_f32_16x16x4_f32, summed over k = (kh KW + kw) Ci + ci in a fixed order on three levels: a chunk of 16 k is one
  *   fp32 fma chain from zero (k = 16 chunk + 4 kk + j, j outer, kk inner), 16 chunks ascending add up to a middle sum, the middle sums
- *   ascending to the total; the bias is added last.
+ *   ascending to the total; the bias is added last.  A NaN sum stays NaN (torch.relu's rule, not fmaxf's): a NaN in x reaches the
+ *   outputs whose taps read it and no other.
  *   ps_fid_conv_takes: 1 <= KH, KW <= 7, stride 1 or 2, 0 <= ph < KH, 0 <= pw < KW, Ci a positive multiple of 4, Co >= 1.
  *   ps_fid_conv_co_tile(Co): the output channels of a workgroup, 32 or 64 (the one that pads Co less, 64 on a tie).
  *   wp: the weights packed for the kernel, ps_fid_conv_packed_floats(KH, KW, Ci, Co) floats (wp_floats says how many there are).
@@ -41,7 +42,8 @@ int ps_fid_conv(const float *x, int ldx, const float *wp, size_t wp_floats, cons
  *   floats, as ps_fid_conv writes.  PS_FID_MAX_S2: 3 x 3 max, stride 2, no padding -> (N, (H - 3) / 2 + 1, (W - 3) / 2 + 1);
  *   PS_FID_MAX_S1: 3 x 3 max, stride 1, padding 1 (the padding never wins) -> (N, H, W); PS_FID_AVG_S1: 3 x 3 average, stride 1,
  *   padding 1, the sum over the taps inside the map (kh, then kw ascending) divided by their number -> (N, H, W); PS_FID_MEAN: the
- *   mean over the map, summed and divided in fp64, rounded to fp32 once -> (N, 1, 1). */
+ *   mean over the map, summed and divided in fp64, rounded to fp32 once -> (N, 1, 1).  A window (a map) that holds a NaN gives NaN in
+ *   every mode, as F.max_pool2d and F.avg_pool2d do. */
 enum { PS_FID_MAX_S2 = 0, PS_FID_MAX_S1 = 1, PS_FID_AVG_S1 = 2, PS_FID_MEAN = 3 };
 int ps_fid_pool(const float *x, int ldx, int mode, int N, int H, int W, int C, float *y, int ldy, int coff, void *stream);
 

@@ -2,14 +2,17 @@
 // (MI355X), on fp32 NHWC maps:
 //
 //   k_fid_input   one thread per output pixel: (B, 3, H, W) fp32 or uint8 read through element strides -> (B, 299, 299, 4), channel 3
-//                 zero; torch's fp32 bilinear resize (align_corners = False) and 2 v - 1 in one pass (the unit is built without FP
-//                 contraction, so the products and sums round as torch's do).
+//                 zero; torch's fp32 bilinear resize (align_corners = False) and 2 v - 1 in one pass, every product and sum of the
+//                 formula below rounded once (the unit is built without FP contraction).  torch's own kernels round elsewhere
+//                 (its CPU resize equals this one bit for bit on an exact 2 x downsample, and differs by the rounding of the
+//                 source index on other sizes: tests/test_fid_conv_edges_gpu.py).
 //   k_fid_conv    the project's general convolution: an implicit GEMM y (pixels, Co) = patches (pixels, K) . w^T (Co, K), K = KH KW Ci,
 //                 on the fp32 matrix pipe (v_mfma_f32_16x16x4_f32: exact fp32 products, fp32 accumulation -- no split operands, no
-//                 overflow guard), the epilogue max(acc + bias, 0) (BatchNorm folded into w and bias on the host) written at a
-//                 channel offset of a wider map: a block's branches land in its concatenated output, no concat pass exists.
+//                 overflow guard), the epilogue max(acc + bias, 0) (BatchNorm folded into w and bias on the host; a NaN stays a
+//                 NaN, as under torch.relu) written at a channel offset of a wider map: a block's branches land in its
+//                 concatenated output, no concat pass exists.
 //   k_fid_pool    the three 3 x 3 pools of the network and the final mean over the map, 4 channels per thread, the same
-//                 channel-offset output.
+//                 channel-offset output.  A NaN in a window is the window's maximum, as under F.max_pool2d.
 //
 // The convolution.  K is walked in groups of 4 input channels of one tap (Ci is a multiple of 4: a group is one 16-byte load of one
 // input pixel), 4 groups to a chunk (one MFMA k-step per element j of the groups), 4 chunks to a stage.  A workgroup of four waves
@@ -38,6 +41,30 @@ using ps::to_unit;
 
 constexpr int FID_SIZE = 299;
 constexpr int CV_THREADS = 256, CV_WAVES = 4, CV_STAGE_K = 64;
+
+// torch.relu and F.max_pool2d hand a NaN on; v_max_f32 returns its other operand.  relu_nan: a compare and a select, NaN < 0 being
+// false.  It has the bits of max(v, 0) for every other v but -0, which no sum that started at +0 ever is (k_fid_conv's do).
+// MaxNan: the plain maximum of the values taken, and whether one of them was NaN (a compare into a scalar mask per value): the
+// result is NaN then, the plain maximum's bits otherwise.
+__device__ __forceinline__ float relu_nan(float v) { return v < 0.0f ? 0.0f : v; }
+__device__ __forceinline__ f32x4 relu_nan(f32x4 v) { return (f32x4){relu_nan(v[0]), relu_nan(v[1]), relu_nan(v[2]), relu_nan(v[3])}; }
+
+struct MaxNan {
+    f32x4 m;
+    bool nan[4];
+    __device__ __forceinline__ explicit MaxNan(f32x4 v) : m(v), nan{v[0] != v[0], v[1] != v[1], v[2] != v[2], v[3] != v[3]} {}
+    __device__ __forceinline__ void take(f32x4 v)
+    {
+        m = __builtin_elementwise_max(m, v);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) nan[c] |= v[c] != v[c];
+    }
+    __device__ __forceinline__ f32x4 result() const
+    {
+        const float q = __builtin_nanf("");
+        return (f32x4){nan[0] ? q : m[0], nan[1] ? q : m[1], nan[2] ? q : m[2], nan[3] ? q : m[3]};
+    }
+};
 
 template <typename T>
 __global__ __launch_bounds__(256) void k_fid_input(Img im, int H, int W, float sh, float sw, f32x4 *__restrict__ out)
@@ -188,11 +215,11 @@ __global__ __launch_bounds__(CV_THREADS, 2) void k_fid_conv(ConvArgs a)
             const int co = cb * (16 * MT) + 16 * t + 4 * kk;
             if (co + 3 < a.Co) {
                 const f32x4 v = acc[t][n] + *(const f32x4 *)(a.bias + co);
-                *(f32x4 *)(row + co) = __builtin_elementwise_max(v, zero);
+                *(f32x4 *)(row + co) = relu_nan(v);
             } else {
 #pragma unroll
                 for (int r = 0; r < 4; ++r)
-                    if (co + r < a.Co) row[co + r] = fmaxf(acc[t][n][r] + a.bias[co + r], 0.0f);
+                    if (co + r < a.Co) row[co + r] = relu_nan(acc[t][n][r] + a.bias[co + r]);
             }
         }
     }
@@ -219,15 +246,17 @@ __global__ __launch_bounds__(256) void k_fid_pool(const float *__restrict__ x, i
         const double hw = (double)H * W;
         o = (f32x4){(float)(s0 / hw), (float)(s1 / hw), (float)(s2 / hw), (float)(s3 / hw)};
     } else if (mode == PS_FID_MAX_S2) {
-        o = at(2 * ho, 2 * wo);
+        MaxNan best(at(2 * ho, 2 * wo));
 #pragma unroll
-        for (int k = 1; k < 9; ++k) o = __builtin_elementwise_max(o, at(2 * ho + k / 3, 2 * wo + k % 3));
+        for (int k = 1; k < 9; ++k) best.take(at(2 * ho + k / 3, 2 * wo + k % 3));
+        o = best.result();
     } else {
         const int h0 = max(ho - 1, 0), h1 = min(ho + 1, H - 1), w0 = max(wo - 1, 0), w1 = min(wo + 1, W - 1);
         if (mode == PS_FID_MAX_S1) {
-            o = at(h0, w0);
+            MaxNan best(at(h0, w0));
             for (int h = h0; h <= h1; ++h)
-                for (int w = w0; w <= w1; ++w) o = __builtin_elementwise_max(o, at(h, w));
+                for (int w = w0; w <= w1; ++w) best.take(at(h, w));
+            o = best.result();
         } else {
             o = (f32x4){0.f, 0.f, 0.f, 0.f};
             for (int h = h0; h <= h1; ++h)
