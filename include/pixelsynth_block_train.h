@@ -25,7 +25,8 @@ extern "C" {
  *                 of x when Co has an even number of chunks, else one with two when Ci has, else one with one)
  *   target      = min(PS_BLOCK_TRAIN_MAX_PARTS, max(1, 512 / tiles))
  *   part pixels = max(PS_BLOCK_TRAIN_MIN_PART, 16 * ceil((npix / 16) / target)),      parts = ceil(npix / part pixels)
- * a function of (npix, Ci, Co) alone, never of the device.  Inside a part the PS_BLOCK_TRAIN_WAVES wavefronts of a workgroup take
+ * a function of (npix, Ci, Co) alone, never of the device.  A count that is no multiple of 64 leaves its last chunk short (Co mod 64
+ * or Ci mod 64 channels of it exist): the lanes past the count multiply zeros and store nothing.  Inside a part the PS_BLOCK_TRAIN_WAVES wavefronts of a workgroup take
  * the groups of four consecutive pixels in turn (wavefront w the groups w, w + WAVES, ...); a wavefront accumulates its groups in
  * ascending order on the fp32 matrix pipe (v_mfma_f32_16x16x4_f32: fp32 fused multiply-adds, no reduced-precision product), the
  * wavefronts are added in ascending order, and a second kernel adds the parts in ascending order (with one part the first kernel

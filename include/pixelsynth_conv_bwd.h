@@ -30,7 +30,12 @@ extern "C" {
 
 /* The reduction over the pixels is split into at most this many parts of consecutive pixel tiles (4 rows x 16 pixels each), each one
  * chain of fp32 sums per element, whose partial results are added in ascending order of the part.  The number of parts is a function of
- * (B, H, W, Ci, Co) alone -- never of the device. */
+ * (B, H, W, Ci, Co) alone -- never of the device:
+ *   tiles          = B (H / 4) (W / 16), numbered frame by frame, row of tiles by row of tiles
+ *   tiles per part = max(8, ceil(tiles / min(PS_CONV_BWD_MAX_PARTS, ceil(512 / ((Co / 64) (Ci / 64))))))
+ *   parts          = ceil(tiles / tiles per part)
+ * Part p takes the tiles p * tiles per part .. ; the last part may be shorter, and a part may span two frames.  Every part is worked
+ * on by (Co / 64) (Ci / 64) workgroups, one per 64 x 64 block of channels. */
 #define PS_CONV_BWD_MAX_PARTS 256
 
 /* Bytes of workspace the calls below need for these sizes (device memory, 256-byte aligned; one workspace serves prepare and
@@ -45,6 +50,8 @@ int ps_conv3x3_bwd_parts(int B, int H, int W, int Ci, int Co);
  * (B,H,W,Co).  grad_bias (Co) or NULL: grad_bias[o] = sum_{b,y,x} g[b,y,x,o] of the UNSCALED g -- the pixels cut into at most 256
  * consecutive ranges of at least 64; inside a range sixteen interleaved chains in ascending pixel order, joined by a fixed tree (chain i
  * with chain i + 8, then + 4, + 2, + 1); the ranges as four interleaved chains in ascending order joined as (0 + 1) + (2 + 3).
+ *   pixels per range = max(64, ceil(B H W / 256)),     ranges = ceil(B H W / pixels per range)
+ * (a range whose length is no multiple of 16 gives its chains unequal lengths).  Every range leaves one maximum per 64 channels of Co.
  * g_scaled must not be g. */
 int ps_conv3x3_bwd_prepare_f32(const float *g, int B, int H, int W, int Co, float *g_scaled, float *scale2, float *grad_bias,
                                void *workspace, size_t workspace_bytes, void *stream);

@@ -22,7 +22,15 @@ extern "C" {
  * one of a frame may be shorter): the smallest multiple that gives a frame at most max(1, PS_NORM_TRAIN_MAX_PARTS / B) parts,
  *   rows per part = PART_ROWS * ceil(ceil(HW / PART_ROWS) / max(1, MAX_PARTS / B)),    parts per frame = ceil(HW / rows per part).
  * A function of B and HW alone; no part spans two frames.  A sum is accumulated in fp64 in a fixed order inside a part and the parts
- * are added in ascending order. */
+ * are added in ascending order.
+ *
+ * Inside a part (tests/_norm_train_ref.py restates this): a workgroup of 256 threads takes cw = min(C / 4, 64) quads of channels, so
+ * ceil((C / 4) / cw) workgroups lie across the channels (the last may take fewer quads), and rl = 256 / cw row lanes (rounded down; the
+ * 256 - cw rl threads left over idle).  Lane l takes the part's rows l, l + rl, l + 2 rl, ...: blocks of four of them through two
+ * register sets in turn, a block's loads issued before the block in front of it is used, for as long as a whole block lies inside the
+ * part; the rows left, at most three, one at a time.  The parts of a sum are added 64 at a time (a batch is staged while the one before
+ * it is added), from the first part of the sum on -- of all parts for the statistics, of each frame's parts for dgain and dbias -- by
+ * workgroups of 32 channels, ceil(C / 32) of them (the last may have fewer channels). */
 #define PS_NORM_TRAIN_MAX_PARTS 512
 #define PS_NORM_TRAIN_PART_ROWS 512
 #define PS_NORM_TRAIN_MAX_C 65536

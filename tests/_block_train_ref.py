@@ -19,6 +19,8 @@ Bounds, with u = 2^-24 (the unit roundoff of fp32) and the fp64 result as the tr
   passes through at most L + parts roundings, and (1 + u)^(L + parts) - 1 <= 1.01 (L + parts) u while (L + parts) u < 0.01: 160 000
   roundings, far beyond what the tests (and the decoder's 4096-pixel parts) reach.
 """
+from collections import namedtuple
+
 import torch
 import torch.nn.functional as F
 
@@ -62,6 +64,38 @@ def chain(npix, Ci, Co):
     return max(len(w) for lo, hi in part_ranges(npix, Ci, Co) for w in wave_pixels(lo, hi)) + WAVES
 
 
+GwPlan = namedtuple("GwPlan", "TO TC tiles_o tiles_c short_g short_x part_pix parts last_pix")
+
+
+def gw_plan(npix, Ci, Co):
+    """gw_plan of csrc/block_train.hip: the kernel is k_grad_weight<TO, TC> on a tiles_o x tiles_c grid of workgroups per part; short_g /
+    short_x: the channels of the last 64-channel chunk of g / x when it ends early (on_g / on_x false for the lanes past them), else 0;
+    pixels of a part, parts, pixels of the last part"""
+    TO, TC, _ = tiles(Ci, Co)
+    parts = part_ranges(npix, Ci, Co)
+    return GwPlan(TO, TC, -(-Co // 64) // TO, -(-Ci // 64) // TC, Co % 64, Ci % 64, parts[0][1] - parts[0][0], len(parts),
+                  parts[-1][1] - parts[-1][0])
+
+
+# ---- the route cases (tests/test_train_routes_cpu.py asserts each reaches what it is there for, tests/test_train_routes_gpu.py runs them) --
+GW_ROUTE_SHAPES = [(528, 128, 64), (528, 80, 48), (528, 48, 80), (528, 192, 192), (528, 256, 192), (131088, 16, 16)]     # (npix, Ci, Co)
+BIG_RESAMPLE = (2, 258, 256, 64)                    # (B, H, W, C) of grad_in: 2^21 + 16 384 float4s, 8192 workgroups of 256 take 2^21 at a time
+UP_ROUTE_SHAPES = [(1, 3, 1, 4), BIG_RESAMPLE]
+DOWN_ROUTE_SHAPES = [BIG_RESAMPLE]
+GRID_MAX, GRID_THREADS = 256 * 32, 256              # grid_for of csrc/block_train.hip
+
+
+def second_trip(shape4):
+    """(float4s of grad_in, those a thread reaches only on its second trip of the grid-stride loop, the rows of the last frame they are
+    -- None unless they are whole rows of the last frame)"""
+    B, H, W, C = shape4
+    total4, first = B * H * W * C // 4, GRID_MAX * GRID_THREADS
+    rest = max(0, total4 - first)
+    row4 = W * C // 4
+    rows = rest // row4 if rest % row4 == 0 and rest <= H * row4 else None
+    return total4, rest, rows
+
+
 # ---- fp64 formulas: torch's own autograd in fp64 on the host ------------------------------------------------------------------------------------
 def resample(kind, x):
     if kind == "Up":
@@ -76,9 +110,26 @@ def adjoint(kind, g, shape, dtype=torch.float64):
     return a.grad
 
 
+def axis_terms(kind, n):
+    """Per index i of an axis of n inputs, the number of outputs it hears from with a weight that is not 0 (the header's tables): "Up"
+    2 i - 1 (i >= 1), 2 i, 2 i + 1, 2 i + 2 (i <= n - 2); "Down" i / 2 and, for an odd i, (i + 1) / 2 where that is an output"""
+    i = torch.arange(n)
+    if kind == "Up":
+        return ((i >= 1).double() + 2 + (i <= n - 2).double())
+    return 1 + ((i % 2 == 1) & ((i + 1) // 2 < n // 2)).double()
+
+
 def adjoint_terms(kind, shape):
     """k of the docstring per element of grad_in (B, C, H, W): the number of outputs the pixel hears from with a weight that is not 0,
-    plus 1 for "Down" """
+    plus 1 for "Down".  Both resamplings are separable, so it is the product of the two axes' counts (tests/test_train_routes_cpu.py
+    holds it equal to adjoint_terms_loop at UP_SHAPES and DOWN_SHAPES)"""
+    B, C, H, W = shape
+    count = axis_terms(kind, H).view(H, 1) * axis_terms(kind, W).view(1, W)
+    return (count + (kind == "Down")).view(1, 1, H, W).expand(shape)
+
+
+def adjoint_terms_loop(kind, shape):
+    """adjoint_terms by one autograd call per output pixel: what the closed form is held to at the small shapes"""
     n = adjoint(kind, torch.ones(resample(kind, torch.zeros(shape, dtype=torch.float64)).shape), shape)      # the weights' sum: only to be sure
     assert (n > 0).all()
     B, C, H, W = shape

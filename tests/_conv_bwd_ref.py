@@ -50,6 +50,27 @@ def part_ranges(B, H, W, Ci, Co):
     return [(t, min(t + chunk, n)) for t in range(0, n, chunk)]
 
 
+PREP_BLOCKS, PREP_MIN_PIXELS = 256, 64      # the pass over g: ranges at most, pixels of a range at least
+
+ConvPlan = namedtuple("ConvPlan", "tiles per_frame blocks chunk parts last straddle npix pchunk nprep ncb")
+
+
+def plan(B, H, W, Ci, Co):
+    """make_plan of csrc/conv_bwd.hip (the header states the formulas): tiles, tiles of a frame, 64 x 64 channel blocks, tiles per part
+    (chunk), parts, tiles of the last part, the parts whose tiles lie in two frames; of the pass over g: pixels, pixels per range
+    (pchunk), ranges (nprep), 64-channel blocks of Co (one maximum per range and block)"""
+    rs = part_ranges(B, H, W, Ci, Co)
+    per_frame = (H // TILE_ROWS) * (W // TILE_COLS)
+    npix = B * H * W
+    pchunk = max(-(-npix // PREP_BLOCKS), PREP_MIN_PIXELS)
+    blocks = (Co // BLOCK) * (Ci // BLOCK)
+    chunk = max(-(-tiles(B, H, W) // min(-(-TARGET_WGS // blocks), MAX_PARTS)), MIN_CHUNK)
+    assert all(hi - lo == chunk for lo, hi in rs[:-1])
+    return ConvPlan(tiles(B, H, W), per_frame, blocks, chunk, len(rs), rs[-1][1] - rs[-1][0],
+                    [i for i, (lo, hi) in enumerate(rs) if lo // per_frame != (hi - 1) // per_frame],
+                    npix, pchunk, -(-npix // pchunk), Co // BLOCK)
+
+
 # ---- the references ---------------------------------------------------------------------------------------------------------------------------
 def wgrad(x, g):
     """sum_{b,y,x} g[b,o,y,x] * xpad[b,c,y+ky-1,x+kx-1] -> (Co, Ci, 3, 3), in the dtype of the operands: the batch as the channels of a
@@ -125,6 +146,16 @@ def check(what, y, r):
 
 # ---- the cases both test files use -----------------------------------------------------------------------------------------------------------
 SHAPES = [(2, 32, 32, 64, 64), (3, 16, 48, 128, 64), (1, 32, 16, 64, 192)]      # (B, H, W, Ci, Co)
+# the route cases (tests/test_train_routes_cpu.py asserts each reaches what it is there for, tests/test_train_routes_gpu.py runs them)
+RouteCase = namedtuple("RouteCase", "id shape why")
+ROUTE_CASES = [
+    RouteCase("blocks_2x2", (1, 16, 16, 128, 128), "four channel blocks, two on each axis: blockIdx.y splits into (co block, ci block)"),
+    RouteCase("blocks_3x2", (1, 16, 32, 128, 192), "six channel blocks, 3 x 2"),
+    RouteCase("ragged_prep", (5, 48, 80, 64, 64), "pchunk = 75 (no multiple of 16), nprep = 256, 38 parts, the last of 4 tiles"),
+    RouteCase("prep_scan_twice", (5, 48, 80, 64, 128), "nprep ncb = 512 > 256: the maximum scan of k_prep_finish goes round again"),
+    RouteCase("chunk_9", (3, 208, 224, 64, 64), "chunk = 9, 243 parts, parts that straddle frames; pchunk = 546"),
+]
+OPERATOR_SHAPES = SHAPES + [(1, 32, 16, 64, 64)]      # every shape of the operator tests of tests/test_conv_bwd_gpu.py (the last: the halo's)
 
 
 def inputs(B, H, W, Ci, Co, seed=0, g_scale=1.0):

@@ -74,11 +74,45 @@ def test_the_adjoints_against_fp64(kind, shape4):
     assert abs(lhs - rhs) <= 34 * ref.U * scale          # (17 roundings a side at the most, see the ref's docstring)
 
 
-@pytest.mark.parametrize("kind,shape4", [("Up", ref.UP_SHAPES[1]), ("Up", ref.UP_SHAPES[2]), ("Down", ref.DOWN_SHAPES[1]), ("Down", ref.DOWN_SHAPES[2])],
+def _one_hot_in_the_second_trip(kind, shape4):
+    """The large shape, whose last rows of the last frame a thread of the adjoint reaches on its second trip of the grid-stride loop: g
+    one-hot (all channels) in the last frame at outputs those rows hear from -- the bottom corners and two pixels further up, one of
+    whose inputs straddle the two trips for "Down".  grad_in is the fp64 adjoint exactly -- zeros in all the rest, first trip included --
+    and where it is not 0 it is the forward kernel's weight, read off a forward pass of one one-hot input per frame"""
+    B, H, W, C = shape4
+    total4, rest, rows = ref.second_trip(shape4)
+    assert rest > 0 and rows == 4
+    Ho, Wo = (2 * H, 2 * W) if kind == "Up" else (H // 2, W // 2)
+    g = torch.zeros(B, C, Ho, Wo, device=DEV).contiguous(memory_format=CL)
+    gin = torch.empty(B, C, H, W, device=DEV).contiguous(memory_format=CL)
+    for Y, X in ((Ho - 1, 0), (Ho - 1, Wo - 1), (Ho - (6 if kind == "Up" else 2), Wo // 2), (Ho - 2, 1)):
+        g[B - 1, :, Y, X] = 1.0
+        gin.fill_(float("nan"))
+        _lib.call("ps_upsample_add_bwd_nhwc_f32" if kind == "Up" else "ps_pool_add_bwd_nhwc_f32", g, B, H, W, C, gin)
+        torch.cuda.synchronize()
+        g[B - 1, :, Y, X] = 0.0
+        one = torch.zeros(1, 1, Ho, Wo)
+        one[0, 0, Y, X] = 1.0
+        want = ref.adjoint(kind, one, (1, 1, H, W)).float()[0, 0]                       # (frames and channels are independent)
+        heard = want.nonzero().tolist()
+        assert 1 <= len(heard) <= 9 and min(y for y, _ in heard) >= H - rows - 1 and max(y for y, _ in heard) >= H - rows
+        assert not gin[:B - 1].any() and torch.equal(gin[B - 1].cpu(), want.expand(C, H, W)), (Y, X)
+        a = torch.zeros(len(heard), 4, H, W)
+        for k, (y, x) in enumerate(heard):
+            a[k, :, y, x] = 1.0
+        with torch.no_grad():
+            fwd = A._resample_sum(kind, _nhwc(a), None)[:, 0, Y, X].cpu()
+        assert torch.equal(fwd, torch.stack([want[y, x] for y, x in heard])), (Y, X)
+
+
+@pytest.mark.parametrize("kind,shape4", [("Up", ref.UP_SHAPES[1]), ("Up", ref.UP_SHAPES[2]), ("Down", ref.DOWN_SHAPES[1]), ("Down", ref.DOWN_SHAPES[2]),
+                                         ("Up", ref.BIG_RESAMPLE), ("Down", ref.BIG_RESAMPLE)],
                          ids=lambda v: v if isinstance(v, str) else "x".join(map(str, v)))
 def test_one_hot_gradients_give_the_forwards_weights_exactly(kind, shape4):
     """g one-hot at the four corners of the output and at one interior pixel: grad_in[y][x] is the weight with which the forward kernel
     sends input (y, x) to that output -- read off the forward kernel itself, one one-hot input per frame -- and equals the fp64 adjoint"""
+    if shape4 == ref.BIG_RESAMPLE:
+        return _one_hot_in_the_second_trip(kind, shape4)
     _, H, W, _ = shape4
     eye = torch.eye(H * W).view(H * W, 1, H, W).expand(H * W, 4, H, W)
     with torch.no_grad():
