@@ -23,12 +23,18 @@ extern "C" {
  * ps_percsim_tap: the tapped layer `layer` (0 .. 4: relu1_2, relu2_2, relu3_3, relu4_3, relu5_3) of a pass at image size H x W (multiples
  *   of 128): y (2P, H >> layer, W >> layer, C) fp32 NHWC, the layer's PRE-ReLU output, C a multiple of 64.  Adds the layer's per-tile
  *   sums of cos_sim(relu(y[i]), relu(y[P + i])) to the workspace; pooled (2P, H >> (layer + 1), W >> (layer + 1), C) or NULL: the
- *   2 x 2 stride-2 max-pool of y (pre-ReLU), written by the same read.
+ *   2 x 2 stride-2 max-pool of y (pre-ReLU), written by the same read.  Non-finite values go through as torch.relu and
+ *   F.max_pool2d hand them on: a NaN in y stays a NaN (not the 0 of a maxNum), so a NaN -- or a +inf, inf / inf -- in any channel of a
+ *   pixel of either image of a pair makes that layer's score and that pair's total NaN and touches no other pair; a pooled window
+ *   that holds a NaN is NaN; -inf is a negative value like any other.
  * ps_percsim_finish: -> layers (P, 5) f32, 1 - mean_pixels(cos_sim) per tapped layer, and total (P) f32, their sum: PNet's
  *   retPerLayer scores and its value.  After the five taps of a pass.
  *   workspace: >= ps_percsim_workspace_bytes(P, H, W) bytes of device memory (per-tile partial sums), shared by a pass's taps and its
- *   finish.  Each call one launch on `stream`, no allocation, no synchronisation, no atomics: bit-reproducible, and a pair's numbers
- *   depend neither on its place in the pass nor on P.
+ *   finish.  Its layout: doubles [layer][pair][tile], layer l's block P * tiles_l long with tiles_l = (H_l / 2)(W_l / 2) / 16,
+ *   H_l = H >> l, W_l = W >> l; a tile is 16 consecutive 2 x 2 pixel blocks of the map in row-major order, its double the sum of its
+ *   64 pixels' cosines.  A tap writes every double of its layer's block and nothing else; the finish reads all five blocks (a layer
+ *   whose block is zero scores 1).  Each call one launch on `stream`, no allocation, no synchronisation, no atomics:
+ *   bit-reproducible, and a pair's numbers depend neither on its place in the pass nor on P.
  * ps_percsim_workspace_bytes: host-only arithmetic; 0 when H or W is not a multiple of 128. */
 enum { PS_PERCSIM_PLAIN = 0, PS_PERCSIM_VIS = 1, PS_PERCSIM_INVIS = 2, PS_PERCSIM_RAW = 3 };
 size_t ps_percsim_workspace_bytes(int P, int H, int W);

@@ -12,7 +12,8 @@
 //                     then dot / ((|r0| + 1e-10)(|r1| + 1e-10)) in fp64 -- cos_sim of the normalised maps without forming them.  The
 //                     tile's 64 terms are added in a fixed order (fp64) and written to the workspace.  With `pooled`, the same read
 //                     writes the 2 x 2 stride-2 max-pool of the PRE-ReLU map of both images: the next slice's input (its first
-//                     convolution applies the ReLU, relu(max(y)) = max(relu(y))).  No atomics.
+//                     convolution applies the ReLU, relu(max(y)) = max(relu(y))).  No atomics.  A NaN in y stays one, as in torch.relu
+//                     and F.max_pool2d (ps::relu_keep_nan, max4_keep_nan): in the pair's sums and in the pooled window that holds it.
 //   k_percsim_finish  one workgroup per pair: per layer the tile sums (fp64, a fixed strided order and a fixed tree), 1 - mean, and
 //                     the sum of the five.  A pair's numbers depend neither on its place in the batch nor on the batch's size.
 //
@@ -66,6 +67,14 @@ __global__ __launch_bounds__(256) void k_percsim_input(Img a, Img b, const float
     one(b, out1);
 }
 
+// The maximum of a 2 x 2 window as F.max_pool2d gives it: NaN where the window holds one.  __builtin_elementwise_max is IEEE maxNum
+// (v_max_f32), which returns its other operand for a NaN; __builtin_elementwise_maximum is IEEE 754-2019's maximum (v_maximum3_f32 on
+// gfx950: two instructions a channel, as many as the maxNum took), which hands the NaN on and gives maxNum's bits for anything else.
+__device__ __forceinline__ f32x4 max4_keep_nan(f32x4 a, f32x4 b, f32x4 c, f32x4 d)
+{
+    return __builtin_elementwise_maximum(__builtin_elementwise_maximum(a, b), __builtin_elementwise_maximum(c, d));
+}
+
 template <bool POOL>
 __global__ __launch_bounds__(T_THREADS) void k_percsim_tap(const f32x4 *__restrict__ y, int P, int H, int W, int C, int tiles,
                                                            f32x4 *__restrict__ pooled, double *__restrict__ part)
@@ -86,7 +95,6 @@ __global__ __launch_bounds__(T_THREADS) void k_percsim_tap(const f32x4 *__restri
     }
     const size_t pq = (size_t)(H >> 1) * Wq;
     const size_t poff0 = ((size_t)pair * pq + q) * C4, poff1 = ((size_t)(P + pair) * pq + q) * C4;
-    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
     float dot[4] = {0.f, 0.f, 0.f, 0.f}, n0[4] = {0.f, 0.f, 0.f, 0.f}, n1[4] = {0.f, 0.f, 0.f, 0.f};
     for (int c = l; c < C4; c += 16) {
         f32x4 v0[4], v1[4];
@@ -97,7 +105,7 @@ __global__ __launch_bounds__(T_THREADS) void k_percsim_tap(const f32x4 *__restri
         }
 #pragma unroll
         for (int p = 0; p < 4; ++p) {
-            const f32x4 r0 = __builtin_elementwise_max(v0[p], zero), r1 = __builtin_elementwise_max(v1[p], zero);
+            const f32x4 r0 = ps::relu_keep_nan(v0[p]), r1 = ps::relu_keep_nan(v1[p]);   // (a NaN reaches the pair's sums, as torch's)
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 dot[p] += r0[j] * r1[j];
@@ -106,8 +114,8 @@ __global__ __launch_bounds__(T_THREADS) void k_percsim_tap(const f32x4 *__restri
             }
         }
         if (POOL) {
-            pooled[poff0 + c] = __builtin_elementwise_max(__builtin_elementwise_max(v0[0], v0[1]), __builtin_elementwise_max(v0[2], v0[3]));
-            pooled[poff1 + c] = __builtin_elementwise_max(__builtin_elementwise_max(v1[0], v1[1]), __builtin_elementwise_max(v1[2], v1[3]));
+            pooled[poff0 + c] = max4_keep_nan(v0[0], v0[1], v0[2], v0[3]);
+            pooled[poff1 + c] = max4_keep_nan(v1[0], v1[1], v1[2], v1[3]);
         }
     }
     // the 16 lanes of a quad: a fixed butterfly (every lane ends with the same, order-fixed sums)

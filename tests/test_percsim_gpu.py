@@ -1,7 +1,9 @@
 """GPU: PercSim on the HIP path (csrc/percsim.hip around the split-fp16 convolutions) against the reference's outputs
 (tests/golden/percsim.npz) and the fp64 restatement (tests/golden/percsim_ref64.py), per tap and in total; the torch path outside the
 HIP shapes; bit-level properties (run to run, batch position and size, uint8 = fp32 of x / 255, channels-last = contiguous, vis = the
-explicitly masked images); the overflow guard; score_views; the CLI with --vgg16 on one rank and two."""
+explicitly masked images); the overflow guard; a NaN or +inf pixel, or a NaN in the mask, gives its own pair's score NaN with the
+guard's warning and leaves the others to the torch formula; score_views; the CLI with --vgg16 on one rank and two.  The three passes
+of csrc/percsim.hip on their own: tests/test_percsim_passes_gpu.py."""
 import json
 import os
 import warnings
@@ -112,6 +114,40 @@ def test_overflow_guard_reruns_in_fp32(pnet):
         pnet(t(a) * 2 - 1, t(b) * 2 - 1)                              # the normal weights: no warning
     with f16x3.decoder_conv("fp32"):
         assert not pnet.hip_takes(x0, x1)
+
+
+@pytest.mark.parametrize("value", [float("nan"), float("inf")], ids=["nan", "inf"])
+def test_a_nonfinite_pixel_gives_its_pair_nan_with_the_warning(pnet, value):
+    a, b = syn.metric_pair(39, 2, 3, 256, 256)
+    a = a.copy()
+    a[1, 1, 100, 37] = value
+    x0, x1 = t(a) * 2 - 1, t(b) * 2 - 1
+    assert pnet.hip_takes(x0, x1)
+    with torch.no_grad():
+        want = pnet.torch_forward(x0, x1)
+    assert bool(want[1].isnan()) and bool(want[0].isfinite()), "the torch formula"
+    with pytest.warns(UserWarning, match="fp16's range"):
+        rows = perceptual_rows(pnet, t(a), t(b))
+    with pytest.warns(UserWarning, match="fp16's range"):
+        got = pnet(x0, x1)
+    for mine in (rows[:, 0], got):
+        assert bool(mine[1].isnan()), "a pair with a broken pixel must not come out as a clean number"
+        torch.testing.assert_close(mine[:1], want[:1], rtol=0, atol=1e-6)
+    assert bool(rows[:, 1:].isnan().all())
+
+
+def test_a_nan_in_the_mask_reaches_vis_and_invis_alone(pnet):
+    a, b = syn.metric_pair(40, 2, 3, 256, 256)
+    m = syn.metric_mask("fractional", 41, 2, 256, 256).copy()
+    clean = perceptual_rows(pnet, t(a), t(b), t(m))
+    assert bool(clean.isfinite().all())
+    m[1, 0, 9, 200] = float("nan")
+    with pytest.warns(UserWarning, match="fp16's range"):
+        rows = perceptual_rows(pnet, t(a), t(b), t(m))
+    assert bool(rows[1, 1:].isnan().all()), "vis and invis of the image whose mask holds the NaN"
+    keep = torch.tensor([[True, True, True], [True, False, False]], device=rows.device)
+    assert torch.equal(rows.isfinite(), keep)
+    torch.testing.assert_close(rows[keep], clean[keep], rtol=0, atol=1e-6)          # (the rerun is the torch formula)
 
 
 def test_score_views_columns_match_direct_calls(pnet):
