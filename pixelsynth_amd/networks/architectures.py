@@ -24,19 +24,29 @@ csrc/norm_train.hip -- statistics, norm + ReLU and their backward pass -- for ch
 elsewhere or under decoder_norm_train("torch").  In eval() every path is the stored-statistics form above, untouched.  Under
 decoder_block_train("hip") (block_train.py; the default is "torch") a block's wide 1 x 1 projection and its Up / Down join are
 differentiated by csrc/block_train.hip as well.
-"""
-import os
 
+This file holds what a checkpoint sees and the blocks' dataflow.  Which kernel a convolution or a join gets is decided in conv_routes.py;
+the four route switches and the test of what the kernels accept as a tensor are routing.py's.
+"""
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import block_train, f16x3, norm_train
+from .. import _lib
+from . import conv_routes, norm_train
 from .block_train import decoder_block_train  # noqa: F401
 from .norm_train import decoder_norm_train  # noqa: F401
-from .f16x3 import _FORCED_CONV, check_f16x3_overflow, decoder_conv, decoder_conv_train, flag as _overflow_flag  # noqa: F401  (the names bench.py and the tests use)
+from .f16x3 import check_f16x3_overflow, decoder_conv, decoder_conv_train  # noqa: F401  (the names bench.py and the tests use)
+# The routes are looked up in THIS module's namespace when a block runs: the tests replace _f16x3_conv here with a spy, and bench.py and
+# tools/ reach them as arch.<name>.
+from .conv_routes import (_conv2d_batches, _conv_mode, _conv_split, _f16x3_conv, _f16x3_takes, _f16x3_train_conv,  # noqa: F401
+                          _normalised_weight, _overflow_flag, _plain_conv_weight, _resample, _resample_sum, _sn_hooks, _sn_linear,
+                          _thin_conv, conv1x1, plain_conv)
+from .routing import empty_nhwc, gpu_f32, per_sample
 
 NOISE_SZ = 20
+# "f16x3" | "fp32" (everything through torch / MIOpen): the process default of decoder_conv, read at every call (bench.py assigns it)
+DECODER_CONV = decoder_conv.from_env()
 
 # decoder tables of get_resnet_arch (models/networks/configs.py): first width, then (width, resample) per block.
 _DEC_WIDTHS = lambda g: [g, 2 * g, 4 * g, 4 * g, 2 * g, 2 * g, 2 * g, 3]
@@ -154,17 +164,15 @@ class LinearNoiseLayer(nn.Module):
                 # tensor or one of another device must go the torch way, where it raises the usual device-mismatch error)
                 and all(t.is_cuda and t.device == x.device and t.dtype == torch.float32 and t.is_contiguous() for t in bufs)
                 and (pend is None or (pend.is_cuda and pend.device == x.device and pend.dtype == torch.float32 and pend.is_contiguous()))
-                and all(type(m) is nn.Linear and m.bias is None for m in (self.gain, self.bias))):
-            from torch.nn.utils.spectral_norm import SpectralNorm
+                and self.gain.bias is None and self.bias.bias is None):
             ws = []
             for lin in (self.gain, self.bias):
-                pre = list(lin._forward_pre_hooks.values())
-                if lin._forward_hooks or getattr(lin, "parametrizations", None) or not all(isinstance(h, SpectralNorm) for h in pre):
+                pre = _sn_hooks(lin, nn.Linear)
+                if pre is None:
                     ws = None
                     break
                 ws.append(_normalised_weight(lin, pre, noise).contiguous())
             if ws is not None:
-                from .. import _lib
                 noise = noise.contiguous()
                 scale = torch.empty(B, C, dtype=torch.float32, device=x.device)
                 shift = torch.empty_like(scale)
@@ -175,7 +183,7 @@ class LinearNoiseLayer(nn.Module):
         if pend is not None and not self.bn.training:     # (on batch statistics a constant missing from x cancels: nothing to fold)
             shift = shift - pend.view(1, -1, 1, 1) * scale
         Bx = x.size(0)
-        return scale.reshape(-1, C).expand(Bx, C).contiguous(), shift.reshape(-1, C).expand(Bx, C).contiguous()
+        return per_sample(scale, Bx, C), per_sample(shift, Bx, C)
 
     def forward(self, x, noise=None):
         if self.bn.training:
@@ -206,288 +214,9 @@ def _nhwc(module, x):
     return x.contiguous(memory_format=torch.channels_last)
 
 
-def _is_nhwc_cuda(*ts):
-    """CUDA fp32 tensors in channels_last storage with C a multiple of 4: what csrc/nets.hip takes."""
-    return all(t is not None and t.is_cuda and t.dtype == torch.float32 and t.dim() == 4 and t.size(1) % 4 == 0
-               and t.is_contiguous(memory_format=torch.channels_last) for t in ts)
-
-
-def _empty_nhwc(B, C, H, W, like):
-    return torch.empty((B, C, H, W), dtype=like.dtype, device=like.device, memory_format=torch.channels_last)
-
-
-def _plain_conv_weight(conv, x):
-    """The weight of `conv` as its forward would use it on `x`, for callers that take the convolution apart -- or None when that
-    is not safe.  Only a plain Conv2d, or one whose single extra is the legacy torch.nn.utils.spectral_norm pre-hook (it recomputes
-    .weight from weight_orig / u / v and returns nothing), is taken apart; anything else -- forward hooks, the parametrizations
-    API, a pre-hook that edits the input, another padding mode -- goes through Module.__call__ untouched."""
-    from torch.nn.utils.spectral_norm import SpectralNorm
-    pre = list(conv._forward_pre_hooks.values())
-    plain = (type(conv) is nn.Conv2d and not conv._forward_hooks and not getattr(conv, "parametrizations", None)
-             and conv.padding_mode == "zeros" and all(isinstance(h, SpectralNorm) for h in pre))
-    if not plain:
-        return None
-    return _normalised_weight(conv, pre, x)
-
-
-def _normalised_weight(mod, pre, x):
-    """mod.weight as mod's spectral-norm pre-hooks leave it.  In eval mode the hook does no power iteration -- weight_orig / sigma with
-    sigma from the stored u, v is a constant of the checkpoint, yet torch recomputes it at every forward (a matrix-vector product, a
-    dot and a division: ~270 launches of a few microseconds per decoder pass, a tenth of its time once the convolutions are
-    fast).  Here it is computed once and kept until weight_orig / u / v change (their storage or version counters)."""
-    if not pre:
-        return mod.weight
-    if mod.training or torch.is_grad_enabled():
-        for hook in pre:
-            hook(mod, (x,))
-        return mod.weight
-    key = tuple((t.data_ptr(), t._version) for t in (mod.weight_orig, mod.weight_u, mod.weight_v))
-    cache = mod.__dict__.get("_ps_sn_cache")
-    if cache is None or cache[0] != key:
-        for hook in pre:
-            hook(mod, (x,))
-        cache = (key, mod.weight.detach())
-        mod.__dict__["_ps_sn_cache"] = cache
-    return cache[1]
-
-
-def _sn_linear(lin, x):
-    """lin(x) for the bias-free, possibly spectral-normalised Linear layers of LinearNoiseLayer, the normalised weight cached as above."""
-    from torch.nn.utils.spectral_norm import SpectralNorm
-    pre = list(lin._forward_pre_hooks.values())
-    if (type(lin) is not nn.Linear or lin.bias is not None or lin._forward_hooks or getattr(lin, "parametrizations", None)
-            or not all(isinstance(h, SpectralNorm) for h in pre)):
-        return lin(x)
-    return F.linear(x, _normalised_weight(lin, pre, x))
-
-
-_MIOPEN_SAFE_BYTES = 2 ** 31
-
-
-def _conv2d_batches(fn, x, out_channels, stride=1):
-    """fn(x) -- a convolution through torch (MIOpen) -- with the batch cut so that neither the input nor the output of a call
-    reaches 2 GiB: MIOpen's fp32 NHWC kernels index with 32 bits, and a (128, 128, 256, 256) activation -- 4 GiB, the decoder's
-    widest layer at C5's 128 views -- comes back WRONG, silently (8e-2 of the output's scale against an fp64 convolution,
-    tools/conv_f16x3_big_check.py; at 64 views, 2 GiB, it is right).  The split-fp16 kernel indexes frames with 64 bits."""
-    B = x.size(0)
-    per = max(x[0].numel(), out_channels * (x.size(2) // stride) * (x.size(3) // stride)) * x.element_size()
-    n = max(1, min(B, (_MIOPEN_SAFE_BYTES - 1) // max(per, 1)))
-    if not x.is_cuda or n >= B:
-        return fn(x)
-    return torch.cat([fn(x[i:i + n]) for i in range(0, B, n)])
-
-
-def conv1x1(conv, x):
-    """conv(x) WITHOUT the bias for a 1 x 1 convolution (stride 1, no padding) on a channels-last CUDA fp32 activation, through
-    csrc/conv1x1.hip (fp32 matrix pipe: exact fp32 products) -- or None when `conv` / `x` are not that (the caller goes through torch)."""
-    if not (type(conv) is nn.Conv2d and conv.kernel_size == (1, 1) and conv.stride == (1, 1) and conv.padding == (0, 0)
-            and conv.dilation == (1, 1) and conv.groups == 1 and _is_nhwc_cuda(x) and not torch.is_grad_enabled()):
-        return None
-    from .. import _lib
-    Ci, Co = conv.in_channels, conv.out_channels
-    if not _lib.call("ps_conv1x1_takes", Ci, Co):
-        return None
-    weight = _plain_conv_weight(conv, x)
-    if weight is None or weight.dtype != torch.float32 or not weight.is_cuda or weight.device != x.device:
-        return None
-    key = (weight.data_ptr(), weight._version, str(weight.device))
-    cache = conv.__dict__.get("_ps_1x1_cache")
-    if cache is None or cache[0] != key:
-        cache = (key, weight.detach().reshape(Co, Ci).contiguous(), weight)       # (the weight is kept alive: its address is the key)
-        conv.__dict__["_ps_1x1_cache"] = cache
-    B, _, H, W = x.shape
-    y = _empty_nhwc(B, Co, H, W, x)
-    if Co == 1:   # (channels_last of one channel is ambiguous to torch; the kernel writes (B, H, W, Co))
-        y = torch.empty((B, H, W, Co), dtype=x.dtype, device=x.device).permute(0, 3, 1, 2)
-    _lib.call("ps_conv1x1_nhwc_f32", x, cache[1], B * H * W, Ci, Co, y)
-    return y
-
-
-def _conv_split(conv, x, mode=None, opt=None):
-    """conv(x) as (output WITHOUT the bias, bias) on the inference GPU path -- torch adds a convolution's bias in a pass
-    of its own; here the per-channel constant rides along in whatever pass consumes the output (csrc/nets.hip).  Elsewhere
-    (CPU, autograd, channel counts the kernels do not take): (conv(x), None).  mode "f16x3": a 1 x 1 convolution through
-    csrc/conv1x1.hip instead of torch (MIOpen).  In grad mode with the training opt-in of `opt` (f16x3.train_mode) a wide 3 x 3
-    convolution goes through f16x3.conv3x3_train (_f16x3_train_conv), and with the block opt-in (block_train.mode) a wide 1 x 1
-    convolution through block_train.conv1x1_train (_block_train_conv1x1)."""
-    if mode == "f16x3":
-        y = conv1x1(conv, x)
-        if y is not None:
-            return y, conv.bias
-    y = _f16x3_train_conv(conv, x, opt)
-    if y is not None:
-        return y, None
-    y = _block_train_conv1x1(conv, x, opt)
-    if y is not None:
-        return y, None
-    if conv.bias is None or torch.is_grad_enabled() or not _is_nhwc_cuda(x) or conv.out_channels % 4:
-        return _conv2d_batches(conv, x, conv.out_channels, conv.stride[0]), None
-    weight = _plain_conv_weight(conv, x)
-    if weight is None:
-        return _conv2d_batches(conv, x, conv.out_channels, conv.stride[0]), None
-    return _conv2d_batches(lambda t: F.conv2d(t, weight, None, conv.stride, conv.padding, conv.dilation, conv.groups), x,
-                           conv.out_channels, conv.stride[0]), conv.bias
-
-
-# ---- the wide 3 x 3 convolutions on the fp16 matrix pipe (csrc/conv_f16x3.hip; packing, launch and overflow guard: f16x3.py) ---------
-DECODER_CONV = os.environ.get("PS_DECODER_CONV", "f16x3")   # "f16x3" | "fp32" (everything through torch / MIOpen)
-
-
-def _conv_mode(opt):
-    """Which convolutions a decoder block takes: decoder_conv(...) in effect, else opt.decoder_conv, else PS_DECODER_CONV."""
-    return _FORCED_CONV[-1] if _FORCED_CONV else (getattr(opt, "decoder_conv", None) or DECODER_CONV)
-
-
-def _f16x3_takes(conv, x):
-    return (conv.kernel_size == (3, 3) and conv.stride == (1, 1) and conv.padding == (1, 1) and conv.dilation == (1, 1)
-            and conv.groups == 1 and conv.in_channels % 32 == 0 and conv.out_channels % 64 == 0
-            and _is_nhwc_cuda(x) and x.size(2) % 16 == 0 and x.size(3) % 16 == 0 and x.size(2) * x.size(3) * x.size(1) < 2 ** 31
-            and not torch.is_grad_enabled())
-
-
-def _f16x3_train_conv(conv, x, opt=None):
-    """conv(x) WITH its bias through f16x3.conv3x3_train -- forward and backward pass on the fp16 matrix pipe -- or None: only in grad mode,
-    only under the opt-in (decoder_conv_train("f16x3") / opt.decoder_conv_train / PS_DECODER_CONV_TRAIN; the default is "fp32"), not where
-    decoder_conv("fp32") or the options send the decoder's convolutions through torch, and only for a convolution _f16x3_takes would
-    take without autograd whose Ci is a multiple of 64 as well.  The weight is the module's own (with spectral norm: as its pre-hook
-    leaves it, which is differentiable in training mode) and is packed at every call: training weights change every step."""
-    if not (torch.is_grad_enabled() and f16x3.train_mode(opt) == "f16x3" and _conv_mode(opt) == "f16x3" and type(conv) is nn.Conv2d
-            and conv.kernel_size == (3, 3) and conv.stride == (1, 1) and conv.padding == (1, 1) and conv.dilation == (1, 1)
-            and conv.groups == 1 and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4
-            and f16x3.train_takes(conv.in_channels, conv.out_channels, x.size(2), x.size(3))):
-        return None
-    weight = _plain_conv_weight(conv, x)
-    if weight is None or weight.dtype != torch.float32 or weight.device != x.device:
-        return None
-    x = x.contiguous(memory_format=torch.channels_last)      # (what torch's norm + ReLU in front hands over usually is already)
-    try:
-        return f16x3.conv3x3_train(x, weight, conv.bias)
-    except ValueError:      # a weight fp16 cannot hold: torch, on the weight already normalised (the pre-hook has run once)
-        return F.conv2d(x, weight, conv.bias, 1, 1)
-
-
-def _block_train_conv1x1(conv, x, opt=None):
-    """conv(x) WITH its bias through block_train.conv1x1_train -- csrc/conv1x1.hip forward, csrc/block_train.hip and conv1x1.hip
-    backward -- or None: only in grad mode, only under the opt-in (decoder_block_train("hip") / opt.decoder_block_train /
-    PS_DECODER_BLOCK_TRAIN; the default is "torch"), not where decoder_conv("fp32") or the options send the decoder's convolutions through
-    torch, and only for a plain 1 x 1 convolution (stride 1, no padding, groups 1) on a CUDA fp32 input whose Ci and Co are multiples of 64
-    up to 256 (the projections of the decoder's four resampling blocks) and whose pixels are a multiple of 16.  The weight is the
-    module's own (with spectral norm: as its pre-hook leaves it, which is differentiable in training mode)."""
-    if not (torch.is_grad_enabled() and type(conv) is nn.Conv2d and conv.kernel_size == (1, 1) and conv.stride == (1, 1)
-            and conv.padding == (0, 0) and conv.dilation == (1, 1) and conv.groups == 1 and x.is_cuda and x.dtype == torch.float32
-            and x.dim() == 4 and conv.in_channels % 64 == 0 and conv.out_channels % 64 == 0
-            and max(conv.in_channels, conv.out_channels) <= block_train.MAX_CHANNELS
-            and block_train.mode(opt) == "hip" and _conv_mode(opt) == "f16x3"
-            and block_train.conv1x1_takes(conv.in_channels, conv.out_channels, x.size(0) * x.size(2) * x.size(3))):
-        return None
-    weight = _plain_conv_weight(conv, x)
-    if weight is None or weight.dtype != torch.float32 or weight.device != x.device:
-        return None
-    return block_train.conv1x1_train(x.contiguous(memory_format=torch.channels_last), weight, conv.bias)
-
-
-def _thin_conv(conv, x, scale=None, shift=None):
-    """conv(act(x)) WITHOUT the bias for the decoder's two thin 3 x 3 layers (4 -> Co, Ci -> <= 4 channels) through csrc/conv_thin.hip
-    (fp32 FMAs), or None when `conv` is not one of them."""
-    Ci, Co = conv.in_channels, conv.out_channels
-    thin_in, thin_out = Ci == 4 and Co % 4 == 0 and Co <= 256, Ci % 32 == 0 and 1 <= Co <= 4
-    if not (conv.kernel_size == (3, 3) and conv.stride == (1, 1) and conv.padding == (1, 1) and conv.dilation == (1, 1) and conv.groups == 1
-            and (thin_in or thin_out) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4
-            and x.is_contiguous(memory_format=torch.channels_last)
-            and ((thin_in and Co == 64 and x.size(3) % 16 == 0) or (x.size(2) % 8 == 0 and x.size(3) % (64 if thin_in else 32) == 0))
-            and not torch.is_grad_enabled()):
-        return None
-    weight = _plain_conv_weight(conv, x)
-    if weight is None:
-        return None
-    from .. import _lib
-    key = (weight.data_ptr(), weight._version, str(weight.device))
-    cache = conv.__dict__.get("_ps_thin_cache")
-    if cache is None or cache[0] != key:
-        cache = (key, weight.detach().permute(2, 3, 1, 0).contiguous(), weight)      # [ky][kx][ci][co]
-        conv.__dict__["_ps_thin_cache"] = cache
-    B, _, H, W = x.shape
-    y = _empty_nhwc(B, Co, H, W, x)
-    if Co == 1:   # (channels_last of one channel is ambiguous to torch; the kernel writes (B, H, W, Co))
-        y = torch.empty((B, H, W, Co), dtype=x.dtype, device=x.device).permute(0, 3, 1, 2)
-    if thin_in and Co == 64 and W % 16 == 0:   # on the fp16 matrix pipe (split operands): 82 instead of 270 us per 16 views
-        _lib.call("ps_conv3x3_thin_in_f16x3_nhwc", x, scale, shift, cache[1], B, H, W, Co, y, _overflow_flag(x.device))
-    elif thin_in:
-        _lib.call("ps_conv3x3_thin_in_nhwc_f32", x, scale, shift, cache[1], B, H, W, Co, y)
-    else:
-        _lib.call("ps_conv3x3_thin_out_nhwc_f32", x, scale, shift, cache[1], B, H, W, Ci, Co, y)
-    return y
-
-
-def _f16x3_conv(conv, x, scale=None, shift=None, bias=None, res=None):
-    """conv(act(x)) WITHOUT the convolution's own bias through the split-fp16 kernel (f16x3.conv3x3), act = max(x * scale - shift, 0)
-    with scale / shift (B, C) contiguous, or the identity; `bias` (Co) and `res` (an NHWC tensor of the output's shape) are added on the
-    way out.  None when the kernel does not take this convolution (the caller then goes through torch)."""
-    if not _f16x3_takes(conv, x):
-        return None
-    weight = _plain_conv_weight(conv, x)
-    if weight is None:
-        return None
-    key = (weight.data_ptr(), weight._version, str(weight.device))
-    cache = conv.__dict__.get("_ps_f16x3_cache")
-    if cache is None or cache[0] != key:     # packed once per weight (with spectral norm in eval mode: per checkpoint, see _normalised_weight)
-        try:
-            packed = f16x3.pack3x3(weight.detach())
-        except ValueError:                   # a weight fp16 cannot hold: this layer stays on torch
-            packed = None
-        cache = (key, packed, weight)        # (the weight is kept alive: its address is the key)
-        conv.__dict__["_ps_f16x3_cache"] = cache
-    if cache[1] is None or (res is not None and not (_is_nhwc_cuda(res) and res.shape == (x.size(0), conv.out_channels) + x.shape[2:])):
-        return None
-    return f16x3.conv3x3(x, cache[1], scale, shift, bias, res)
-
-
 def _sum_bias(*bs):
     bs = [b for b in bs if b is not None]
     return None if not bs else bs[0] if len(bs) == 1 else (bs[0] + bs[1]).contiguous()
-
-
-def _resample_sum(kind, a, b, bias=None, post=None, opt=None):
-    """_resample(kind, a + bias) + _resample(kind, b) -- blocks.py:61-73 -- as ONE pass through csrc/nets.hip on the GPU
-    (`bias`: per-channel constant still missing from the inputs, see _conv_split).  b = None: a alone -- resampling is linear, so
-    a caller that already holds the SUM of the two branches resamples once.  post ('Down' only): a tensor of the output's shape added
-    after the pooling.  Where autograd follows an operand: through block_train.resample_sum_train under its opt-in (block_train.mode(opt)
-    "hip"; `bias` and `post` None, which they are in grad mode), else through torch."""
-    from .. import _lib
-    # (an operand that autograd follows goes through torch: the HIP passes are forward-only and would cut the graph)
-    graph = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (a, b, bias, post))
-    if graph and bias is None and post is None and block_train.mode(opt) == "hip" and block_train.resample_takes(kind, a, b):
-        return block_train.resample_sum_train(kind, a, b)
-    if (graph or not (_is_nhwc_cuda(a) if b is None else _is_nhwc_cuda(a, b)) or (b is not None and a.shape != b.shape)
-            or (kind and kind != "Up" and (a.size(2) % 2 or a.size(3) % 2)) or (b is None and not kind)):
-        if bias is not None:
-            a = a + bias.view(1, -1, 1, 1)
-        out = _resample(kind, a) if b is None else _resample(kind, a) + _resample(kind, b)
-        return out if post is None else out + post
-    B, C, H, W = a.shape
-    if not kind:
-        out = torch.empty_like(a)
-        _lib.call("ps_add_bias_nhwc_f32", a, b, bias, B, H * W, C, out)
-    elif kind == "Up":
-        out = _empty_nhwc(B, C, 2 * H, 2 * W, a)
-        _lib.call("ps_upsample_add_nhwc_f32", a, b, bias, B, H, W, C, out)
-    else:
-        out = _empty_nhwc(B, C, H // 2, W // 2, a)
-        if post is not None and not (_is_nhwc_cuda(post) and post.shape == out.shape):
-            raise ValueError("_resample_sum: post must be a channels_last tensor of the pooled shape")
-        _lib.call("ps_pool_add_post_nhwc_f32", a, b, bias, post, B, H, W, C, out)
-        return out
-    if post is not None:
-        raise ValueError("_resample_sum: post goes with 'Down' only")
-    return out
-
-
-def _resample(kind, x):
-    if kind == "Up":
-        return F.interpolate(x, scale_factor=2, mode="bilinear", align_corners=False)
-    if kind:            # "Down" or True
-        return F.avg_pool2d(x, kernel_size=3, stride=2, padding=1)
-    return x
 
 
 def _on_batch_stats(layer):
@@ -518,7 +247,7 @@ class ResNet_Block(nn.Module):
             if x.is_cuda:      # (what the convolution or resampling in front hands over usually is already)
                 x = x.contiguous(memory_format=torch.channels_last)
             return norm_train.batch_norm_train(x, gain, offset, layer.bn, True, bias)
-        if affine is None and _is_nhwc_cuda(x) and not torch.is_grad_enabled() and hasattr(layer, "affine_bc"):
+        if affine is None and gpu_f32(x, multiple=4) and not torch.is_grad_enabled() and hasattr(layer, "affine_bc"):
             affine = layer.affine_bc(x, noise, bias)
         if affine is not None:   # (bias already folded in; as (B, C) or broadcastable to (B, C, 1, 1))
             scale, shift = (t.view(t.size(0), -1, 1, 1) if t.dim() == 2 else t for t in affine)
@@ -527,12 +256,9 @@ class ResNet_Block(nn.Module):
             if bias is not None:
                 shift = shift - bias.view(1, -1, 1, 1) * scale
         B, C = x.size(0), x.size(1)
-        if _is_nhwc_cuda(x) and scale.numel() in (C, B * C) and not torch.is_grad_enabled():
-            from .. import _lib
-            sc = scale.reshape(-1, C).expand(B, C).contiguous()
-            sh = shift.reshape(-1, C).expand(B, C).contiguous()
+        if gpu_f32(x, multiple=4) and scale.numel() in (C, B * C) and not torch.is_grad_enabled():
             y = torch.empty_like(x)   # (preserves channels_last)
-            _lib.call("ps_affine_relu_nhwc_f32", x, sc, sh, B, x.size(2) * x.size(3), C, y)
+            _lib.call("ps_affine_relu_nhwc_f32", x, per_sample(scale, B, C), per_sample(shift, B, C), B, x.size(2) * x.size(3), C, y)
             return y
         return torch.clamp_min(torch.addcmul(-shift, x, scale), 0)
 
@@ -569,8 +295,8 @@ class ResNet_Block(nn.Module):
         a, ba, _ = self._norm_relu_conv(self.ch_a[0], self.ch_a[2], x, noise[0])
         mode = _conv_mode(self.opt)
         # (not in train(): the test of the 1 x 1 weight below would run its spectral norm's power iteration a second time)
-        if (self.resample and self.resample != "Up" and mode == "f16x3" and _is_nhwc_cuda(x) and not torch.is_grad_enabled() and not self.training
-                and x.size(2) % 2 == 0 and x.size(3) % 2 == 0 and self.ch_b[0].kernel_size == (1, 1) and self.ch_b[0].stride == (1, 1)
+        if (self.resample and self.resample != "Up" and mode == "f16x3" and gpu_f32(x, multiple=4) and not torch.is_grad_enabled() and not self.training
+                and x.size(2) % 2 == 0 and x.size(3) % 2 == 0 and plain_conv(self.ch_b[0], 1, 0)
                 # (the 1 x 1 conv's bias must come back SEPARATE from _conv_split, to go through the pool's bias * inside / 9 term: a
                 # convolution that cannot be taken apart returns conv(x) + bias, whose border pixels would then differ from the reference's)
                 and (self.ch_b[0].bias is None or (self.ch_b[0].out_channels % 4 == 0 and _plain_conv_weight(self.ch_b[0], x) is not None))):
@@ -609,12 +335,11 @@ class ResNetDecoder(nn.Module):
         return 2 * len(self.eblocks)
 
     def forward(self, x, background_mask=None, noise=None):
-        if (background_mask is not None and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.size(1) == 3 and x.is_contiguous()
+        if (background_mask is not None and gpu_f32(x, layout=torch.contiguous_format) and x.size(1) == 3
                 and background_mask.dtype == torch.bool and background_mask.is_contiguous()
                 and background_mask.shape == (x.size(0), x.size(2), x.size(3)) and not torch.is_grad_enabled()):
-            from .. import _lib
             B, _, H, W = x.shape
-            h = _empty_nhwc(B, 4, H, W, x)          # cat + NCHW -> NHWC in one pass
+            h = empty_nhwc(B, 4, H, W, x)          # cat + NCHW -> NHWC in one pass
             _lib.call("ps_cat_mask_nhwc_f32", x, background_mask, B, H, W, h)
             _nhwc(self, h)                            # (the weights, once)
         else:
@@ -664,7 +389,7 @@ class Unet(nn.Module):
         """dconv8 reads 2 f channels at the input's size: the call's batch keeps that activation below the 2 GiB at which MIOpen's fp32
         kernels start to index wrongly (_conv2d_batches) -- by bytes, so at 512 x 512 it is a quarter of what it is at 256 x 256."""
         per = self.dconv8.in_channels * H * W * 4
-        return max(1, min(self.MAX_BATCH, (_MIOPEN_SAFE_BYTES - 1) // per))
+        return max(1, min(self.MAX_BATCH, (conv_routes._MIOPEN_SAFE_BYTES - 1) // per))
 
     @staticmethod
     def _conv(conv, x):

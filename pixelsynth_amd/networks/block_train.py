@@ -12,54 +12,19 @@ resample_sum_train(kind, a, b)     resample(a) + resample(b) -- bilinear x2 for 
 The switch, for the decoder's blocks (networks/architectures.py): decoder_block_train(...) in effect, else opt.decoder_block_train, else
 PS_DECODER_BLOCK_TRAIN; the default "torch" leaves every call where it was.
 """
-import os
-
 import torch
 
 from .. import _lib
+from .routing import Switch, empty_nhwc, gpu_f32, grad_nhwc
 
-
-def _env_mode(environ=None):
-    """PS_DECODER_BLOCK_TRAIN of `environ` (the process's): "torch" unless set"""
-    return (os.environ if environ is None else environ).get("PS_DECODER_BLOCK_TRAIN", "torch")
-
-
-_FORCED = []        # decoder_block_train(mode) in effect, innermost last
-DECODER_BLOCK_TRAIN = _env_mode()   # "torch" (the shortcut and the join through torch autograd) | "hip" (the Functions below)
+# with decoder_block_train("hip"): ... -- in grad mode a decoder block's 1 x 1 projection (Ci and Co multiples of 64, at most 256) and its
+# resample-and-sum inside go through conv1x1_train / resample_sum_train; "torch": through torch autograd, whatever the options say.
+decoder_block_train = Switch("decoder_block_train", "PS_DECODER_BLOCK_TRAIN", ("hip", "torch"), "torch", __name__, "DECODER_BLOCK_TRAIN",
+                             attr="decoder_block_train")
+DECODER_BLOCK_TRAIN = decoder_block_train.from_env()   # "torch" (the shortcut and the join through torch autograd) | "hip" (the Functions below)
+mode = decoder_block_train.resolve                     # the route in effect for a block whose options are `opt`
 _WS = _lib.Workspace()
 MAX_CHANNELS = 256
-
-
-class decoder_block_train:
-    """with decoder_block_train("hip"): ... -- in grad mode a decoder block's 1 x 1 projection (Ci and Co multiples of 64, at most 256)
-    and its resample-and-sum inside go through conv1x1_train / resample_sum_train; "torch": through torch autograd, whatever the options
-    say."""
-
-    def __init__(self, mode):
-        if mode not in ("hip", "torch"):
-            raise ValueError("decoder_block_train: 'hip' or 'torch'")
-        self.mode = mode
-
-    def __enter__(self):
-        _FORCED.append(self.mode)
-        return self
-
-    def __exit__(self, *exc):
-        _FORCED.pop()
-        return False
-
-
-def mode(opt=None):
-    """The route in effect: decoder_block_train(...) innermost, else opt.decoder_block_train, else PS_DECODER_BLOCK_TRAIN ("torch")"""
-    m = _FORCED[-1] if _FORCED else (getattr(opt, "decoder_block_train", None) or DECODER_BLOCK_TRAIN)
-    if m not in ("hip", "torch"):
-        raise ValueError(f"decoder_block_train / PS_DECODER_BLOCK_TRAIN = {m!r}: 'hip' or 'torch'")
-    return m
-
-
-def _nhwc_f32(t):
-    return (t.is_cuda and t.dtype == torch.float32 and t.dim() == 4 and t.is_contiguous(memory_format=torch.channels_last)
-            and t.data_ptr() % 16 == 0)
 
 
 # ---- the 1 x 1 convolution ---------------------------------------------------------------------------------------------------------------
@@ -78,7 +43,7 @@ class _Conv1x1Train(torch.autograd.Function):
         B, Ci, H, W = x.shape
         Co = weight.size(0)
         w2 = weight.detach().reshape(Co, Ci).contiguous()
-        y = torch.empty((B, Co, H, W), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
+        y = empty_nhwc(B, Co, H, W, x)
         _lib.call("ps_conv1x1_ex_nhwc_f32", x, Ci, w2, None if bias is None else bias.detach().contiguous(), None, 0, B * H * W, Ci, Co, y)
         ctx.save_for_backward(x, weight)
         ctx.has_bias = bias is not None
@@ -91,7 +56,7 @@ class _Conv1x1Train(torch.autograd.Function):
         B, Ci, H, W = x.shape
         Co, dev, npix = weight.size(0), x.device, B * H * W
         need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.has_bias and ctx.needs_input_grad[2]
-        g = grad_y.to(torch.float32).contiguous(memory_format=torch.channels_last)       # (a sliced or expanded grad_y: one copy)
+        g = grad_nhwc(grad_y)
         gx = gw = gb = None
         if need_x:
             w2 = weight.detach().reshape(Co, Ci)
@@ -113,7 +78,7 @@ def conv1x1_train(x, weight, bias=None):
     """conv2d(x, weight, bias) for a 1 x 1 weight (stride 1, no padding) through csrc/conv1x1.hip, differentiable once in x, weight and
     bias.  x (B, Ci, H, W) channels_last fp32 on the device, weight (Co, Ci, 1, 1) or (Co, Ci), bias (Co) or None; conv1x1_takes(Ci, Co,
     B H W) sizes.  ValueError for anything else: the caller goes through torch."""
-    if not (_nhwc_f32(x) and x.numel() > 0):
+    if not (gpu_f32(x, aligned=True) and x.numel() > 0):
         raise ValueError("conv1x1_train: x must be a channels_last fp32 tensor (B, Ci, H, W) on the device")
     Ci = x.size(1)
     if not (weight.dim() in (2, 4) and weight.shape[:2] == (weight.size(0), Ci) and weight.numel() == weight.size(0) * Ci
@@ -130,8 +95,8 @@ def conv1x1_train(x, weight, bias=None):
 def resample_takes(kind, a, b=None):
     """What resample_sum_train takes: kind "Up" or "Down"; channels-last CUDA fp32 operands of equal shape with C a multiple of 4; even
     sides for "Down" """
-    return (kind in ("Up", "Down") and _nhwc_f32(a) and a.size(1) % 4 == 0 and a.numel() > 0
-            and (b is None or (_nhwc_f32(b) and b.shape == a.shape and b.device == a.device))
+    return (kind in ("Up", "Down") and gpu_f32(a, multiple=4, aligned=True) and a.numel() > 0
+            and (b is None or (gpu_f32(b, aligned=True) and b.shape == a.shape and b.device == a.device))
             and (kind == "Up" or (a.size(2) % 2 == 0 and a.size(3) % 2 == 0)))
 
 
@@ -140,10 +105,10 @@ class _ResampleSum(torch.autograd.Function):
     def forward(ctx, kind, a, b):
         B, C, H, W = a.shape
         if kind == "Up":
-            out = torch.empty((B, C, 2 * H, 2 * W), dtype=a.dtype, device=a.device, memory_format=torch.channels_last)
+            out = empty_nhwc(B, C, 2 * H, 2 * W, a)
             _lib.call("ps_upsample_add_nhwc_f32", a, b, None, B, H, W, C, out)
         else:
-            out = torch.empty((B, C, H // 2, W // 2), dtype=a.dtype, device=a.device, memory_format=torch.channels_last)
+            out = empty_nhwc(B, C, H // 2, W // 2, a)
             _lib.call("ps_pool_add_nhwc_f32", a, b, None, B, H, W, C, out)
         ctx.kind, ctx.shape, ctx.two = kind, tuple(a.shape), b is not None
         return out
@@ -155,8 +120,8 @@ class _ResampleSum(torch.autograd.Function):
         need_a, need_b = ctx.needs_input_grad[1], ctx.two and ctx.needs_input_grad[2]
         if not (need_a or need_b):
             return None, None, None
-        g = grad_out.to(torch.float32).contiguous(memory_format=torch.channels_last)
-        gin = torch.empty((B, C, H, W), dtype=torch.float32, device=g.device, memory_format=torch.channels_last)
+        g = grad_nhwc(grad_out)
+        gin = empty_nhwc(B, C, H, W, g)
         _lib.call("ps_upsample_add_bwd_nhwc_f32" if ctx.kind == "Up" else "ps_pool_add_bwd_nhwc_f32", g, B, H, W, C, gin)
         return None, gin if need_a else None, gin if need_b else None
 

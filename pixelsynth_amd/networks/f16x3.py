@@ -10,72 +10,29 @@ torch.autograd.Function whose backward pass runs on the same matrix pipe -- grad
 as a GEMM over the pixels, grad_input as the forward kernel on the flipped, transposed weight.  It is opt-in for the decoder's blocks:
 decoder_conv_train("f16x3"), opt.decoder_conv_train or PS_DECODER_CONV_TRAIN; the default "fp32" leaves every call where it is.
 """
-import os
 import warnings
 
 import torch
 
 from .. import _lib
+from .routing import Switch, empty_nhwc, gpu_f32, grad_nhwc
 
-_FORCED_CONV = []   # decoder_conv(mode) in effect, innermost last
 _flags = {}         # str(device) -> int32 (1,) overflow flag
 _open = set()       # str(device) of the guarded scopes open
 
+# with decoder_conv("fp32"): ... -- every split-fp16 convolution inside (decoder and VQ-VAE) through torch (MIOpen fp32), whatever the
+# options say: how checked() reruns a pass whose split-fp16 convolutions met an activation beyond fp16's range.  The process default is
+# architectures.DECODER_CONV, which the benchmark assigns.
+decoder_conv = Switch("decoder_conv", "PS_DECODER_CONV", ("f16x3", "fp32"), "f16x3", __package__ + ".architectures", "DECODER_CONV",
+                      attr="decoder_conv")
+forced_mode = decoder_conv.forced      # the mode of the innermost decoder_conv(...) in effect, or None
 
-def forced_mode():
-    """The mode of the innermost decoder_conv(...) in effect, or None."""
-    return _FORCED_CONV[-1] if _FORCED_CONV else None
-
-
-class decoder_conv:
-    """with decoder_conv("fp32"): ... -- every split-fp16 convolution inside (decoder and VQ-VAE) through torch (MIOpen fp32), whatever
-    the options say: how checked() reruns a pass whose split-fp16 convolutions met an activation beyond fp16's range."""
-
-    def __init__(self, mode):
-        if mode not in ("f16x3", "fp32"):
-            raise ValueError("decoder_conv: 'f16x3' or 'fp32'")
-        self.mode = mode
-
-    def __enter__(self):
-        _FORCED_CONV.append(self.mode)
-        return self
-
-    def __exit__(self, *exc):
-        _FORCED_CONV.pop()
-        return False
-
-
-def _env_train_mode(environ=None):
-    """PS_DECODER_CONV_TRAIN of `environ` (the process's): "fp32" unless set"""
-    return (os.environ if environ is None else environ).get("PS_DECODER_CONV_TRAIN", "fp32")
-
-
-_FORCED_TRAIN = []  # decoder_conv_train(mode) in effect, innermost last
-DECODER_CONV_TRAIN = _env_train_mode()   # "fp32" (training convolutions through torch autograd) | "f16x3" (conv3x3_train)
-
-
-class decoder_conv_train:
-    """with decoder_conv_train("f16x3"): ... -- in grad mode the decoder blocks' wide 3 x 3 convolutions (Ci and Co multiples of 64, H and
-    W multiples of 16) inside go through conv3x3_train; "fp32": through torch autograd, whatever the options say."""
-
-    def __init__(self, mode):
-        if mode not in ("f16x3", "fp32"):
-            raise ValueError("decoder_conv_train: 'f16x3' or 'fp32'")
-        self.mode = mode
-
-    def __enter__(self):
-        _FORCED_TRAIN.append(self.mode)
-        return self
-
-    def __exit__(self, *exc):
-        _FORCED_TRAIN.pop()
-        return False
-
-
-def train_mode(opt=None):
-    """Which route a decoder block's 3 x 3 convolution takes in grad mode: decoder_conv_train(...) in effect, else opt.decoder_conv_train,
-    else PS_DECODER_CONV_TRAIN ("fp32")."""
-    return _FORCED_TRAIN[-1] if _FORCED_TRAIN else (getattr(opt, "decoder_conv_train", None) or DECODER_CONV_TRAIN)
+# with decoder_conv_train("f16x3"): ... -- in grad mode the decoder blocks' wide 3 x 3 convolutions (Ci and Co multiples of 64, H and W
+# multiples of 16) inside go through conv3x3_train; "fp32": through torch autograd, whatever the options say.
+decoder_conv_train = Switch("decoder_conv_train", "PS_DECODER_CONV_TRAIN", ("f16x3", "fp32"), "fp32", __name__, "DECODER_CONV_TRAIN",
+                            attr="decoder_conv_train")
+DECODER_CONV_TRAIN = decoder_conv_train.from_env()   # "fp32" (training convolutions through torch autograd) | "f16x3" (conv3x3_train)
+train_mode = decoder_conv_train.resolve              # which route a decoder block's 3 x 3 convolution takes in grad mode
 
 
 def flag(device):
@@ -152,7 +109,7 @@ def conv3x3(x, p, scale=None, shift=None, bias=None, res=None, overflow=None):
         C, H, W = 4 * C, H // 2, W // 2
     assert C == p["Ci"] and x.is_contiguous(memory_format=torch.channels_last)
     shape = (B, p["Co"] // 4, 2 * H, 2 * W) if p["d2s"] else (B, p["Co"], H, W)
-    y = torch.empty(shape, dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
+    y = empty_nhwc(*shape, x)
     bias = p["bias"] if bias is None else bias
     _lib.call("ps_conv3x3_f16x3_ex_nhwc", x, scale, shift, p["packed"], bias, res, B, H, W, C, p["Co"], p["live"], int(p["s2d"]),
               int(p["d2s"]), y, flag(x.device) if overflow is None else overflow)
@@ -191,7 +148,7 @@ class _Conv3x3Train(torch.autograd.Function):
         B, Ci, H, W = x.shape
         Co, dev = weight.size(0), x.device
         need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.has_bias and ctx.needs_input_grad[2]
-        g = grad_y.to(torch.float32).contiguous(memory_format=torch.channels_last)       # (a sliced or expanded grad_y: one copy)
+        g = grad_nhwc(grad_y)
         ws = _WS.query(dev, "ps_conv3x3_bwd_workspace_bytes", B, H, W, Ci, Co)
         gs = torch.empty_like(g)                                                          # (preserves channels_last)
         scale2 = torch.empty(2, dtype=torch.float32, device=dev)
@@ -218,7 +175,7 @@ def conv3x3_train(x, weight, bias=None):
     H, W) sizes.  ValueError for anything else, or for a weight fp16 cannot hold (the forward's pack3x3 synchronises to find out): the
     caller goes through torch.  An activation beyond fp16's range raises flag(x.device), as in the no-grad route: checked() or
     check_f16x3_overflow() is the caller's."""
-    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.is_contiguous(memory_format=torch.channels_last)):
+    if not gpu_f32(x):
         raise ValueError("conv3x3_train: x must be a channels_last fp32 tensor (B, Ci, H, W) on the device")
     if not (weight.dim() == 4 and tuple(weight.shape[1:]) == (x.size(1), 3, 3) and weight.dtype == torch.float32 and weight.device == x.device
             and train_takes(x.size(1), weight.size(0), x.size(2), x.size(3))):

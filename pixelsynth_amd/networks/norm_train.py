@@ -14,53 +14,22 @@ Both routes update bn.stored_mean / bn.stored_var from detached statistics, unde
 bn.accumulate_standing, sums and bn.accumulation_counter.  `pend` (C) is a convolution bias still missing from x: it shifts the batch mean
 and nothing else, so it goes into the stored mean only -- y does not change, (x + pend) - (mean + pend) = x - mean.
 """
-import os
-
 import torch
 
 from .. import _lib
+from .routing import Switch, gpu_f32, grad_nhwc, per_sample
 
-
-def _env_mode(environ=None):
-    """PS_DECODER_NORM_TRAIN of `environ` (the process's): "hip" unless set"""
-    return (os.environ if environ is None else environ).get("PS_DECODER_NORM_TRAIN", "hip")
-
-
-_FORCED = []        # decoder_norm_train(mode) in effect, innermost last
-DECODER_NORM_TRAIN = _env_mode()
+# with decoder_norm_train("torch"): ... -- every training-mode noise-conditioned batch norm inside through the torch formula; "hip":
+# through csrc/norm_train.hip where takes(x) holds.  The one switch without an option: the norm layers hold no `opt`.
+decoder_norm_train = Switch("decoder_norm_train", "PS_DECODER_NORM_TRAIN", ("hip", "torch"), "hip", __name__, "DECODER_NORM_TRAIN")
+DECODER_NORM_TRAIN = decoder_norm_train.from_env()
+mode = decoder_norm_train.resolve      # the route in effect
 _WS = _lib.Workspace()
-
-
-class decoder_norm_train:
-    """with decoder_norm_train("torch"): ... -- every training-mode noise-conditioned batch norm inside through the torch formula;
-    "hip": through csrc/norm_train.hip where takes(x) holds."""
-
-    def __init__(self, mode):
-        if mode not in ("hip", "torch"):
-            raise ValueError("decoder_norm_train: 'hip' or 'torch'")
-        self.mode = mode
-
-    def __enter__(self):
-        _FORCED.append(self.mode)
-        return self
-
-    def __exit__(self, *exc):
-        _FORCED.pop()
-        return False
-
-
-def mode():
-    """The route in effect: decoder_norm_train(...) innermost, else PS_DECODER_NORM_TRAIN ("hip")"""
-    m = _FORCED[-1] if _FORCED else DECODER_NORM_TRAIN
-    if m not in ("hip", "torch"):
-        raise ValueError(f"PS_DECODER_NORM_TRAIN={m!r}: 'hip' or 'torch'")
-    return m
 
 
 def takes(x):
     """What the HIP route takes: a CUDA fp32 (B, C, H, W) tensor in channels-last storage with C a multiple of 4"""
-    return (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.size(1) % 4 == 0 and x.numel() > 0
-            and x.is_contiguous(memory_format=torch.channels_last))
+    return gpu_f32(x, multiple=4) and x.numel() > 0
 
 
 def _store(bn, mean, var, pend=None):
@@ -126,7 +95,7 @@ class _NormTrain(torch.autograd.Function):
         x, mean, rstd, gain, bias = ctx.saved_tensors
         B, C, H, W = x.shape
         dev = x.device
-        dy = grad_y.to(torch.float32).contiguous(memory_format=torch.channels_last)
+        dy = grad_nhwc(grad_y)
         ws = _WS.query(dev, "ps_norm_train_workspace_bytes", B, H * W, C)
         dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
         dgain, dbias = torch.empty_like(gain), torch.empty_like(gain)
@@ -136,7 +105,7 @@ class _NormTrain(torch.autograd.Function):
 
 def _plain(t, device):
     """t as the kernels take a per-channel vector or (B, C) table: fp32, contiguous, 16-byte aligned, on `device`"""
-    return t.dtype == torch.float32 and t.device == device and t.is_contiguous() and t.data_ptr() % 16 == 0
+    return gpu_f32(t, layout=torch.contiguous_format, aligned=True, dims=None) and t.device == device
 
 
 def batch_norm_train(x, gain, bias, bn, relu, pend=None):
@@ -147,7 +116,7 @@ def batch_norm_train(x, gain, bias, bn, relu, pend=None):
     if (mode() == "hip" and takes(x) and _plain(bn.stored_mean, x.device) and _plain(bn.stored_var, x.device)
             and x.size(2) * x.size(3) * C < 2 ** 31 and gain.dtype == bias.dtype == torch.float32 and gain.device == bias.device == x.device
             and (pend is None or (pend.dtype == torch.float32 and pend.device == x.device and pend.numel() == C))):
-        g2, b2 = (t.reshape(-1, C).expand(B, C).contiguous() for t in (gain, bias))
+        g2, b2 = per_sample(gain, B, C), per_sample(bias, B, C)
         if pend is not None:
             pend = pend.detach().reshape(C)
             if not _plain(pend, x.device):

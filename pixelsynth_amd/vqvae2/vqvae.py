@@ -382,7 +382,7 @@ class VQVAETop(nn.Module):
 
     # ---------------------------------------------------------------- the novel-view path
     MAX_BATCH = 256   # views per call on the GPU, at most
-    _MIOPEN_SAFE_BYTES = 2 ** 31   # where MIOpen's fp32 kernels start to index wrongly (networks/architectures.py:_conv2d_batches)
+    _MIOPEN_SAFE_BYTES = 2 ** 31   # where MIOpen's fp32 kernels start to index wrongly (networks/conv_routes.py:_conv2d_batches)
 
     def _views_per_call(self, H, W):
         """Views per call on the GPU for (H, W) IMAGES: the widest activation on either side of the codes -- channel / 2 maps at half the

@@ -1,9 +1,9 @@
 """CPU-only: the host side of a decoder block's training passes (csrc/block_train.hip, networks/block_train.py): the C ABI of
 libpixelsynth_block_train.so against its header and bindings, the split of the pixels into parts against its pure-Python mirror, the
-refusals before anything is launched, the fp64 formulas of tests/_block_train_ref.py (gradcheck, the adjoint identity), and the switch."""
+refusals before anything is launched, the fp64 formulas of tests/_block_train_ref.py (gradcheck, the adjoint identity); the switch is in
+tests/test_decoder_routing_cpu.py."""
 import os
 import re
-import types
 
 import pytest
 import torch
@@ -148,27 +148,6 @@ def test_gradcheck_of_the_conv1x1_formula():
     assert ref.check("fp32 autograd grad_weight", w32, w64, bound) < 1.0
     g[0, :, 0, 0] = 0
     assert ref.check("grad_weight without a pixel", ref.conv1x1_grads(x, w, b, g, torch.float32)[1], w64, bound) > 1.0
-
-
-def test_the_switch(monkeypatch):
-    assert BT._env_mode({}) == "torch" and BT._env_mode({"PS_DECODER_BLOCK_TRAIN": "hip"}) == "hip"
-    monkeypatch.setattr(BT, "DECODER_BLOCK_TRAIN", BT._env_mode({}))
-    assert BT.mode() == "torch" and BT.mode(types.SimpleNamespace()) == "torch" and A.decoder_block_train is BT.decoder_block_train
-    opt = types.SimpleNamespace(decoder_block_train="hip")
-    assert BT.mode(opt) == "hip"                                   # the options over the environment
-    monkeypatch.setattr(BT, "DECODER_BLOCK_TRAIN", "hip")
-    assert BT.mode() == "hip" and BT.mode(types.SimpleNamespace(decoder_block_train="torch")) == "torch"
-    with BT.decoder_block_train("torch"):                          # the context manager over both
-        assert BT.mode(opt) == "torch" and BT.mode() == "torch"
-        with BT.decoder_block_train("hip"):
-            assert BT.mode(types.SimpleNamespace(decoder_block_train="torch")) == "hip"
-        assert BT.mode(opt) == "torch"
-    assert BT.mode() == "hip"
-    with pytest.raises(ValueError, match="'hip' or 'torch'"):
-        BT.decoder_block_train("f16x3")
-    monkeypatch.setattr(BT, "DECODER_BLOCK_TRAIN", "fast")
-    with pytest.raises(ValueError, match="PS_DECODER_BLOCK_TRAIN"):
-        BT.mode()
 
 
 def test_on_the_host_the_opt_in_changes_nothing(monkeypatch):

@@ -122,20 +122,11 @@ def test_entry_points_refuse_before_anything_is_launched():
 
 
 def test_the_opt_in_defaults_to_fp32(monkeypatch):
-    assert f16x3._env_train_mode({}) == "fp32" and f16x3._env_train_mode({"PS_DECODER_CONV_TRAIN": "f16x3"}) == "f16x3"
+    """(the switch itself: tests/test_decoder_routing_cpu.py)"""
+    assert f16x3.decoder_conv_train.from_env({}) == "fp32"
     assert f16x3.DECODER_CONV_TRAIN == os.environ.get("PS_DECODER_CONV_TRAIN", "fp32")
     monkeypatch.setattr(f16x3, "DECODER_CONV_TRAIN", "fp32")
-    assert f16x3.train_mode() == "fp32" and f16x3.train_mode(object()) == "fp32"
-    import argparse
-    assert f16x3.train_mode(argparse.Namespace(decoder_conv_train="f16x3")) == "f16x3"
-    with f16x3.decoder_conv_train("f16x3"):
-        assert f16x3.train_mode() == "f16x3"
-        with A.decoder_conv_train("fp32"):
-            assert f16x3.train_mode(argparse.Namespace(decoder_conv_train="f16x3")) == "fp32"
-        assert f16x3.train_mode() == "f16x3"
     assert f16x3.train_mode() == "fp32"
-    with pytest.raises(ValueError):
-        f16x3.decoder_conv_train("fp16")
     # on the host nothing is taken: a CPU convolution in grad mode under the opt-in stays torch's
     conv = torch.nn.Conv2d(64, 64, 3, 1, 1)
     x = torch.randn(1, 64, 16, 16, requires_grad=True)

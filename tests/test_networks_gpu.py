@@ -324,7 +324,7 @@ def test_convolutions_through_torch_are_cut_below_2_gib_per_call(monkeypatch):
     """_conv2d_batches: the decoder's convolutions that still go through torch (MIOpen) see at most _MIOPEN_SAFE_BYTES of input or
     output per call.  With the limit lowered so that a 5-view batch is cut into calls of 2, 2 and 1 views: the same image as uncut (1e-5),
     channels_last preserved, and the calls are the expected ones."""
-    from pixelsynth_amd.networks import architectures as A
+    from pixelsynth_amd.networks import architectures as A, conv_routes as C      # (_conv_split, in conv_routes, is who cuts)
     monkeypatch.setattr(A, "DECODER_CONV", "fp32")
     dec = _filled(get_decoder(syn.network_opts()), 9)
     x = torch.from_numpy(syn.image(5, 5, 3, 256)).to(DEV)
@@ -333,17 +333,17 @@ def test_convolutions_through_torch_are_cut_below_2_gib_per_call(monkeypatch):
     with torch.no_grad():
         want = dec(x, bgm, noise=noise)
         sizes = []
-        real = A._conv2d_batches
+        real = C._conv2d_batches
 
         def spy(fn, t, *a, **k):
             return real(lambda u: (sizes.append(u.size(0)), fn(u))[1], t, *a, **k)
-        monkeypatch.setattr(A, "_conv2d_batches", spy)
-        monkeypatch.setattr(A, "_MIOPEN_SAFE_BYTES", 2 * 128 * 256 * 256 * 4 + 1)   # two views of the widest layer
+        monkeypatch.setattr(C, "_conv2d_batches", spy)
+        monkeypatch.setattr(C, "_MIOPEN_SAFE_BYTES", 2 * 128 * 256 * 256 * 4 + 1)   # two views of the widest layer
         got = dec(x, bgm, noise=noise)
     assert 2 in sizes and 1 in sizes and max(sizes) <= 5 and sizes.count(5) > 0    # (narrow layers still go in one call)
     assert (got - want).abs().max().item() < 1e-5      # (MIOpen may pick another algorithm for another batch size: not bit-equal)
     t = torch.randn(5, 8, 16, 16, device=DEV).contiguous(memory_format=torch.channels_last)
-    monkeypatch.setattr(A, "_MIOPEN_SAFE_BYTES", 2 * 8 * 16 * 16 * 4 + 1)
+    monkeypatch.setattr(C, "_MIOPEN_SAFE_BYTES", 2 * 8 * 16 * 16 * 4 + 1)
     out = real(lambda u: u * 2, t, 8)
     assert out.is_contiguous(memory_format=torch.channels_last) and torch.equal(out, t * 2)
 

@@ -260,21 +260,9 @@ def test_the_other_ways_into_the_norm_no_longer_raise():
 
 
 def test_the_switch(monkeypatch):
-    assert NT._env_mode({}) == "hip" and NT._env_mode({"PS_DECODER_NORM_TRAIN": "torch"}) == "torch"
-    monkeypatch.setattr(NT, "DECODER_NORM_TRAIN", NT._env_mode({}))
+    """(the switch itself: tests/test_decoder_routing_cpu.py)"""
+    monkeypatch.setattr(NT, "DECODER_NORM_TRAIN", NT.decoder_norm_train.from_env({}))
     assert NT.mode() == "hip" and A.decoder_norm_train is NT.decoder_norm_train
-    with NT.decoder_norm_train("torch"):
-        assert NT.mode() == "torch"
-        with NT.decoder_norm_train("hip"):
-            assert NT.mode() == "hip"
-        assert NT.mode() == "torch"
-    assert NT.mode() == "hip"
-    with pytest.raises(ValueError, match="'hip' or 'torch'"):
-        NT.decoder_norm_train("fp32")
-    monkeypatch.setattr(NT, "DECODER_NORM_TRAIN", "fast")
-    with pytest.raises(ValueError, match="PS_DECODER_NORM_TRAIN"):
-        NT.mode()
-    monkeypatch.setattr(NT, "DECODER_NORM_TRAIN", "hip")
     # on the host both settings are the torch route: the same bits, and no entry point is called
     calls, real = [], _lib.call
     monkeypatch.setattr(_lib, "call", lambda name, *a, **k: (calls.append(name), real(name, *a, **k))[1])

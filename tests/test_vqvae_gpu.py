@@ -247,7 +247,7 @@ def test_modules_the_kernels_do_not_take_go_through_torch(monkeypatch, kw):
 
 def test_large_batches_are_cut_per_call(monkeypatch):
     """VQVAETop.encode_codes / decode_code and Unet.forward cut a batch beyond MAX_BATCH into several calls (MIOpen's fp32 kernels
-    index wrongly from 2 GiB activations on: networks/architectures.py:_conv2d_batches).  With MAX_BATCH lowered to 2, five views
+    index wrongly from 2 GiB activations on: networks/conv_routes.py:_conv2d_batches).  With MAX_BATCH lowered to 2, five views
     give the codes and images of one call -- codes equal except where two distances tie within float noise, images to 1e-5."""
     from pixelsynth_amd.networks import Unet
     from pixelsynth_amd.vqvae2.vqvae import VQVAETop
