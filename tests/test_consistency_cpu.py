@@ -138,6 +138,33 @@ def test_consistency_library_exports_its_header():
     assert L.ps_consistency_last_error()
 
 
+def test_consistency_library_refuses_sizes_and_alignment_before_any_launch():
+    import ctypes
+    strides = (ctypes.c_int64 * 4)(3 * 64, 64, 8, 1)
+    p = 4096                                        # stands for a device pointer: every refusal below comes before one is read
+
+    def call(H, W, mode=0, pin=None, ws_bytes=1 << 30):
+        _lib.call("ps_consistency", p, strides, p, strides, 0, p, p, 0, p, 1, H, W, mode, pin, p, p, ws_bytes, stream=0)
+    for H, W in ((32768, 8), (8, 32768), (0, 8), (8, 0), (40000, 40000)):     # sat_short's range: a column 32767 must stay outside
+        with pytest.raises(RuntimeError, match=r"1 <= H, W <= 32767 required \(H = %d, W = %d\)" % (H, W)):
+            call(H, W)
+    with pytest.raises(RuntimeError, match="percsim_in must be 16-byte aligned"):
+        call(8, 8, mode=1, pin=p + 8)
+    with pytest.raises(RuntimeError, match="percsim_in must be 16-byte aligned"):
+        call(8, 8, mode=2, pin=p + 4)
+    with pytest.raises(RuntimeError, match="percsim_in goes with"):
+        call(8, 8, mode=0, pin=p)
+    with pytest.raises(RuntimeError, match="percsim_in goes with"):
+        call(8, 8, mode=1, pin=None)
+    with pytest.raises(RuntimeError, match="percsim_mode 3"):
+        call(8, 8, mode=3, pin=p)
+    # the largest sizes are taken as far as the workspace check (an aligned percsim_in with them)
+    need = _lib.call("ps_consistency_workspace_bytes", 1, 32767, 32767)
+    assert need == 2 * 512 * 8192 * 2 * 8
+    with pytest.raises(RuntimeError, match="workspace of %d bytes required" % need):
+        call(32767, 32767, mode=2, pin=p, ws_bytes=need - 1)
+
+
 def test_consistency_rows_argument_checks():
     import torch
     a, m = torch.zeros(2, 3, 16, 16, dtype=torch.uint8), torch.zeros(2, 1, 16, 16, dtype=torch.uint8)
