@@ -220,11 +220,23 @@ BLOCK_TRAIN_PROTOS = {
     "ps_pool_add_bwd_nhwc_f32": (RC, [c_void_p] + [c_int] * 4 + [c_void_p, STREAM]),
 }
 
+# libpixelsynth_content.so (include/pixelsynth_content.h): the passes between the convolutions of the VGG19 content loss
+CONTENT_PROTOS = {
+    "ps_content_last_error": (ctypes.c_char_p, []),
+    "ps_content_tiles": (c_size_t, [c_size_t]),
+    "ps_content_input": (RC, [c_void_p] * 4 + [c_int] * 3 + [c_void_p, STREAM]),
+    "ps_content_bias": (RC, [c_void_p, c_void_p, c_size_t, c_int, STREAM]),
+    "ps_content_tap": (RC, [c_void_p] + [c_int] * 4 + [c_void_p, STREAM]),
+    "ps_content_finish": (RC, [c_void_p] * 5 + [STREAM]),
+    "ps_content_pool": (RC, [c_void_p] + [c_int] * 4 + [c_void_p, STREAM]),
+    "ps_content_join": (RC, [c_void_p] * 5 + [c_float] + [c_int] * 5 + [c_void_p, STREAM]),
+}
+
 # short name of _libraries.LIBRARIES -> its prototype table; _OWNER: entry point -> the table entry of its library, built once
 PROTOS = {"hip": _PROTOS, "percsim": PERCSIM_PROTOS, "consistency": CONSISTENCY_PROTOS, "fid": FID_PROTOS, "scene": SCENE_PROTOS,
           "plan": PLAN_PROTOS, "rank": RANK_PROTOS, "rank_groups": RANK_GROUPS_PROTOS, "nll": NLL_PROTOS, "lmconv_bwd": LMCONV_BWD_PROTOS, "splat_bwd": SPLAT_BWD_PROTOS,
           "vq_train": VQ_TRAIN_PROTOS, "conv_bwd": CONV_BWD_PROTOS, "norm_train": NORM_TRAIN_PROTOS,
-          "block_train": BLOCK_TRAIN_PROTOS}
+          "block_train": BLOCK_TRAIN_PROTOS, "content": CONTENT_PROTOS}
 _ENTRIES = {e.name: e for e in _libraries.LIBRARIES}
 assert set(PROTOS) == set(_ENTRIES)
 _OWNER = {fn: _ENTRIES[name] for name, table in PROTOS.items() for fn in table}

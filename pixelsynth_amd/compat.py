@@ -91,3 +91,33 @@ def install_evaluation_aliases(force=False):
         setattr(sys.modules[".".join(parts[:-1])], parts[-1], mod)
         installed.append(ref)
     return installed
+
+
+TRAINING_ALIASES = {
+    "models.losses.synthesis": "pixelsynth_amd.losses.synthesis",
+}
+
+
+def _install(table, force):
+    """Register the mirrors of `table` under the reference's module names -> the names installed"""
+    installed = []
+    for ref, ours in table.items():
+        if ref in sys.modules and not force:
+            continue
+        parts = ref.split(".")
+        for i in range(1, len(parts)):
+            parent = _parent_package(".".join(parts[:i]))
+            if i > 1:
+                setattr(sys.modules[".".join(parts[:i - 1])], parts[i - 1], parent)
+        mod = importlib.import_module(ours)
+        sys.modules[ref] = mod
+        setattr(sys.modules[".".join(parts[:-1])], parts[-1], mod)
+        installed.append(ref)
+    return installed
+
+
+def install_training_aliases(force=False):
+    """Register the generator's image loss (SynthesisLoss and its terms, the VGG19 content term on the HIP kernels) under the
+    reference's module name, so a training script's `from models.losses.synthesis import SynthesisLoss` runs unchanged.  Separate
+    from the other two: a caller that only renders or scores does not import the loss."""
+    return _install(TRAINING_ALIASES, force)

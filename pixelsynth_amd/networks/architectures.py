@@ -43,6 +43,7 @@ from .conv_routes import (_conv2d_batches, _conv_mode, _conv_split, _f16x3_conv,
                           _normalised_weight, _overflow_flag, _plain_conv_weight, _resample, _resample_sum, _sn_hooks, _sn_linear,
                           _thin_conv, conv1x1, plain_conv)
 from .routing import empty_nhwc, gpu_f32, per_sample
+from .vgg19 import VGG19  # noqa: F401  (the content loss's network, where the reference keeps it)
 
 NOISE_SZ = 20
 # "f16x3" | "fp32" (everything through torch / MIOpen): the process default of decoder_conv, read at every call (bench.py assigns it)
