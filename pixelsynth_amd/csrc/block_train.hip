@@ -259,7 +259,7 @@ __global__ __launch_bounds__(256) void k_pool_add_bwd(const f32x4 *__restrict__ 
 
 unsigned grid_for(size_t total4) { return (unsigned)std::min<size_t>((total4 + 255) / 256, 256 * 32); }
 
-inline bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
+using ps::aligned16;
 
 template <int TO, int TC> int launch_grad_weight(const GwArgs &a, const GwPlan &p, hipStream_t st)
 {

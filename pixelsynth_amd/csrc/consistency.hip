@@ -171,7 +171,7 @@ int ps_consistency(const void *view1, const int64_t *strides1, const void *view2
                percsim_mode);
     PS_REQUIRE((percsim_mode == PS_CONSISTENCY_NO_PERCSIM) == (percsim_in == nullptr),
                "consistency: percsim_in goes with PS_CONSISTENCY_PERCSIM / _PERCSIM_RAW");
-    PS_REQUIRE(((uintptr_t)percsim_in & 15) == 0, "consistency: percsim_in must be 16-byte aligned");
+    PS_REQUIRE(ps::aligned16(percsim_in), "consistency: percsim_in must be 16-byte aligned");
     const size_t need = ps_consistency_workspace_bytes(B, H, W);
     PS_REQUIRE(workspace && workspace_bytes >= need, "consistency: workspace of %zu bytes required (got %zu)", need, workspace_bytes);
     const Img a(view1, strides1), b(view2, strides2);

@@ -18,8 +18,10 @@
 
 namespace {
 
+using ps::aligned16;
 using ps::f32x4;
 using ps::Img;
+using ps::max4_keep_nan;
 
 constexpr int THREADS = PS_CONTENT_THREADS, TILE = PS_CONTENT_TILE, LEVELS = PS_CONTENT_LEVELS;
 
@@ -92,12 +94,6 @@ __global__ __launch_bounds__(THREADS) void k_finish(const double *__restrict__ s
         blk += tiles;
     }
     if (tid == 0) total[0] = (float)tot;
-}
-
-// F.max_pool2d's value of a window: NaN where it holds one (IEEE 754-2019 maximum, not maxNum)
-__device__ __forceinline__ f32x4 max4_keep_nan(f32x4 a, f32x4 b, f32x4 c, f32x4 d)
-{
-    return __builtin_elementwise_maximum(__builtin_elementwise_maximum(a, b), __builtin_elementwise_maximum(c, d));
 }
 
 // float4 index of pixel (y, x) of image f in a (., H, W, C4) map
@@ -208,7 +204,6 @@ template <bool SEED> __global__ __launch_bounds__(256) void k_join_pooled(Join a
 
 unsigned grid_for(size_t total4) { return (unsigned)std::min<size_t>((total4 + 255) / 256, 256 * 32); }
 
-inline bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 
 // what every map-shaped call asks of its sizes
 inline bool map_ok(long long N, int H, int W, int C)

@@ -191,8 +191,7 @@ int ps_conv1x1_ex_nhwc_f32(const float *x, int ldx, const float *w, const float 
     PS_REQUIRE(ps_conv1x1_takes(Ci, Co), "conv1x1: Ci in {4, 32, 64, 128, 256} and ceil16(Co) * Ci <= 32768 required (Ci = %d, Co = %d)", Ci, Co);
     PS_REQUIRE(ldx >= Ci && ldx % 4 == 0, "conv1x1: ldx >= Ci and a multiple of 4 required (ldx = %d)", ldx);
     PS_REQUIRE((flags & ~3) == 0, "conv1x1: unknown flags %d", flags);
-    PS_REQUIRE(((uintptr_t)x & 15) == 0 && ((uintptr_t)w & 15) == 0 && ((uintptr_t)y & 15) == 0 && ((uintptr_t)bias & 15) == 0 &&
-               ((uintptr_t)res & 15) == 0, "conv1x1: 16-byte aligned buffers required");
+    PS_REQUIRE(ps::aligned16(x) && ps::aligned16(w) && ps::aligned16(y) && ps::aligned16(bias) && ps::aligned16(res), "conv1x1: 16-byte aligned buffers required");
     C1Args a{x, w, y, npix, Ci, Co, (Co + 15) / 16, ldx, bias, res, flags & 1, (flags >> 1) & 1};
     hipStream_t st = (hipStream_t)stream;
     switch (Ci) {

@@ -291,7 +291,7 @@ int ps_fid_input(const void *img, const int64_t *strides, int dtype, int B, int 
 {
     PS_REQUIRE_IMAGES("fid_input", img && strides && out, dtype, B, strides, nullptr);
     PS_REQUIRE(H >= 1 && W >= 1 && (size_t)H * W < ((size_t)1 << 31), "fid_input: H = %d, W = %d", H, W);
-    PS_REQUIRE(((uintptr_t)out & 15) == 0, "fid_input: out must be 16-byte aligned");
+    PS_REQUIRE(ps::aligned16(out), "fid_input: out must be 16-byte aligned");
     const Img im(img, strides);
     const float sh = (float)H / (float)FID_SIZE, sw = (float)W / (float)FID_SIZE;
     const dim3 grid((FID_SIZE * FID_SIZE + 255) / 256, B);
@@ -329,7 +329,7 @@ int ps_fid_conv(const float *x, int ldx, const float *wp, size_t wp_floats, cons
     PS_REQUIRE(ldx >= Ci && ldx % 4 == 0, "fid_conv: ldx >= Ci and a multiple of 4 required (ldx = %d)", ldx);
     PS_REQUIRE(coff >= 0 && coff % 4 == 0 && ldy % 4 == 0 && ldy >= coff + Co,
                "fid_conv: coff and ldy multiples of 4, coff + Co <= ldy required (coff = %d, Co = %d, ldy = %d)", coff, Co, ldy);
-    PS_REQUIRE((((uintptr_t)x | (uintptr_t)wp | (uintptr_t)y | (uintptr_t)bias) & 15) == 0, "fid_conv: 16-byte aligned buffers required");
+    PS_REQUIRE(ps::aligned16(x) && ps::aligned16(wp) && ps::aligned16(y) && ps::aligned16(bias), "fid_conv: 16-byte aligned buffers required");
     const size_t need = ps_fid_conv_packed_floats(KH, KW, Ci, Co);
     PS_REQUIRE(wp_floats == need, "fid_conv: packed weights of %zu floats required (got %zu)", need, wp_floats);
     const int Ho = (H + 2 * ph - KH) / stride + 1, Wo = (W + 2 * pw - KW) / stride + 1;
@@ -348,7 +348,7 @@ int ps_fid_pool(const float *x, int ldx, int mode, int N, int H, int W, int C, f
     PS_REQUIRE(ldx >= C && ldx % 4 == 0, "fid_pool: ldx >= C and a multiple of 4 required (ldx = %d)", ldx);
     PS_REQUIRE(coff >= 0 && coff % 4 == 0 && ldy % 4 == 0 && ldy >= coff + C,
                "fid_pool: coff and ldy multiples of 4, coff + C <= ldy required (coff = %d, C = %d, ldy = %d)", coff, C, ldy);
-    PS_REQUIRE((((uintptr_t)x | (uintptr_t)y) & 15) == 0, "fid_pool: 16-byte aligned buffers required");
+    PS_REQUIRE(ps::aligned16(x) && ps::aligned16(y), "fid_pool: 16-byte aligned buffers required");
     const int Ho = mode == PS_FID_MEAN ? 1 : mode == PS_FID_MAX_S2 ? (H - 3) / 2 + 1 : H;
     const int Wo = mode == PS_FID_MEAN ? 1 : mode == PS_FID_MAX_S2 ? (W - 3) / 2 + 1 : W;
     const size_t total = (size_t)N * Ho * Wo * (C / 4);

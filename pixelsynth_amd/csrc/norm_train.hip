@@ -338,7 +338,7 @@ __global__ __launch_bounds__(THREADS) void k_bwd_dx(const f32x4 *__restrict__ x,
     });
 }
 
-inline bool aligned16(const void *p) { return (uintptr_t)p % 16 == 0; }
+using ps::aligned16;
 
 }  // namespace
 

@@ -13,7 +13,7 @@
 //                     tile's 64 terms are added in a fixed order (fp64) and written to the workspace.  With `pooled`, the same read
 //                     writes the 2 x 2 stride-2 max-pool of the PRE-ReLU map of both images: the next slice's input (its first
 //                     convolution applies the ReLU, relu(max(y)) = max(relu(y))).  No atomics.  A NaN in y stays one, as in torch.relu
-//                     and F.max_pool2d (ps::relu_keep_nan, max4_keep_nan): in the pair's sums and in the pooled window that holds it.
+//                     and F.max_pool2d (ps::relu_keep_nan, ps::max4_keep_nan): in the pair's sums and in the pooled window that holds it.
 //   k_percsim_finish  one workgroup per pair: per layer the tile sums (fp64, a fixed strided order and a fixed tree), 1 - mean, and
 //                     the sum of the five.  A pair's numbers depend neither on its place in the batch nor on the batch's size.
 //
@@ -35,6 +35,7 @@ using ps::c_pnet_scale;
 using ps::c_pnet_shift;
 using ps::f32x4;
 using ps::Img;
+using ps::max4_keep_nan;
 using ps::to_unit;
 
 template <typename T>
@@ -65,14 +66,6 @@ __global__ __launch_bounds__(256) void k_percsim_input(Img a, Img b, const float
     };
     one(a, out0);
     one(b, out1);
-}
-
-// The maximum of a 2 x 2 window as F.max_pool2d gives it: NaN where the window holds one.  __builtin_elementwise_max is IEEE maxNum
-// (v_max_f32), which returns its other operand for a NaN; __builtin_elementwise_maximum is IEEE 754-2019's maximum (v_maximum3_f32 on
-// gfx950: two instructions a channel, as many as the maxNum took), which hands the NaN on and gives maxNum's bits for anything else.
-__device__ __forceinline__ f32x4 max4_keep_nan(f32x4 a, f32x4 b, f32x4 c, f32x4 d)
-{
-    return __builtin_elementwise_maximum(__builtin_elementwise_maximum(a, b), __builtin_elementwise_maximum(c, d));
 }
 
 template <bool POOL>
@@ -193,7 +186,7 @@ int ps_percsim_input(const void *img1, const int64_t *strides1, const void *img2
     PS_REQUIRE(mode != MODE_RAW || (dtype == PS_DTYPE_F32 && !mask), "percsim_input: PS_PERCSIM_RAW takes fp32 images and no mask");
     PS_REQUIRE((mode == MODE_VIS || mode == MODE_INVIS) == (mask != nullptr), "percsim_input: a mask goes with PS_PERCSIM_VIS / _INVIS");
     PS_REQUIRE(H >= 1 && W >= 1 && (size_t)H * W < ((size_t)1 << 31), "percsim_input: H = %d, W = %d", H, W);
-    PS_REQUIRE((((uintptr_t)out0 | (uintptr_t)out1) & 15) == 0, "percsim_input: out0 / out1 must be 16-byte aligned");
+    PS_REQUIRE(ps::aligned16(out0) && ps::aligned16(out1), "percsim_input: out0 / out1 must be 16-byte aligned");
     const Img a(img1, strides1), b(img2, strides2);
     const dim3 grid((unsigned)(((size_t)H * W + 255) / 256), B);
     ps::for_dtype(dtype, [&](auto t) {
@@ -212,7 +205,7 @@ int ps_percsim_tap(const float *y, int P, int H, int W, int layer, int C, float 
     PS_REQUIRE(H > 0 && W > 0 && H % 128 == 0 && W % 128 == 0, "percsim_tap: H and W multiples of 128 required (H = %d, W = %d)", H, W);
     PS_REQUIRE(layer >= 0 && layer < P_LAYERS, "percsim_tap: layer %d", layer);
     PS_REQUIRE(C > 0 && C % 64 == 0, "percsim_tap: C a multiple of 64 required (C = %d)", C);
-    PS_REQUIRE(((uintptr_t)y & 15) == 0 && ((uintptr_t)pooled & 15) == 0, "percsim_tap: y / pooled must be 16-byte aligned");
+    PS_REQUIRE(ps::aligned16(y) && ps::aligned16(pooled), "percsim_tap: y / pooled must be 16-byte aligned");
     const size_t need = ps_percsim_workspace_bytes(P, H, W);
     PS_REQUIRE(workspace_bytes >= need, "percsim_tap: workspace of %zu bytes required (got %zu)", need, workspace_bytes);
     const int Hl = H >> layer, Wl = W >> layer, tiles = tiles_of(H, W, layer);

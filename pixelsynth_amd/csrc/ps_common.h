@@ -45,6 +45,9 @@ inline int fail(int code, const char *fmt, ...)
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// What "16-byte aligned" means at an entry point (host code): the kernels move 16 bytes per lane and access.  A null pointer passes.
+inline bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
+
 // The ReLU of the kernels that stand in for torch.relu / clamp_min: a NaN stays a NaN.  max(v, 0) is IEEE maxNum (v_max_f32), which
 // answers 0 for a NaN -- a clean-looking result from a broken input, and nothing left for the split-fp16 overflow guard to see.
 // float or an ext_vector of floats; -inf and any negative value give 0, +inf stays.

@@ -1,6 +1,7 @@
-// What the units that read a strided image batch share (metrics.hip, percsim.hip, consistency.hip, fid.hip): the batch as a kernel
-// argument, TF.to_tensor's value of an element, PNet's input constants, the argument requirements and the dtype dispatch of their
-// entry points, and the fixed-order block sum of their fp64 partial sums.  gfx950 only.
+// What the units that read a strided image batch share (metrics.hip, percsim.hip, consistency.hip, fid.hip, content_loss.hip): the
+// batch as a kernel argument, TF.to_tensor's value of an element, the 2 x 2 max-pool's window (percsim.hip, content_loss.hip), PNet's
+// input constants, the argument requirements and the dtype dispatch of their entry points, and the fixed-order block sum of their fp64
+// partial sums.  gfx950 only.
 #pragma once
 #include "ps_common.h"
 
@@ -19,6 +20,14 @@ template <typename T> __device__ __forceinline__ float to_unit(T v);
 template <> __device__ __forceinline__ float to_unit<float>(float v) { return v; }
 // true division, as TF.to_tensor's float().div(255) on the host (not a multiply by the reciprocal)
 template <> __device__ __forceinline__ float to_unit<uint8_t>(uint8_t v) { return (float)v / 255.0f; }
+
+// The maximum of a 2 x 2 window as F.max_pool2d gives it: NaN where the window holds one.  __builtin_elementwise_max is IEEE maxNum
+// (v_max_f32), which returns its other operand for a NaN; __builtin_elementwise_maximum is IEEE 754-2019's maximum (v_maximum3_f32 on
+// gfx950: two instructions a channel, as many as the maxNum took), which hands the NaN on and gives maxNum's bits for anything else.
+__device__ __forceinline__ f32x4 max4_keep_nan(f32x4 a, f32x4 b, f32x4 c, f32x4 d)
+{
+    return __builtin_elementwise_maximum(__builtin_elementwise_maximum(a, b), __builtin_elementwise_maximum(c, d));
+}
 
 // PNet's shift / scale (pretrained_networks.py:45-46) as the fp32 values torch.Tensor([...]) holds.  static: a copy per unit that
 // includes this header, as __constant__ data needs (no unit shares device symbols with another)

@@ -175,7 +175,7 @@ int ps_vq_stem_s2d_f32(const float *x, const float *w, const float *bias, int B,
 {
     PS_REQUIRE(x && w && bias && y, "vq_stem: null pointer");
     PS_REQUIRE(B > 0 && H > 0 && W > 0 && H % 4 == 0 && W % 16 == 0, "vq_stem: H a multiple of 4 and W of 16 required (H = %d, W = %d)", H, W);
-    PS_REQUIRE(((uintptr_t)y & 15) == 0 && ((uintptr_t)bias & 15) == 0, "vq_stem: 16-byte aligned y / bias required");
+    PS_REQUIRE(ps::aligned16(y) && ps::aligned16(bias), "vq_stem: 16-byte aligned y / bias required");
     StemArgs a{x, w, bias, y, B, H, W};
     const size_t ntiles = (size_t)B * (H / 4) * (W / 16);
     hipLaunchKernelGGL(k_vq_stem, dim3(grid_waves(ntiles, 8)), dim3(VE_THREADS), 0, (hipStream_t)stream, a);
@@ -187,7 +187,7 @@ int ps_vq_head_f32(const float *h, const float *wt, const float *bias, int B, in
 {
     PS_REQUIRE(h && wt && bias && y, "vq_head: null pointer");
     PS_REQUIRE(B > 0 && Hh > 0 && Wh > 0 && Wh % 16 == 0, "vq_head: Wh a multiple of 16 required (Wh = %d)", Wh);
-    PS_REQUIRE(((uintptr_t)h & 15) == 0, "vq_head: 16-byte aligned h required");
+    PS_REQUIRE(ps::aligned16(h), "vq_head: 16-byte aligned h required");
     HeadArgs a{h, wt, bias, y, B, Hh, Wh};
     const size_t ntiles = (size_t)B * Hh * (Wh / 16);
     hipLaunchKernelGGL(k_vq_head, dim3(grid_waves(ntiles, 4)), dim3(VE_THREADS), 0, (hipStream_t)stream, a);

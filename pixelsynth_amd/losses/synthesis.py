@@ -18,7 +18,8 @@ ps_content_tap on the five tapped PRE-ReLU maps, ps_content_finish.  In grad mod
 19 M floats, about 76 MB, per 256 x 256 image -- and the target's five tapped ones (8.5 MB); the target's other maps are dropped as they
 are consumed.  Without grad nothing is saved.  Backward: ps_content_join seeds the gradient at conv5_1, then per convolution, last to
 second, ps_conv3x3_bwd_prepare_f32 (the power-of-two scale), ps_conv3x3_f16x3_ex_nhwc on the flipped, transposed pack (an overflow word
-of its own, never read: a gradient that is not finite is there to see in the result) and ps_content_join (unscale, route through the
+of its own, never read: a gradient that is not finite is there to see in the result) -- f16x3.bwd_prepare and f16x3.grad_input, the
+steps of f16x3.conv3x3_train's backward pass -- and ps_content_join (unscale, route through the
 pool, add the tap's seed, mask by the ReLU); ps_conv3x3_thin_out_nhwc_f32 on conv1_1's flipped weight gives the image's gradient.
 Nothing is read back and nothing synchronises.
 
@@ -42,9 +43,6 @@ from ..networks.routing import empty_nhwc
 from ..networks.vgg19 import POOL_BEFORE, TAPPED, VGG19
 
 WEIGHTS = (1.0 / 32, 1.0 / 16, 1.0 / 8, 1.0 / 4, 1.0)
-_WS = _lib.Workspace()
-_grad_flags = {}    # str(device) -> int32 (1,): what the forward kernel raises while it convolves a GRADIENT (never read)
-_relu_tables = {}   # str(device) -> (ones, zeros), the largest asked for so far: a plain ReLU as the convolutions' act, scale 1 and shift 0
 
 
 def torch_content_loss(vgg, pred, gt):
@@ -84,17 +82,12 @@ def _network(layers, pred, gt, keep):
     dev, N = pred.device, 2 * pred.size(0)
     x = torch.empty((N, H, W, 4), dtype=torch.float32, device=dev)
     _lib.call("ps_content_input", pred, _images.strides(pred), gt, _images.strides(gt), P, H, W, x)
-    if str(dev) not in _relu_tables or _relu_tables[str(dev)][0].numel() < N * 512:
-        _relu_tables[str(dev)] = (torch.ones(N * 512, dtype=torch.float32, device=dev), torch.zeros(N * 512, dtype=torch.float32, device=dev))
-    ones, zeros = _relu_tables[str(dev)]
-    relu = lambda C: (ones[:N * C].view(N, C), zeros[:N * C].view(N, C))     # act(x) = max(x * 1 - 0, 0)
     tiles = [_lib.call("ps_content_tiles", P * (H >> l) * (W >> l)) for l in range(5)]
     sums = torch.empty(sum(tiles), dtype=torch.float64, device=dev)
     counts, maps, gts, h = [], [], [], None
     for k in range(13):
         if k == 0:
-            h = empty_nhwc(N, 64, H, W, x)
-            _lib.call("ps_conv3x3_thin_in_f16x3_nhwc", x, None, None, layers["w0"], N, H, W, 64, h, f16x3.flag(dev))
+            h = f16x3.conv3x3_thin_in(x.permute(0, 3, 1, 2), layers["w0"])
             _lib.call("ps_content_bias", h, layers["b0"], N * H * W, 64)
         else:
             if k in POOL_BEFORE:
@@ -103,7 +96,7 @@ def _network(layers, pred, gt, keep):
                 _lib.call("ps_content_pool", h, N, Hl, Wl, C, pooled)
                 h = pooled
             p = layers["packed"][k - 1]
-            h = f16x3.conv3x3(h, p, *relu(p["Ci"]))
+            h = f16x3.conv3x3(h, p, *f16x3.plain_relu(N, p["Ci"], dev))
         tapped = k in TAPPED
         if tapped:
             C, Hl, Wl = h.shape[1:]
@@ -130,24 +123,16 @@ def _join(y, y_gt, up, scale2, g, weight, pooled):
 def _backward(layers, saved, g):
     """The gradient of total to pred (P, 3, H, W) for g = d loss / d total, a (1,) fp32 tensor on the device"""
     maps, gts = saved["maps"], saved["gt"]
-    dev = g.device
-    key = str(dev)
-    if key not in _grad_flags:
-        _grad_flags[key] = torch.zeros(1, dtype=torch.int32, device=dev)
     G = _join(maps[12], gts[4], None, None, g, WEIGHTS[4], False)
     for k in range(12, 0, -1):
-        P, Co, Hk, Wk = G.shape
         flipped = layers["flipped"][k - 1]
-        ws = _WS.query(dev, "ps_conv3x3_bwd_workspace_bytes", P, Hk, Wk, flipped["Co"], Co)
-        gs = torch.empty_like(G)
-        scale2 = torch.empty(2, dtype=torch.float32, device=dev)
-        _lib.call("ps_conv3x3_bwd_prepare_f32", G, P, Hk, Wk, Co, gs, scale2, None, ws, ws.numel())
-        up = f16x3.conv3x3(gs, flipped, overflow=_grad_flags[key])          # still multiplied by the scale: the join divides
+        gs, scale2, _, _ = f16x3.bwd_prepare(G, flipped["Co"])
+        up = f16x3.grad_input(gs, flipped)          # still multiplied by the scale: the join divides
         level = TAPPED.index(k - 1) if k - 1 in TAPPED else None
         G = _join(maps[k - 1], None if level is None else gts[level], up, scale2, g, 0.0 if level is None else WEIGHTS[level],
                   k in POOL_BEFORE)
     P, _, H, W = G.shape
-    gx = torch.empty((P, H, W, 3), dtype=torch.float32, device=dev)
+    gx = torch.empty((P, H, W, 3), dtype=torch.float32, device=g.device)
     _lib.call("ps_conv3x3_thin_out_nhwc_f32", G, None, None, layers["w0_flipped"], P, H, W, 64, 3, gx)
     return gx.permute(0, 3, 1, 2)
 
@@ -191,7 +176,7 @@ def content_loss(vgg, pred, gt, return_saved=False):
 
 class PerceptualLoss(nn.Module):
     """synthesis.py:85-104: the content term on a frozen VGG19.  The network's weights: `weights` (a path or a state dict) or
-    opt.vgg19_weights, else torchvision's cached file; `rand` or opt.vgg19_rand: torchvision's initialisation (networks/vgg19.py)."""
+    opt.vgg19_weights, else torchvision's cached file; `rand` or opt.vgg19_rand: torchvision's initialisation (networks/vgg19.py, networks/vgg.py)."""
 
     def __init__(self, opt=None, weights=None, rand=None):
         super().__init__()

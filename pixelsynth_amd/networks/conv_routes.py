@@ -1,5 +1,5 @@
 """Which kernel a convolution of the refinement decoder gets (the blocks' dataflow is architectures.py's): the weight a module's forward
-would use, taken apart only where that is safe (_plain_conv_weight) and cached per module (cached); the batch cut of what still goes
+would use, taken apart only where that is safe (_plain_conv_weight) and cached per module (routing.cached); the batch cut of what still goes
 through torch (_conv2d_batches); the no-grad routes -- conv1x1 (csrc/conv1x1.hip), _thin_conv (csrc/conv_thin.hip), _f16x3_conv
 (csrc/conv_f16x3.hip through f16x3.py) --; the two training routes behind one gate (_train_route); and the join of a block's branches
 (_resample_sum, csrc/nets.hip).  Every route returns None for what it does not take and the caller goes on to the next; _conv_split ends
@@ -11,8 +11,8 @@ from torch.nn.utils.spectral_norm import SpectralNorm
 
 from .. import _lib
 from . import block_train, f16x3
-from .f16x3 import flag as _overflow_flag
-from .routing import empty_nhwc, gpu_f32
+from .f16x3 import flag as _overflow_flag  # noqa: F401  (architectures.py hands it on)
+from .routing import cached, empty_nhwc, gpu_f32
 
 _conv_mode = f16x3.decoder_conv.resolve      # which convolutions a decoder block takes: "f16x3" | "fp32" (everything through torch / MIOpen)
 
@@ -22,17 +22,6 @@ def plain_conv(conv, k, pad):
     computes"""
     return (type(conv) is nn.Conv2d and conv.kernel_size == (k, k) and conv.stride == (1, 1) and conv.padding == (pad, pad)
             and conv.dilation == (1, 1) and conv.groups == 1)
-
-
-def cached(mod, slot, sources, make):
-    """make() -- a value derived from the tensors `sources` of `mod` -- computed once and kept in mod.__dict__[slot] as (key, value, sources)
-    until a source is replaced or written to (its address, version counter or device).  The sources are kept alive: their addresses are
-    the key."""
-    key = tuple((t.data_ptr(), t._version, t.device) for t in sources)
-    entry = mod.__dict__.get(slot)
-    if entry is None or entry[0] != key:
-        entry = mod.__dict__[slot] = (key, make(), sources)
-    return entry[1]
 
 
 def _sn_hooks(mod, kind):
@@ -195,11 +184,11 @@ def _thin_conv(conv, x, scale=None, shift=None):
     if weight is None:
         return None
     wl = cached(conv, "_ps_thin_cache", (weight,), lambda: weight.detach().permute(2, 3, 1, 0).contiguous())      # [ky][kx][ci][co]
+    if thin_in and Co == 64 and x.size(3) % 16 == 0:   # on the fp16 matrix pipe (split operands): 82 instead of 270 us per 16 views
+        return f16x3.conv3x3_thin_in(x, wl, scale, shift)
     B, _, H, W = x.shape
     y = empty_nhwc(B, Co, H, W, x)
-    if thin_in and Co == 64 and W % 16 == 0:   # on the fp16 matrix pipe (split operands): 82 instead of 270 us per 16 views
-        _lib.call("ps_conv3x3_thin_in_f16x3_nhwc", x, scale, shift, wl, B, H, W, Co, y, _overflow_flag(x.device))
-    elif thin_in:
+    if thin_in:
         _lib.call("ps_conv3x3_thin_in_nhwc_f32", x, scale, shift, wl, B, H, W, Co, y)
     else:
         _lib.call("ps_conv3x3_thin_out_nhwc_f32", x, scale, shift, wl, B, H, W, Ci, Co, y)

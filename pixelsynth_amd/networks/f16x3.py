@@ -9,6 +9,9 @@ Training (csrc/conv_bwd.hip, libpixelsynth_conv_bwd.so): conv3x3_train(x, weight
 torch.autograd.Function whose backward pass runs on the same matrix pipe -- grad_y scaled by a power of two on the device, grad_weight
 as a GEMM over the pixels, grad_input as the forward kernel on the flipped, transposed weight.  It is opt-in for the decoder's blocks:
 decoder_conv_train("f16x3"), opt.decoder_conv_train or PS_DECODER_CONV_TRAIN; the default "fp32" leaves every call where it is.
+
+What the runners of whole networks (perceptual.py, losses/synthesis.py) share lives here too: check_weight (what fp16 cannot hold),
+plain_relu (the act tables of a plain ReLU), conv3x3_thin_in (the 4 -> 64 stem) and the gradient step grad_flag / bwd_prepare / grad_input.
 """
 import warnings
 
@@ -77,6 +80,13 @@ def checked(device, fn, check=True):
         _open.discard(key)
 
 
+def check_weight(w):
+    """ValueError for a weight fp16 cannot hold: a magnitude of 6e4 or more, or not a number (synchronises to find out)"""
+    top = float(w.abs().max())
+    if not (top == top and top < 6.0e4):
+        raise ValueError("split-fp16 convolution: a weight fp16 cannot hold")
+
+
 def pack3x3(weight, bias=None, s2d=False, d2s=False, check=True):
     """A (Co, Ci, 3, 3) fp32 CUDA weight (and (Co) bias) packed for conv3x3, Co padded to a multiple of 64 (the first `live` channels are
     the layer's); s2d / d2s: for a space-to-depth input (Ci / 4 a multiple of 32) / a depth-to-space output (Co / 4 a multiple of 64).
@@ -90,9 +100,7 @@ def pack3x3(weight, bias=None, s2d=False, d2s=False, check=True):
         weight = torch.cat([weight, weight.new_zeros(Cop - Co, Ci, 3, 3)])
     wl = weight.permute(0, 2, 3, 1).contiguous()       # (Co, 3, 3, Ci): no copy for a channels_last weight
     if check:
-        top = float(wl.abs().max())
-        if not (top == top and top < 6.0e4):
-            raise ValueError("split-fp16 convolution: a weight fp16 cannot hold")
+        check_weight(wl)
     packed = torch.empty(_lib.call("ps_conv3x3_f16x3_packed_bytes", Cop, Ci), dtype=torch.uint8, device=weight.device)
     _lib.call("ps_conv3x3_f16x3_pack", wl, Cop, Ci, packed)
     if bias is not None:
@@ -116,9 +124,59 @@ def conv3x3(x, p, scale=None, shift=None, bias=None, res=None, overflow=None):
     return y
 
 
+_relu_tables = {}   # str(device) -> (ones, zeros), the largest asked for so far
+
+
+def plain_relu(N, C, device):
+    """-> (scale, shift), (N, C) views of ones and zeros kept per device and grown on demand: a plain ReLU as conv3x3's act,
+    max(x * 1 - 0, 0)"""
+    key = str(device)
+    if key not in _relu_tables or _relu_tables[key][0].numel() < N * C:
+        _relu_tables[key] = (torch.ones(N * C, dtype=torch.float32, device=device), torch.zeros(N * C, dtype=torch.float32, device=device))
+    ones, zeros = _relu_tables[key]
+    return ones[:N * C].view(N, C), zeros[:N * C].view(N, C)
+
+
+def conv3x3_thin_in(x, w, scale=None, shift=None):
+    """conv3x3(act(x)) WITHOUT a bias of the 4 -> 64 layer (ps_conv3x3_thin_in_f16x3_nhwc: csrc/conv_thin.hip on the fp16 matrix pipe,
+    raising flag(x.device) as conv3x3 does): x (B, 4, H, W) channels_last fp32, W a multiple of 16, w [ky][kx][ci of 4][co of 64] fp32,
+    act as conv3x3's -> y (B, 64, H, W) channels_last"""
+    B, _, H, W = x.shape
+    y = empty_nhwc(B, 64, H, W, x)
+    _lib.call("ps_conv3x3_thin_in_f16x3_nhwc", x, scale, shift, w, B, H, W, 64, y, flag(x.device))
+    return y
+
+
 # ---- training: the plain convolution with its backward pass (csrc/conv_bwd.hip) ------------------------------------------------------------
 _WS = _lib.Workspace()
-_grad_flags = {}    # str(device) -> int32 (1,): what the forward kernel raises while it convolves a GRADIENT (never read: see _Conv3x3Train)
+_grad_flags = {}    # str(device) -> int32 (1,), see grad_flag
+
+
+def grad_flag(device):
+    """The word the forward kernel raises on `device` while it convolves a GRADIENT (int32 (1,)); never read: see _Conv3x3Train"""
+    key = str(device)
+    if key not in _grad_flags:
+        _grad_flags[key] = torch.zeros(1, dtype=torch.int32, device=device)
+    return _grad_flags[key]
+
+
+def bwd_prepare(g, Ci, bias=False):
+    """The first step of a convolution's backward pass (ps_conv3x3_bwd_prepare_f32) on its output's gradient g (B, Co, H, W) channels_last
+    fp32, Ci the convolution's input channels -> (gs, g scaled by a power of two; scale2 (2,), the scale and its inverse on the device;
+    gb (Co), the bias's gradient, or None without `bias`; ws, the workspace the grad_weight kernel goes on with)"""
+    B, Co, H, W = g.shape
+    ws = _WS.query(g.device, "ps_conv3x3_bwd_workspace_bytes", B, H, W, Ci, Co)
+    gs = torch.empty_like(g)                                                              # (preserves channels_last)
+    scale2 = torch.empty(2, dtype=torch.float32, device=g.device)
+    gb = torch.empty(Co, dtype=torch.float32, device=g.device) if bias else None
+    _lib.call("ps_conv3x3_bwd_prepare_f32", g, B, H, W, Co, gs, scale2, gb, ws, ws.numel())
+    return gs, scale2, gb, ws
+
+
+def grad_input(gs, flipped):
+    """The gradient to a convolution's input, still multiplied by bwd_prepare's scale: the forward kernel on the scaled gradient gs and
+    `flipped`, the pack3x3 of W'[c, t, o] = W[o, 8 - t, c]; what it raises goes to grad_flag"""
+    return conv3x3(gs, flipped, overflow=grad_flag(gs.device))
 
 
 def train_takes(Ci, Co, H, W):
@@ -148,23 +206,15 @@ class _Conv3x3Train(torch.autograd.Function):
         B, Ci, H, W = x.shape
         Co, dev = weight.size(0), x.device
         need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.has_bias and ctx.needs_input_grad[2]
-        g = grad_nhwc(grad_y)
-        ws = _WS.query(dev, "ps_conv3x3_bwd_workspace_bytes", B, H, W, Ci, Co)
-        gs = torch.empty_like(g)                                                          # (preserves channels_last)
-        scale2 = torch.empty(2, dtype=torch.float32, device=dev)
-        gb = torch.empty(Co, dtype=torch.float32, device=dev) if need_b else None
-        _lib.call("ps_conv3x3_bwd_prepare_f32", g, B, H, W, Co, gs, scale2, gb, ws, ws.numel())
+        gs, scale2, gb, ws = bwd_prepare(grad_nhwc(grad_y), Ci, need_b)
         gx = gw = None
         if need_w:
             gw = torch.empty((Co, 3, 3, Ci), dtype=torch.float32, device=dev)
             _lib.call("ps_conv3x3_grad_weight_f16x3", x, gs, scale2, B, H, W, Ci, Co, gw, flag(dev), ws, ws.numel())
             gw = gw.permute(0, 3, 1, 2)                                                   # (Co, Ci, 3, 3): a view
         if need_x:
-            key = str(dev)
-            if key not in _grad_flags:
-                _grad_flags[key] = torch.zeros(1, dtype=torch.int32, device=dev)
             flipped = pack3x3(weight.detach().flip(2, 3).transpose(0, 1), check=False)    # (the forward's pack3x3 looked at these values)
-            gx = conv3x3(gs, flipped, overflow=_grad_flags[key])
+            gx = grad_input(gs, flipped)
             _lib.call("ps_conv3x3_bwd_unscale_f32", gx, gx.numel(), scale2)
         return gx, gw, gb
 

@@ -18,6 +18,8 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from .routing import cached
+
 SIZE, DIMS, BN_EPS = 299, 2048, 0.001
 
 
@@ -125,7 +127,6 @@ class FIDInception(nn.Module):
                 for br in branches:
                     box.add_module(br, BasicConv2d(*specs[f"{mod}.{br}"]))
                 self.add_module(mod, box)
-        self._hip_cache = None
         if weights is not None:
             self.load_weights(weights)
         for p in self.parameters():
@@ -157,7 +158,6 @@ class FIDInception(nn.Module):
         if extra:
             raise KeyError(f"FIDInception: unexpected key {extra[0]} in the state dict")
         self.load_state_dict({k: torch.as_tensor(v) for k, v in given.items()}, strict=False)
-        self._hip_cache = None
 
     # ---- the torch formula
     def torch_forward(self, x):
@@ -197,22 +197,21 @@ class FIDInception(nn.Module):
         return w.float(), b.float()
 
     def hip_layers(self, device):
-        """{name: the folded convolution packed by fid.pack_conv} on `device`, once per set of weights; None when a convolution is
-        outside what ps_fid_conv takes (torch then runs)."""
+        """{name: the folded convolution packed by fid.pack_conv} on `device`, once per set of weights and device (routing.cached); None
+        when a convolution is outside what ps_fid_conv takes (torch then runs)."""
         from .. import fid
         tensors = [t for n in conv_specs() for m in (self.conv(n),)
                    for t in (m.conv.weight, m.bn.weight, m.bn.bias, m.bn.running_mean, m.bn.running_var)]
-        key = (str(device),) + tuple((t.data_ptr(), t._version) for t in tensors)
-        if self._hip_cache is None or self._hip_cache[0] != key:
+
+        def pack():
             layers = {}
             for name, (ci, co, k, s, p) in conv_specs().items():
                 w, b = self.folded(name)
                 layers[name] = fid.pack_conv(w.to(device), b.to(device), s, p)
                 if layers[name] is None:
-                    layers = None
-                    break
-            self._hip_cache = (key, layers, tensors)     # (keeps the keyed tensors alive)
-        return self._hip_cache[1]
+                    return None
+            return layers
+        return cached(self, f"_hip_cache_{device}", tensors, pack)
 
 
 def conv_shapes():

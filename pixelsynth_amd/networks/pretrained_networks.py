@@ -15,12 +15,17 @@ csrc/percsim.hip; perceptual.py) when both inputs are CUDA fp32 (N, 3, H, W) wit
 the weights are on the inputs' device and fp16 can hold them, and networks.f16x3.decoder_conv("fp32") is not in effect; that pass is a
 guarded scope (f16x3.checked: an activation beyond fp16's range warns and reruns through torch).  Everything else runs the torch
 formula (torch_forward), on any device.
+
+The trunk -- the features builder, the slices, the key translation, the loading and the preparation of the convolutions -- is
+networks/vgg.py's, shared with the content loss's VGG19 (vgg19.py); here are VGG16's tables and PNet.
 """
-import os
 from collections import namedtuple
 
 import torch
 import torch.nn as nn
+
+from . import vgg
+from .routing import cached
 
 VGG16_FILE = "vgg16-397923af.pth"    # torchvision's name of its VGG16 checkpoint
 # torchvision's vgg16().features (configuration "D"): 3 x 3 convolutions (each followed by a ReLU) and "M" 2 x 2 max-pools, 31 modules
@@ -45,70 +50,27 @@ def cos_sim(in0, in1):
     return per_pixel.mean(1).mean(1)
 
 
-def vgg16_features():
-    """torchvision's vgg16().features as a list of modules, with torchvision's initialisation (Kaiming normal, fan_out, zero bias)."""
-    layers, c = [], 3
-    for v in _CFG:
-        if v == "M":
-            layers.append(nn.MaxPool2d(kernel_size=2, stride=2))
-            continue
-        conv = nn.Conv2d(c, v, kernel_size=3, padding=1)
-        nn.init.kaiming_normal_(conv.weight, mode="fan_out", nonlinearity="relu")
-        nn.init.zeros_(conv.bias)
-        layers += [conv, nn.ReLU(inplace=True)]
-        c = v
-    return layers
-
-
-class vgg16(nn.Module):
-    """VGG16's features up to relu5_3 as five nn.Sequential slices named by their torchvision indices (slice1.0, slice1.2, slice2.5,
-    ...).  forward -> a namedtuple of the five tapped maps.  `pretrained` is accepted for the reference's signature; PNet loads the
-    weights (module docstring)."""
+class vgg16(vgg.Slices):
+    """VGG16's features up to relu5_3 as five nn.Sequential slices named by their torchvision indices (vgg.Slices).  forward -> a
+    namedtuple of the five tapped maps.  `pretrained` is accepted for the reference's signature; PNet loads the weights (module
+    docstring)."""
 
     def __init__(self, requires_grad=False, pretrained=True):
-        super().__init__()
-        feats = vgg16_features()
-        self.N_slices = len(SLICES)
-        for s, (lo, hi) in enumerate(SLICES):
-            self.add_module(f"slice{s + 1}", nn.Sequential())
-            for i in range(lo, hi):
-                getattr(self, f"slice{s + 1}").add_module(str(i), feats[i])
-        for p in self.parameters():
-            p.requires_grad_(requires_grad)
-
-    def slices(self):
-        return [getattr(self, f"slice{s + 1}") for s in range(self.N_slices)]
+        super().__init__(_CFG, SLICES, requires_grad)
 
     def forward(self, X):
-        taps = []
-        for sl in self.slices():
-            X = sl(X)
-            taps.append(X)
-        return _Taps(*taps)
-
-    def convs(self):
-        """The 13 Conv2d modules in order."""
-        return [m for sl in self.slices() for m in sl if isinstance(m, nn.Conv2d)]
+        return _Taps(*super().forward(X))
 
 
 def default_weights_path():
     """Where torchvision caches its VGG16 checkpoint: torch.hub.get_dir()/checkpoints/vgg16-397923af.pth (TORCH_HOME decides)."""
-    return os.path.join(torch.hub.get_dir(), "checkpoints", VGG16_FILE)
+    return vgg.default_weights_path(VGG16_FILE)
 
 
 def vgg16_slices_state_dict(sd):
-    """A torchvision VGG16 state dict (features.*; classifier.* ignored) or a PNet / vgg16 one -> vgg16's keys (slice1.0.weight, ...)."""
-    if not any(k.startswith("features.") for k in sd):
-        return {k[4:] if k.startswith("net.") else k: v for k, v in sd.items()}
-    slice_of = {i: s + 1 for s, (lo, hi) in enumerate(SLICES) for i in range(lo, hi)}
-    out = {}
-    for k, v in sd.items():
-        if k.startswith("features."):
-            _, i, what = k.split(".")
-            if int(i) not in CONVS:
-                raise KeyError(f"unexpected key {k} in a VGG16 state dict")
-            out[f"slice{slice_of[int(i)]}.{i}.{what}"] = v
-    return out
+    """A torchvision VGG16 state dict (features.*; classifier.* ignored) or a PNet / vgg16 one -> vgg16's keys (slice1.0.weight, ...);
+    KeyError for every features.N that is no convolution of VGG16."""
+    return vgg.slices_state_dict(sd, "VGG16", CONVS, SLICES, own_prefix="net.")
 
 
 class PNet(nn.Module):
@@ -126,23 +88,16 @@ class PNet(nn.Module):
             raise ValueError(f"PNet: unknown pnet_type {pnet_type!r}")
         self.net = vgg16(requires_grad=False, pretrained=not pnet_rand)
         if weights is None and not pnet_rand:
-            weights = default_weights_path()
-            if not os.path.exists(weights):
-                raise FileNotFoundError(f"PNet: no VGG16 weights at {weights} (torchvision's cache under TORCH_HOME); pass weights= a "
-                                        f"{VGG16_FILE} file or a state dict (nothing is downloaded)")
+            weights = vgg.cached_weights("PNet", "VGG16", VGG16_FILE)
         if weights is not None:
             self.load_weights(weights)
         self.L = self.net.N_slices
-        self._hip_cache = None
         if use_gpu:
             self.cuda()
 
     def load_weights(self, weights):
         """weights: a path (torch.load on the CPU, tensors only) or a state dict, in torchvision's or PNet's format."""
-        if isinstance(weights, (str, os.PathLike)):
-            weights = torch.load(weights, map_location="cpu", weights_only=True)
-        self.net.load_state_dict(vgg16_slices_state_dict(weights))
-        self._hip_cache = None
+        self.net.load_state_dict(vgg16_slices_state_dict(vgg.load(weights)))
 
     def _apply(self, fn, *args, **kwargs):      # .cuda() / .to() / .float(): shift and scale follow the network
         out = super()._apply(fn, *args, **kwargs)
@@ -162,25 +117,11 @@ class PNet(nn.Module):
         return in0.shape == in1.shape and in0.device == in1.device == dev and self.hip_layers(dev) is not None
 
     def hip_layers(self, device):
-        """The 13 convolutions prepared for the kernels -- conv1_1 as a [ky][kx][ci of 4][co] fp32 weight and its bias, the others
-        packed by f16x3.pack3x3 with their bias --, once per set of weights; None when fp16 cannot hold a weight (torch then runs)."""
-        from . import f16x3
+        """The 13 convolutions prepared for the kernels (vgg.prepare_convs: w0, b0, packed), once per set of weights and device
+        (routing.cached); None when fp16 cannot hold a weight (torch then runs)."""
         convs = self.net.convs()
-        key = (str(device),) + tuple((c.weight.data_ptr(), c.weight._version, c.bias.data_ptr(), c.bias._version) for c in convs)
-        if self._hip_cache is None or self._hip_cache[0] != key:
-            with torch.no_grad():
-                w0 = convs[0].weight.detach().float()
-                w0 = torch.cat([w0, w0.new_zeros(w0.size(0), 1, 3, 3)], 1).permute(2, 3, 1, 0).contiguous()
-                top = float(w0.abs().max())
-                try:
-                    if not top < 6.0e4:
-                        raise ValueError("split-fp16 convolution: a weight fp16 cannot hold")
-                    packed = [f16x3.pack3x3(c.weight.detach().float(), c.bias.detach().float()) for c in convs[1:]]
-                    layers = dict(w0=w0, b0=convs[0].bias.detach().float().contiguous(), packed=packed)
-                except ValueError:
-                    layers = None
-            self._hip_cache = (key, layers, [c.weight for c in convs] + [c.bias for c in convs])   # (keeps the keyed tensors alive)
-        return self._hip_cache[1]
+        return cached(self, f"_hip_cache_{device}", [t for c in convs for t in (c.weight, c.bias)],
+                      lambda: vgg.prepare_convs(convs, device))
 
     # ---- the torch formula
     def torch_forward(self, in0, in1, retPerLayer=False):

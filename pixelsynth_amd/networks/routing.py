@@ -1,6 +1,6 @@
 """What the refinement decoder's routes share, so that each is decided in one place: the switch that names a route (decoder_conv,
-decoder_conv_train, decoder_norm_train and decoder_block_train are instances), the test of what the kernels accept as a tensor, and the
-three tensor idioms every route repeats.  Imports nothing of the package: every module of networks/ may import it."""
+decoder_conv_train, decoder_norm_train and decoder_block_train are instances), the cache of what is prepared from a module's weights (cached), the test of
+what the kernels accept as a tensor, and the three tensor idioms every route repeats.  Imports nothing of the package: every module of networks/ may import it."""
 import os
 import sys
 
@@ -55,6 +55,18 @@ class Switch:
         if mode not in self.values:
             raise ValueError(f"{self.name} / {self.env} = {mode!r}: {self.expected}")
         return mode
+
+
+def cached(mod, slot, sources, make):
+    """make() -- a value derived from the tensors `sources` of `mod` -- computed once and kept in mod.__dict__[slot] as (key, value, sources)
+    until a source is replaced or written to (its address, version counter or device).  The sources are kept alive: their addresses are
+    the key.  Every prepared weight of the package is kept this way: the decoder's (conv_routes.py), the VGG trunks' and the FID
+    network's (hip_layers)."""
+    key = tuple((t.data_ptr(), t._version, t.device) for t in sources)
+    entry = mod.__dict__.get(slot)
+    if entry is None or entry[0] != key:
+        entry = mod.__dict__[slot] = (key, make(), sources)
+    return entry[1]
 
 
 def gpu_f32(t, layout=torch.channels_last, multiple=1, aligned=False, dims=4):

@@ -8,7 +8,7 @@ are NaN.  The three variants share one network pass.  Everything is checked befo
 fallback).  H and W multiples of 256 run on the HIP path, any other size through the torch formula on the device.
 
 A network pass: the input pass writes 2P standardised images (B, H, W, 4) (the P first are in0 of the pairs, the next P their in1);
-conv1_1 (ps_conv3x3_thin_in_f16x3_nhwc, no bias), conv1_2 (act shift = -bias of conv1_1, its own bias on the way out), then per tap
+conv1_1 (f16x3.conv3x3_thin_in, no bias), conv1_2 (act shift = -bias of conv1_1, its own bias on the way out), then per tap
 ps_percsim_tap on the layer's pre-ReLU output -- the cosine partial sums and, for the first four, the max-pooled input of the next slice,
 whose convolutions apply the ReLU on the way in -- and ps_percsim_finish.  Passes are cut so that one activation map stays near 1 GiB;
 a pass is a guarded scope (networks.f16x3.checked).
@@ -17,6 +17,7 @@ import torch
 
 from . import _images, _lib
 from .networks import f16x3
+from .networks.routing import empty_nhwc
 
 COLUMNS = ("percsim", "percsim_vis", "percsim_invis")
 PLAIN, VIS, INVIS, RAW = 0, 1, 2, 3                       # PS_PERCSIM_*
@@ -28,31 +29,23 @@ def pairs_per_pass(H, W):
     return max(1, min(65535, _MAP_BYTES // (2 * H * W * 64 * 4)))
 
 
-def _nhwc(N, C, H, W, dev):
-    return torch.empty((N, C, H, W), dtype=torch.float32, device=dev, memory_format=torch.channels_last)
-
-
 def network_pass(layers, x, P, H, W):
     """The pass over x (2P, 4, H, W) channels_last (the input pass's output, or consistency.py's) with pnet.hip_layers `layers`
     -> (layers (P, 5), total (P)) f32.  At most pairs_per_pass(H, W) pairs; inside the caller's guarded scope."""
     dev, N = x.device, 2 * P
-    ones = torch.ones(N * 512, dtype=torch.float32, device=dev)
-    zeros = torch.zeros(N * 512, dtype=torch.float32, device=dev)
-    relu = lambda C: (ones[:N * C].view(N, C), zeros[:N * C].view(N, C))     # act(x) = max(x * 1 - 0, 0)
     ws, nbytes = _images.workspace("ps_percsim_workspace_bytes", P, H, W, device=dev)
     h = None
     for level, convs in enumerate(_LEVELS):
         for i in convs:
             if i == 0:
-                h = _nhwc(N, 64, H, W, dev)
-                _lib.call("ps_conv3x3_thin_in_f16x3_nhwc", x, None, None, layers["w0"], N, H, W, 64, h, f16x3.flag(dev))
+                h = f16x3.conv3x3_thin_in(x, layers["w0"])
             elif i == 1:       # conv1_1's bias enters as the act's shift: max(y + b, 0)
-                h = f16x3.conv3x3(h, layers["packed"][0], ones[:N * 64].view(N, 64), (-layers["b0"]).expand(N, 64).contiguous())
+                h = f16x3.conv3x3(h, layers["packed"][0], f16x3.plain_relu(N, 64, dev)[0], (-layers["b0"]).expand(N, 64).contiguous())
             else:
                 p = layers["packed"][i - 1]
-                h = f16x3.conv3x3(h, p, *relu(p["Ci"]))
+                h = f16x3.conv3x3(h, p, *f16x3.plain_relu(N, p["Ci"], dev))
         C, Hl, Wl = h.shape[1:]
-        pooled = _nhwc(N, C, Hl // 2, Wl // 2, dev) if level < 4 else None
+        pooled = empty_nhwc(N, C, Hl // 2, Wl // 2, h) if level < 4 else None
         _lib.call("ps_percsim_tap", h, P, H, W, level, C, pooled, ws, nbytes)
         h = pooled
     per_layer = torch.empty(P, 5, dtype=torch.float32, device=dev)
