@@ -419,7 +419,7 @@ def wavefronts(order_host, H, W, first_step, device=None, max_cols=None, keep_ho
 
 
 def pack_launches(batches, cap, until_oldest_done=True, budget=None):
-    """Launch after launch out of the batches in flight (round 6; z_buffermodel.outpaint_pipelined): `batches`, OLDEST FIRST, are dicts
+    """Launch after launch out of the batches in flight (round 6; outpaint.OutpaintPipeline.outpaint_pipelined): `batches`, OLDEST FIRST, are dicts
     with 'ws' (a schedule's wave boundaries, numpy), 'w' (the wave the batch stands at) and 'off' (columns of that wave already
     launched) -- advanced in place.  A launch takes, from the oldest batch on, what is left of each batch's CURRENT wave while there is
     room under `cap` (the columns of a wave are independent: a wave may be dealt to several launches); a batch moves on to its next wave
@@ -456,7 +456,7 @@ def pack_launches(batches, cap, until_oldest_done=True, budget=None):
 
 
 class LaunchPipeline:
-    """The host side of z_buffermodel.outpaint_pipelined: the batches in flight, oldest first, as the records pack_launches advances
+    """The host side of outpaint.OutpaintPipeline.outpaint_pipelined: the batches in flight, oldest first, as the records pack_launches advances
     ('ws', 'w', 'off'; admit adds the caller's own fields), at most `depth` of them."""
 
     def __init__(self, depth):

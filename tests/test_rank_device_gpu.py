@@ -309,3 +309,61 @@ def test_get_best_sample_shard_downloads_its_scores_once(scorers, view, monkeypa
     disc, entr = spies.batched[0]
     assert handed[0] == (disc.double().cpu().tolist(), entr.double().cpu().tolist())
     assert torch.equal(best, spies.decoded[int(ranking.select(disc, entr))])
+
+
+# ---------------------------------------------------------------- the candidates: when they are decoded, how they are grouped
+def test_host_route_scores_a_candidate_before_the_next_is_decoded(scorers, view, monkeypatch):
+    """Two candidates per engine run: a candidate still goes through the discriminator and the classifier before the next one is
+    decoded -- one log fed by all three reads decode, disc, entr four times over"""
+    netD, _ = scorers
+    m, args, img, _ = view
+    monkeypatch.delenv("PS_RANK", raising=False)
+    monkeypatch.setattr(m, "sample_batch", 2)
+    log = []
+
+    def logged(name, inner):
+        def spy(*a, **kw):
+            log.append(name)
+            return inner(*a, **kw)
+        return spy
+    monkeypatch.setattr(m, "_decode_checked", logged("decode", m._decode_checked), raising=False)
+    monkeypatch.setattr(netD, "run_discriminator_one_step", logged("disc", netD.run_discriminator_one_step), raising=False)
+    monkeypatch.setattr(m, "_entropy_score", logged("entr", m._entropy_score), raising=False)
+    m.get_best_sample(*args, netD, img, rank_on="host")
+    assert log == ["decode", "disc", "entr"] * 4
+
+
+def test_grouping_of_the_engine_runs_does_not_matter(scorers, view, monkeypatch):
+    """sample_batch 1, 2 and 32 -- four engine runs of one frame, two of two, one of four -- with the same draws: the same decoded
+    candidates, bit for bit, and the same winner, on both routes.
+    The winner is compared from run to run, so it must not hang on the last bit of a score: the classifier of the fixture is a random
+    initialisation, its entropies of the four candidates lie within 1e-6 of one another, and the same candidate's entropy differs by
+    5e-7 between two calls of the same code (measured: the classifier's kernels do not sum in a fixed order) -- so on both routes the
+    entropy is replaced by a quantity that separates the candidates and has a fixed summation order, the fp64 sum of the image.  The
+    discriminator's scores stay -- they move by one ulp, 6e-8, between two calls at the most (measured), and lie 1e-6 apart and more: a
+    condition of this test, asserted -- and so does the rank rule of either route."""
+    netD, _ = scorers
+    m, args, img, _ = view
+    monkeypatch.delenv("PS_RANK", raising=False)
+    uniforms = torch.rand(4, 1, 1024, generator=torch.Generator(device="cpu").manual_seed(7)).to(DEV)
+    score_candidates = ranking.score_candidates
+    monkeypatch.setattr(m, "_entropy_score", lambda im: float(im.double().sum().cpu()), raising=False)
+    monkeypatch.setattr(ranking, "score_candidates", lambda stack, *a: (score_candidates(stack, *a)[0], stack.double().sum((1, 2, 3)).float()))
+    for route in ("host", "device"):
+        runs = []
+        for per_run in (1, 2, 32):
+            with monkeypatch.context() as mp:
+                mp.setattr(m, "sample_batch", per_run)
+                spies = Spies(mp, m, netD)
+                best = m.get_best_sample(*args, netD, img, uniforms=uniforms, rank_on=route)
+            assert len(spies.decoded) == 4 and len(spies.batched) == (route == "device")
+            assert spies.per_candidate == ([] if route == "device" else ["disc", "entr"] * 4)
+            if route == "device":
+                gap = float(spies.batched[0][0].sort().values.diff().min())
+                print(f"sample_batch {per_run}: smallest gap between two candidates' D_Fake {gap:.3g}")
+                assert gap >= 1e-6, "the candidates do not hold the discriminator's scores apart"
+            runs.append((spies.decoded, best))
+        for decoded, best in runs[1:]:
+            assert all(torch.equal(a, b) for a, b in zip(runs[0][0], decoded)), route
+            assert torch.equal(best, runs[0][1]), route
+        assert any(torch.equal(runs[0][1], c) for c in runs[0][0]), route             # (the winner is one of the four)
