@@ -14,7 +14,12 @@ A sum of n products accumulated by fused multiply-adds, in whatever order and sp
 accumulation: every term passes at most n roundings, (1 + u)^n - 1 <= 1.01 n u for n u < 0.01.  The 66 = PARTS + 2 pays for at most 64
 additions of partial sums and for the product of the mask value with the shifted input (one rounding, before the chain), with one to
 spare.  Where a bound is 0 -- every tap closed, or outside the grid -- the result must be exactly 0.
+
+The forward's own bound is stated at forward64().  plan() mirrors the kernel's split of the reduction; ROUTE_CASES are the shapes that take
+the steps, parts and location walks the operator shapes (OPERATOR_SHAPES) leave out.
 """
+from collections import namedtuple
+
 import torch
 
 from oracle import lmconv_oracle as lo
@@ -22,6 +27,71 @@ from oracle import lmconv_oracle as lo
 U = 2.0 ** -24
 MAX_PARTS = 64                     # = PS_LMCONV_BWD_MAX_PARTS (test_lmconv_bwd_cpu.py reads the header)
 SLACK = MAX_PARTS + 2
+
+
+TILE, BLOCK, KSTEP, DEPTH, TARGET_WAVES = 16, 32, 4, 4, 256 * 4 * 4      # csrc/lmconv_bwd.hip's
+LmPlan = namedtuple("LmPlan", "N ksteps chunk parts last bytes")
+
+
+def plan(B, Ci, Co, H, W):
+    """csrc/lmconv_bwd.hip's make_plan: locations, steps of KSTEP locations, steps per part, parts, the last part's steps, and the
+    workspace's size (which tests/test_train_routes2_cpu.py holds to the library's own: it fixes parts)"""
+    up = lambda v: -(-v // 256) * 256
+    N = B * H * W
+    Cop, Cip = -(-Co // TILE) * TILE, -(-Ci // TILE) * TILE
+    ksteps, tasks = -(-N // KSTEP), 9 * -(-Cop // BLOCK) * -(-Cip // BLOCK)
+    want = max(1, min(-(-TARGET_WAVES // tasks), MAX_PARTS, ksteps))
+    chunk = -(-ksteps // want)
+    parts = -(-ksteps // chunk)
+    return LmPlan(N, ksteps, chunk, parts, ksteps - (parts - 1) * chunk, up(up(up(N * Cop * 4) + N * Cip * 4) + parts * 9 * Cop * Cip * 4))
+
+
+RouteCase = namedtuple("RouteCase", "id shape why")          # shape (B, Ci, Co, H, W, dilation)
+ROUTE_CASES = [
+    RouteCase("chunk6_short_last", (2, 16, 16, 15, 43, 1), "chunk = 6: the second batch of a part holds two steps; 54 parts, the last of 5 steps; N % 4 = 2"),
+    RouteCase("chunk6_d2", (1, 16, 16, 37, 35, 2), "chunk = 6 at dilation 2; N % 4 = 3"),
+    RouteCase("chunk3", (4, 160, 80, 8, 8, 1), "chunk = 3: a batch with one step closed in every part; 22 parts, the last of 1 step"),
+    RouteCase("grid_1x1", (5, 3, 2, 1, 1, 1), "five locations: a lane's step of 4 crosses four images, both whiles loop"),
+    RouteCase("grid_2x1_d2", (3, 3, 2, 2, 1, 2), "W = 1, and every off-centre tap closed by the dilation"),
+    RouteCase("grid_3x3", (2, 5, 3, 3, 3, 1), "W = 3 < KSTEP: a step always changes the row"),
+    RouteCase("row_1x3", (7, 20, 40, 1, 3, 1), "H = 1: a step always changes the image; Co = 40: two tiles of 16 in one block, the second short"),
+    RouteCase("dilation_past_grid", (2, 7, 5, 6, 9, 7), "dilation 7 >= H = 6: every off-centre row closed, the columns open at the rims"),
+]
+# (B, Ci, Co, H, W, dilation) of the operator and network tests of tests/test_lmconv_bwd_gpu.py
+OPERATOR_SHAPES = [(3, 7, 5, 6, 9, 2), (2, 7, 5, 6, 9, 1), (2, 7, 5, 6, 9, 2), (2, 160, 80, 8, 8, 1), (2, 160, 160, 8, 8, 1), (2, 80, 80, 8, 8, 2),
+                   (2, 80, 80, 8, 8, 1), (1, 513, 80, 8, 8, 1), (2, 513, 80, 8, 8, 1), (5, 16, 16, 32, 32, 1)]
+
+
+def inputs(B, Ci, Co, H, W, seed):
+    """Per-image fractional masks with zeros throughout, as tests/test_lmconv_bwd_gpu.py's _inputs(..., frac=True) makes them (the same
+    draws in the same order).  On a grid of fewer than ten locations the centre tap of image 0 is opened: five 1 x 1 images have all
+    five centre taps closed once in a hundred seeds, and every gradient but the bias's is then an exact 0 that proves nothing."""
+    gen = torch.Generator().manual_seed(seed)
+    x = torch.randn(B, Ci, H, W, generator=gen)
+    w = torch.randn(Co, Ci, 3, 3, generator=gen) * 0.1
+    b = torch.randn(Co, generator=gen)
+    m = torch.rand(B, 9, H * W, generator=gen)
+    m = torch.where(m < 0.4, torch.zeros_like(m), m)
+    g = torch.randn(B, Co, H, W, generator=gen)
+    if H * W < 10:
+        m[0, 4] = 0.75
+    return x, m, w, b, g
+
+
+def forward64(x, m, w, bias, dilation):
+    """-> (y in fp64 by the oracle's unfold formula on the same fp32 inputs, its bound):
+
+        |d y[b,o,l]| <= 1.01 (9 Ci + 2) u (|bias[o]| + sum_{c,t} |W| |m| |xpad|)
+
+    y is a sum of 9 Ci + 1 terms, the bias among them.  Added in whatever order and split into however many chains (the forward kernel
+    keeps one set of accumulators per tap, adds the taps of a row, then the three rows and the bias), a term passes at most 9 Ci
+    additions that round -- one that adds an exact 0, a closed tap or a padded channel, does not -- and a fused multiply-add's product
+    does not round on its own; the product of the mask value with the shifted input rounds once before the chain: 9 Ci + 1, with one
+    to spare as in the gradients' bounds.  Where the bound is 0 -- every tap closed and no bias -- y must be exactly 0."""
+    x, m, w, bias = (None if t is None else t.detach().cpu().double() for t in (x, m, w, bias))
+    y = lo.lmconv(x, m, w, bias, dilation)
+    mag = lo.lmconv(x.abs(), m.abs(), w.abs(), None if bias is None else bias.abs(), dilation)
+    return y, 1.01 * (9 * x.shape[1] + 2) * U * mag
 
 
 def adjoint_mask(m, H, W, dilation):

@@ -17,6 +17,12 @@ The kernels sum in another order and take their roots and quotients differently 
 same unit roundoff, hence the margin of 4; a wrong or missing term is at least 1e-2 of max |g64|, orders above the bar.  E32 / max |g64|
 measured on the reference alone: 1e-7 .. 4e-6 for tau >= 1, about 1e-4 for grad_pts at tau = 0.5 (the derivative is unbounded at the
 rim of a disc), which is why the accuracy of grad_pts is not pinned at tau < 1.
+
+ROUTE_CASES are the cases with more feature channels than the operator test's (OPERATOR_CASE_IDS: 3, 5 or 8): 13 to 130, the model's own
+64 among them, where k_splat_bwd_pixels carries q_k over several chunks of 8 channels (pixel_chunks) and k_splat_bwd_points walks a point's
+box once per 64 channels (box_walks).  The kernel adds q_k = <g, f> over the C channels as one ascending chain, torch's fp32 sum does
+not; E32 / max |g64| of the reference alone stays at 1.5e-7 .. 2.3e-6 for them and the same bar holds with MARGIN 4 as it is (largest
+max |g_hip - g64| / E32 on the MI355X: 1.78, grad_pts at C = 130), so E32 is the one fp32 evaluation's as for every other case.
 """
 import numpy as np
 import torch
@@ -29,6 +35,41 @@ KINK = 1e-4            # a hit this close to a clamp bound (relative at 1e-3, ab
 EPS = 1e-2             # z_buffer_manipulator.py:8
 D_LO = float(np.float32(1e-3))
 T_MIN = float(np.float32(1e-4))
+
+
+# The cases of the operator test (tests/test_splat_bwd_gpu.py: test_gradients_against_fp64_autograd), by id in _splat_ref.CASES: 3, 5 or 8
+# feature channels, every one
+OPERATOR_CASE_IDS = ("division_S40", "division_S40_scale50", "wsum_tau1", "wsum_tau2", "wsumnorm_tau1", "wsumnorm_tau2", "tau2_S40",
+                     "channels_5", "channels_8", "partial_tiles_S20", "rad_pow1_C3", "rad_pow3_C5", "footprint_gt9", "sort_len_129",
+                     "tau0.5_S40")
+QCH = 8                # csrc/splat_bwd.hip's QCH: channels of grad_out k_splat_bwd_pixels keeps while it walks a list once
+LANES = 64             # channels k_splat_bwd_points owns in one walk of a point's box
+
+
+def pixel_chunks(C):
+    """Trips of k_splat_bwd_pixels' channel loop: q_k is carried from chunk to chunk through the plane"""
+    return -(-C // QCH)
+
+
+def box_walks(C):
+    """Walks of a point's box in k_splat_bwd_points when grad_feat is asked for: one per 64 channels, the points' gradient in the first"""
+    return -(-C // LANES)
+
+
+def _route(id, C, seed, acc="alphacomposite", tau=1.0, S=24, N=800, K=8, r=3):
+    return sr._small_case(id, S, N, K, r, ksize=3, C=C, acc=acc, tau=tau, seed=seed)
+
+
+# More channels than a chunk and than a wave (tests/test_train_routes2_cpu.py asserts what each reaches, tests/test_train_routes2_gpu.py
+# runs them).  A tuple of its own: the forward tests iterate over _splat_ref.CASES.  N = 300: most lists end in -1 before K.
+ROUTE_CASES = (
+    _route("bwd_C13_wsumnorm", 13, 401, acc="wsumnorm"),      # two chunks, the last of 5; wq sums a q made of both
+    _route("bwd_C16", 16, 402, N=300),                        # two full chunks
+    _route("bwd_C64", 64, 403),                               # eight chunks; every lane of the point kernel owns a channel
+    _route("bwd_C70_tau2", 70, 404, tau=2.0),                 # nine chunks, the last of 6; a second walk with 6 lanes live
+    _route("bwd_C130_wsum", 130, 405, acc="wsum", S=16, N=300, K=4, r=2.5),      # three walks, the last with 2 lanes live
+    _route("bwd_K1", 9, 406, K=1),                            # both walks of a list one step long
+)
 
 
 def splat_formula(pts, feat, idx, S, radius_px, rad_pow, tau, acc):

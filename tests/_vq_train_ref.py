@@ -37,7 +37,12 @@ embed       embed' = fl(embed_avg' / s): |d embed'| <= |d embed_avg'| / s + |emb
 grad_input  c = grad_diff 2 / (N D) is kept in fp64; z - e rounds once, the product once: the second term t = c (z - e) is off by at
             most 2 u |t| -- 3 u |t| allowed; the sum rounds once, u |grad_quantize + t| <= u (|grad_quantize| + |t|):
             |d grad_input| <= 1.01 u (|grad_quantize| + 4 |t|).  With grad_diff = 0: grad_quantize bit for bit.
+
+A code outside 0 .. K-1 (the header's contract: a row of zeros in the gathers, no code in the statistics) is expected by the same formulas
+on a codebook with a column of zeros appended and every such code sent to it: with_zero_row().
 """
+from collections import namedtuple
+
 import torch
 
 U = 2.0 ** -24
@@ -53,6 +58,34 @@ def part_rows(N):
     return PART_ROWS * -(-blocks // MAX_PARTS)
 
 
+TILE, CT, Q_ELEMS = 16, 2, 16384   # csrc/vq_train.hip's: channels / codes of an MFMA tile, code tiles a wave keeps, k_quantize's workgroup
+VqPlan = namedtuple("VqPlan", "dt kt wpp part_rows parts qwgs bytes")
+
+
+def plan(N, D, K):
+    """csrc/vq_train.hip's make_plan: channel tiles (the DT of k_stats_parts<DT>), code tiles, waves per part, the split of the rows,
+    k_quantize's workgroups, and the workspace's size (which tests/test_train_routes2_cpu.py holds to the library's own)"""
+    up = lambda v: -(-v // 256) * 256
+    Dp, Kp = -(-D // TILE) * TILE, -(-K // TILE) * TILE
+    rows = part_rows(N)
+    parts, qwgs = -(-N // rows), -(-N * D // Q_ELEMS)
+    qpart = up(up(parts * Dp * Kp * 4) + parts * Kp * 4)
+    return VqPlan(Dp // TILE, Kp // TILE, -(-Kp // TILE // CT), rows, parts, qwgs, up(up(qpart + qwgs * 8) + K * 4))
+
+
+RouteCase = namedtuple("RouteCase", "id shape why")          # shape (N, D, K)
+ROUTE_CASES = [
+    RouteCase("dt3_parts3", (1027, 33, 40), "DT = 3 with one live channel in its last tile, an odd number of code tiles, three parts; "
+                                            "k_quantize's second and third workgroup start off channel 0"),
+    RouteCase("dt3_one_code_tile", (700, 48, 16), "DT = 3 on full tiles; K <= 16: one wave per part, c_hi never true"),
+    RouteCase("dt2", (515, 20, 100), "DT = 2, seven code tiles on four waves, two parts"),
+    RouteCase("dt2_edge", (1027, 17, 33), "DT = 2 with one live channel in the second tile; k_quantize's second workgroup starts at channel 13"),
+    RouteCase("dt1_quantize_walk", (3300, 5, 37), "seven parts at DT = 1; the D = 5 walk of k_quantize across a workgroup boundary"),
+]
+# (N, D, K) of the operator tests of tests/test_vq_train_gpu.py
+OPERATOR_SHAPES = [(1003, 64, 512), (131, 5, 37), (1, 64, 512), (1, 5, 37), (1027, 64, 512), (65573, 64, 512)]
+
+
 def _f64(t):
     return t.detach().cpu().double()
 
@@ -60,6 +93,14 @@ def _f64(t):
 def gather(embed, idx):
     """embed (D,K), idx (N) -> e (N,D)"""
     return embed.t()[idx.long()]
+
+
+def with_zero_row(embed, idx):
+    """embed (D,K), idx (N) with codes of any value -> (embed with a column of zeros appended (D,K+1), idx with every code outside
+    0 .. K-1 sent to K): the formulas of this module on the pair are the header's contract for such codes"""
+    K = embed.shape[1]
+    idx = idx.detach().cpu().long()
+    return torch.cat([embed, torch.zeros_like(embed[:, :1])], 1), torch.where((idx < 0) | (idx >= K), torch.full_like(idx, K), idx)
 
 
 def quantize(z, embed, idx):

@@ -24,8 +24,7 @@ from pixelsynth_amd import _lib, synthetic as syn
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 CASE_BY_ID = {c.id: c for c in sr.CASES}
-CASE_IDS = ("division_S40", "division_S40_scale50", "wsum_tau1", "wsum_tau2", "wsumnorm_tau1", "wsumnorm_tau2", "tau2_S40", "channels_5",
-            "channels_8", "partial_tiles_S20", "rad_pow1_C3", "rad_pow3_C5", "footprint_gt9", "sort_len_129", "tau0.5_S40")
+CASE_IDS = ref.OPERATOR_CASE_IDS
 _REF = {}
 
 
@@ -68,9 +67,10 @@ def _at_the_bar(name, got, g64, g32, keep=None):
     assert scale > 0 and err <= bound, (name, err, bound)
 
 
-@pytest.mark.parametrize("case_id", CASE_IDS)
-def test_gradients_against_fp64_autograd(case_id):
-    c = CASE_BY_ID[case_id]
+def check_gradients(c):
+    """A case through the module against the fp64 autograd of the formula: the forward's bits against the debug route, exact zeros for
+    unseen points and for z, both gradients at the bar -> (grad_pts, grad_feat, the debug route's idx and dist) on the device.  Shared with
+    tests/test_train_routes2_gpu.py, whose cases are not in _splat_ref.CASES."""
     pts, feat, o, g, (_, gp64, gf64), (_, gp32, gf32) = _reference(c)
     out, bg, gp, gf, after = _hip(c, pts, feat, g)
     assert gp.shape == (c.B, c.N, 3) and gf.shape == (c.B, c.C, c.N) and gp.dtype == gf.dtype == torch.float32
@@ -83,18 +83,24 @@ def test_gradients_against_fp64_autograd(case_id):
     assert np.array_equal(dbg[2].cpu().numpy(), o["idx"])
     # points in no list: exact zeros; z: exact zeros
     seen = ref.hit_points(o["idx"], c.B, c.N)
-    assert seen.any() and ((~seen).any() or case_id == "sort_len_129")     # (the pile: every point is on the one pixel's list)
+    assert seen.any() and ((~seen).any() or c.id == "sort_len_129")     # (the pile: every point is on the one pixel's list)
     gpn, gfn = gp.cpu().numpy(), gf.cpu().numpy()
     assert not gpn[..., 2].any()
     assert not gpn[~seen].any() and not gfn.transpose(0, 2, 1)[~seen].any()
-    _at_the_bar(f"{case_id} grad_feat", gf, gf64, gf32)
+    _at_the_bar(f"{c.id} grad_feat", gf, gf64, gf32)
     if c.tau < 1.0:
         assert np.isfinite(gpn).all()      # (accuracy of grad_pts not pinned at tau < 1: see the module docstring)
-        return
+        return gp, gf, dbg[2], dbg[4]
     kink = ref.kink_points(c, o["idx"], o["dist"], c.B, c.N)
-    print(f"{case_id}: {kink.sum()} of {seen.sum()} points with a hit lie within {ref.KINK:g} of a clamp bound")
+    print(f"{c.id}: {kink.sum()} of {seen.sum()} points with a hit lie within {ref.KINK:g} of a clamp bound")
     assert kink.sum() <= 0.02 * seen.sum()
-    _at_the_bar(f"{case_id} grad_pts", gp[..., :2], gp64[..., :2], gp32[..., :2], keep=~kink)
+    _at_the_bar(f"{c.id} grad_pts", gp[..., :2], gp64[..., :2], gp32[..., :2], keep=~kink)
+    return gp, gf, dbg[2], dbg[4]
+
+
+@pytest.mark.parametrize("case_id", CASE_IDS)
+def test_gradients_against_fp64_autograd(case_id):
+    check_gradients(CASE_BY_ID[case_id])
 
 
 def test_two_runs_and_a_cloud_alone_give_the_same_bits():
