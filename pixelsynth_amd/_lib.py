@@ -232,11 +232,21 @@ CONTENT_PROTOS = {
     "ps_content_join": (RC, [c_void_p] * 5 + [c_float] + [c_int] * 5 + [c_void_p, STREAM]),
 }
 
+# libpixelsynth_thin_train.so (include/pixelsynth_thin_train.h): the backward passes of the decoder's thin first and last layers
+THIN_TRAIN_PROTOS = {
+    "ps_thin_train_last_error": (ctypes.c_char_p, []),
+    "ps_thin_train_parts": (c_int, [c_int] * 6),
+    "ps_thin_train_workspace_bytes": (c_size_t, [c_int] * 6),
+    "ps_thin_expand_f32": (RC, [c_void_p, c_void_p] + [c_int] * 6 + [c_void_p, STREAM]),
+    "ps_thin_grad_weight_f32": (RC, [c_void_p, c_void_p] + [c_int] * 7 + [c_void_p] * 3 + [c_size_t, STREAM]),
+    "ps_thin_add_bias_f32": (RC, [c_void_p, c_void_p, c_size_t, c_int, STREAM]),
+}
+
 # short name of _libraries.LIBRARIES -> its prototype table; _OWNER: entry point -> the table entry of its library, built once
 PROTOS = {"hip": _PROTOS, "percsim": PERCSIM_PROTOS, "consistency": CONSISTENCY_PROTOS, "fid": FID_PROTOS, "scene": SCENE_PROTOS,
           "plan": PLAN_PROTOS, "rank": RANK_PROTOS, "rank_groups": RANK_GROUPS_PROTOS, "nll": NLL_PROTOS, "lmconv_bwd": LMCONV_BWD_PROTOS, "splat_bwd": SPLAT_BWD_PROTOS,
           "vq_train": VQ_TRAIN_PROTOS, "conv_bwd": CONV_BWD_PROTOS, "norm_train": NORM_TRAIN_PROTOS,
-          "block_train": BLOCK_TRAIN_PROTOS, "content": CONTENT_PROTOS}
+          "block_train": BLOCK_TRAIN_PROTOS, "content": CONTENT_PROTOS, "thin_train": THIN_TRAIN_PROTOS}
 _ENTRIES = {e.name: e for e in _libraries.LIBRARIES}
 assert set(PROTOS) == set(_ENTRIES)
 _OWNER = {fn: _ENTRIES[name] for name, table in PROTOS.items() for fn in table}

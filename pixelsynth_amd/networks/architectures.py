@@ -23,10 +23,11 @@ update the stored ones (the running average, or standing sums with bn.accumulate
 csrc/norm_train.hip -- statistics, norm + ReLU and their backward pass -- for channels-last fp32 activations on the GPU, the torch formula
 elsewhere or under decoder_norm_train("torch").  In eval() every path is the stored-statistics form above, untouched.  Under
 decoder_block_train("hip") (block_train.py; the default is "torch") a block's wide 1 x 1 projection and its Up / Down join are
-differentiated by csrc/block_train.hip as well.
+differentiated by csrc/block_train.hip as well, and under decoder_thin_train("hip") (thin_train.py; the default is "torch") the thin
+first and last layers -- block 0's 4 -> 64 and block 7's 128 -> 3 convolutions, 3 x 3 and 1 x 1 -- by csrc/thin_train.hip.
 
 This file holds what a checkpoint sees and the blocks' dataflow.  Which kernel a convolution or a join gets is decided in conv_routes.py;
-the four route switches and the test of what the kernels accept as a tensor are routing.py's.
+the five route switches and the test of what the kernels accept as a tensor are routing.py's.
 """
 import torch
 import torch.nn as nn
@@ -36,6 +37,7 @@ from .. import _lib
 from . import conv_routes, norm_train
 from .block_train import decoder_block_train  # noqa: F401
 from .norm_train import decoder_norm_train  # noqa: F401
+from .thin_train import decoder_thin_train  # noqa: F401
 from .f16x3 import check_f16x3_overflow, decoder_conv, decoder_conv_train  # noqa: F401  (the names bench.py and the tests use)
 # The routes are looked up in THIS module's namespace when a block runs: the tests replace _f16x3_conv here with a spy, and bench.py and
 # tools/ reach them as arch.<name>.

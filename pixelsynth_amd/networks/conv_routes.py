@@ -1,7 +1,7 @@
 """Which kernel a convolution of the refinement decoder gets (the blocks' dataflow is architectures.py's): the weight a module's forward
 would use, taken apart only where that is safe (_plain_conv_weight) and cached per module (routing.cached); the batch cut of what still goes
 through torch (_conv2d_batches); the no-grad routes -- conv1x1 (csrc/conv1x1.hip), _thin_conv (csrc/conv_thin.hip), _f16x3_conv
-(csrc/conv_f16x3.hip through f16x3.py) --; the two training routes behind one gate (_train_route); and the join of a block's branches
+(csrc/conv_f16x3.hip through f16x3.py) --; the three training routes behind one gate (_train_route); and the join of a block's branches
 (_resample_sum, csrc/nets.hip).  Every route returns None for what it does not take and the caller goes on to the next; _conv_split ends
 at the module's own forward."""
 import torch
@@ -10,7 +10,7 @@ import torch.nn.functional as F
 from torch.nn.utils.spectral_norm import SpectralNorm
 
 from .. import _lib
-from . import block_train, f16x3
+from . import block_train, f16x3, thin_train
 from .f16x3 import flag as _overflow_flag  # noqa: F401  (architectures.py hands it on)
 from .routing import cached, empty_nhwc, gpu_f32
 
@@ -110,7 +110,8 @@ def _conv_split(conv, x, mode=None, opt=None):
     (CPU, autograd, channel counts the kernels do not take): (conv(x), None).  mode "f16x3": a 1 x 1 convolution through
     csrc/conv1x1.hip instead of torch (MIOpen).  In grad mode with the training opt-in of `opt` (f16x3.train_mode) a wide 3 x 3
     convolution goes through f16x3.conv3x3_train (_f16x3_train_conv), and with the block opt-in (block_train.mode) a wide 1 x 1
-    convolution through block_train.conv1x1_train (_block_train_conv1x1)."""
+    convolution through block_train.conv1x1_train (_block_train_conv1x1), and with the thin opt-in (thin_train.mode) the thin 3 x 3 and
+    1 x 1 convolutions at the decoder's ends through thin_train's Functions (_thin_train_conv)."""
     if mode == "f16x3":
         y = conv1x1(conv, x)
         if y is not None:
@@ -119,6 +120,9 @@ def _conv_split(conv, x, mode=None, opt=None):
     if y is not None:
         return y, None
     y = _block_train_conv1x1(conv, x, opt)
+    if y is not None:
+        return y, None
+    y = _thin_train_conv(conv, x, opt)
     if y is not None:
         return y, None
     if conv.bias is None or torch.is_grad_enabled() or not gpu_f32(x, multiple=4) or conv.out_channels % 4:
@@ -168,6 +172,21 @@ def _block_train_conv1x1(conv, x, opt=None):
                         lambda Ci, Co: (Ci % 64 == 0 and Co % 64 == 0 and max(Ci, Co) <= block_train.MAX_CHANNELS
                                         and block_train.conv1x1_takes(Ci, Co, x.size(0) * x.size(2) * x.size(3))),
                         block_train.conv1x1_train)
+
+
+def _thin_train_conv(conv, x, opt=None):
+    """conv(x) through thin_train.conv_thin_in_train (4 -> Co) or conv_thin_out_train (Ci -> at most 4 channels) -- csrc/conv_thin.hip or
+    conv1x1.hip forward, those and csrc/thin_train.hip backward -- or None (_train_route): the opt-in is decoder_thin_train("hip") /
+    opt.decoder_thin_train / PS_DECODER_THIN_TRAIN (the default is "torch"), the convolution 3 x 3 or 1 x 1, the sizes
+    thin_train.takes_in / takes_out (the decoder's block 0 and block 7)."""
+    k = getattr(conv, "kernel_size", (0,))[0]
+    if k not in (1, 3):
+        return None
+    thin_in = conv.in_channels == thin_train.THIN_IN
+    takes = thin_train.takes_in if thin_in else thin_train.takes_out
+    return _train_route(conv, x, opt, thin_train.decoder_thin_train, "hip", k, k // 2,
+                        lambda Ci, Co: takes(Ci, Co, k, x.size(2), x.size(3)),
+                        thin_train.conv_thin_in_train if thin_in else thin_train.conv_thin_out_train)
 
 
 # ---- the no-grad 3 x 3 routes ------------------------------------------------------------------------------------------------------------

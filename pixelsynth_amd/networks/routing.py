@@ -1,5 +1,5 @@
 """What the refinement decoder's routes share, so that each is decided in one place: the switch that names a route (decoder_conv,
-decoder_conv_train, decoder_norm_train and decoder_block_train are instances), the cache of what is prepared from a module's weights (cached), the test of
+decoder_conv_train, decoder_norm_train, decoder_block_train and decoder_thin_train are instances), the cache of what is prepared from a module's weights (cached), the test of
 what the kernels accept as a tensor, and the three tensor idioms every route repeats.  Imports nothing of the package: every module of networks/ may import it."""
 import os
 import sys
