@@ -242,11 +242,23 @@ THIN_TRAIN_PROTOS = {
     "ps_thin_add_bias_f32": (RC, [c_void_p, c_void_p, c_size_t, c_int, STREAM]),
 }
 
+# libpixelsynth_gan_train.so (include/pixelsynth_gan_train.h): instance norm + LeakyReLU and the feature-matching L1 of the discriminator's
+# training pass.  maps, half_elems, weights and grads are host tables (ctypes arrays)
+GAN_TRAIN_PROTOS = {
+    "ps_gan_train_last_error": (ctypes.c_char_p, []),
+    "ps_in_lrelu_forward_f32": (RC, [c_void_p, c_int, c_int, c_float, c_float] + [c_void_p] * 4 + [c_size_t, STREAM]),
+    "ps_in_lrelu_backward_f32": (RC, [c_void_p] * 4 + [c_int, c_int, c_float, c_void_p, c_void_p, c_size_t, STREAM]),
+    "ps_gan_feat_workspace_bytes": (c_size_t, [c_void_p, c_int]),
+    "ps_gan_feat_l1_f32": (RC, [c_void_p] * 3 + [c_int] + [c_void_p] * 3 + [c_size_t, STREAM]),
+    "ps_gan_feat_l1_backward_f32": (RC, [c_void_p] * 3 + [c_int, c_void_p, c_void_p, STREAM]),
+}
+
 # short name of _libraries.LIBRARIES -> its prototype table; _OWNER: entry point -> the table entry of its library, built once
 PROTOS = {"hip": _PROTOS, "percsim": PERCSIM_PROTOS, "consistency": CONSISTENCY_PROTOS, "fid": FID_PROTOS, "scene": SCENE_PROTOS,
           "plan": PLAN_PROTOS, "rank": RANK_PROTOS, "rank_groups": RANK_GROUPS_PROTOS, "nll": NLL_PROTOS, "lmconv_bwd": LMCONV_BWD_PROTOS, "splat_bwd": SPLAT_BWD_PROTOS,
           "vq_train": VQ_TRAIN_PROTOS, "conv_bwd": CONV_BWD_PROTOS, "norm_train": NORM_TRAIN_PROTOS,
-          "block_train": BLOCK_TRAIN_PROTOS, "content": CONTENT_PROTOS, "thin_train": THIN_TRAIN_PROTOS}
+          "block_train": BLOCK_TRAIN_PROTOS, "content": CONTENT_PROTOS, "thin_train": THIN_TRAIN_PROTOS,
+          "gan_train": GAN_TRAIN_PROTOS}
 _ENTRIES = {e.name: e for e in _libraries.LIBRARIES}
 assert set(PROTOS) == set(_ENTRIES)
 _OWNER = {fn: _ENTRIES[name] for name, table in PROTOS.items() for fn in table}

@@ -121,3 +121,16 @@ def install_training_aliases(force=False):
     reference's module name, so a training script's `from models.losses.synthesis import SynthesisLoss` runs unchanged.  Separate
     from the other two: a caller that only renders or scores does not import the loss."""
     return _install(TRAINING_ALIASES, force)
+
+
+GAN_ALIASES = {
+    "models.losses.gan_loss": "pixelsynth_amd.losses.gan_loss",
+    "models.networks.discriminators": "pixelsynth_amd.networks.discriminators",
+}
+
+
+def install_gan_aliases(force=False):
+    """Register the discriminator and its losses (DiscriminatorLoss with both one-step entry points, the instance norm and the feature
+    matching on the HIP kernels when training) under the reference's module names, so `from models.losses.gan_loss import
+    DiscriminatorLoss` in models/base_model.py runs unchanged.  A table of its own: a caller picks the adversarial half by itself."""
+    return _install(GAN_ALIASES, force)

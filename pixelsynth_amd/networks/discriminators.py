@@ -4,20 +4,27 @@ state_dict keys (spectral-norm triples `weight_orig` / `weight_u` / `weight_v` i
 
 Inference form: the spectral normalisation is a fixed scale at test time (sigma = u . W v from the stored vectors, no power
 iteration in eval mode) and is folded into the convolution weights once; instance normalisation (affine=False) and LeakyReLU
-stay torch ops on MIOpen's convolutions -- this net scores a handful of candidates per view, it is not on the hot path."""
+stay torch ops on MIOpen's convolutions -- this net scores a handful of candidates per view, it is not on the hot path.
+
+Training form, with opt.isTrain (what the reference's train options set; module.training alone does not select it): _SNConv in train()
+runs the hook's power iteration and keeps sigma in the graph, and under grad mode the InstanceNorm2d + LeakyReLU pairs of model1..3 go
+through gan_train.instance_norm_lrelu_train (csrc/gan_train.hip on the "hip" route).  The convolutions stay torch's."""
 import numpy as np
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
+
+from . import gan_train
 
 
 class _SNConv(nn.Module):
     """Conv2d under spectral normalisation, eval-mode arithmetic of torch.nn.utils.spectral_norm: W = weight_orig / sigma with
     sigma = u . (W_mat v); parameters named like the hook's (the conv itself has no bias: a normalisation follows)."""
 
-    def __init__(self, cin, cout, k, stride, pad):
+    def __init__(self, cin, cout, k, stride, pad, opt=None):
         super().__init__()
         self.stride, self.pad = stride, pad
+        self.opt = opt      # (isTrain is read at every call: the options are the caller's)
         self.weight_orig = nn.Parameter(torch.empty(cout, cin, k, k))
         self.register_buffer("weight_u", torch.empty(cout))
         self.register_buffer("weight_v", torch.empty(cin * k * k))
@@ -28,6 +35,14 @@ class _SNConv(nn.Module):
 
     def weight(self):
         wm = self.weight_orig.reshape(self.weight_orig.size(0), -1)
+        if self.training and getattr(self.opt, "isTrain", False):
+            # torch.nn.utils.spectral_norm in training: one power iteration on the stored vectors, in place and outside the graph;
+            # sigma on copies of them (a later forward's update must not touch what this one's backward reads), W in the graph
+            with torch.no_grad():
+                self.weight_v.copy_(F.normalize(torch.mv(wm.t(), self.weight_u), dim=0, eps=1e-12))
+                self.weight_u.copy_(F.normalize(torch.mv(wm, self.weight_v), dim=0, eps=1e-12))
+                u, v = self.weight_u.clone(), self.weight_v.clone()
+            return self.weight_orig / torch.dot(u, torch.mv(wm, v))
         sigma = torch.dot(self.weight_u, torch.mv(wm, self.weight_v))
         return self.weight_orig / sigma
 
@@ -52,15 +67,20 @@ class NLayerDiscriminator(nn.Module):
         for n in range(1, opt.n_layers_D):
             nf_prev, nf = nf, min(nf * 2, 512)
             stride = 1 if n == opt.n_layers_D - 1 else 2
-            block = nn.Sequential(nn.Sequential(_SNConv(nf_prev, nf, kw, stride, padw), nn.InstanceNorm2d(nf, affine=False)),
+            block = nn.Sequential(nn.Sequential(_SNConv(nf_prev, nf, kw, stride, padw, opt), nn.InstanceNorm2d(nf, affine=False)),
                                   nn.LeakyReLU(0.2, False))
             self.add_module("model" + str(n), block)
         self.add_module("model" + str(opt.n_layers_D), nn.Sequential(nn.Conv2d(nf, 1, kernel_size=kw, stride=1, padding=padw)))
 
     def forward(self, input):
         results = [input]
+        fused = getattr(self.opt, "isTrain", False) and torch.is_grad_enabled()
         for submodel in self.children():
-            results.append(submodel(results[-1]))
+            if fused and isinstance(submodel[0], nn.Sequential):        # model1..3: (SN-conv, InstanceNorm2d), LeakyReLU
+                (conv, norm), act = submodel[0], submodel[1]
+                results.append(gan_train.instance_norm_lrelu_train(conv(results[-1]), norm.eps, act.negative_slope, self.opt))
+            else:
+                results.append(submodel(results[-1]))
         return results[1:] if not self.opt.no_ganFeat_loss else results[-1]
 
 
