@@ -147,7 +147,9 @@ def score_codes(model_or_engine, codes, plan_or_masks, region=None, temperature=
 def ar_loss(model, codes, plan_or_masks, region=None, group="sampled", temperature=1.0):
     """The mean cross entropy in nats of `codes` over the locations of `group` ("all", "sampled", "observed") as a DIFFERENTIABLE 0-dim
     fp32 loss -- the quantity score_codes(...).mean_nll(group) reports from the fused engine, here from OurPixelCNN._forward_layers on
-    the one-hot codes: plain torch but for the masked convolutions, whose forward and backward are HIP kernels.  Arguments as
+    the one-hot codes: plain torch but for the masked convolutions, whose forward and backward are HIP kernels -- or, under
+    pixelcnn_train("hip") (lmconv/train_ops.py: the block, opt.pixelcnn_train of a model with options, PS_PIXELCNN_TRAIN; default "torch"), with
+    the normalisations, activations, gates and the loss's backward on HIP as well.  Arguments as
     score_codes; model: ZbufferModelPts (its outpaint2) or OurPixelCNN.  After optimizer.step() the model's engine rebuilds itself
     (it is keyed on the parameters' versions), so sampling and scoring use the tuned weights.  A group without a location: NaN."""
     if group not in GROUPS:
@@ -161,7 +163,13 @@ def ar_loss(model, codes, plan_or_masks, region=None, group="sampled", temperatu
     H, W, masks, region = _plan_args("ar_loss", codes, plan_or_masks, region)
     targets = codes.reshape(F_, H * W).long()
     x = torch.nn.functional.one_hot(targets.view(F_, H, W), CLASSES).permute(0, 3, 1, 2).float()
-    with torch.cuda.device(codes.device):
+    from .lmconv import train_ops
+    if train_ops.mode(getattr(model, "opt", None)) == "hip":
+        # the layers' passes between the convolutions and the loss's backward on csrc/pixelcnn_train.hip; the logits stay in the (F,H,W,512)
+        # storage nin_out leaves them in, and the value is sum nll / count of code_nll's fp64 sums: score_codes(...).mean_nll(group)'s formula
+        with train_ops.pixelcnn_train("hip"), torch.cuda.device(codes.device):
+            return train_ops.code_cross_entropy(net._forward_layers(x, True, *masks), targets, region, group, temperature)
+    with train_ops.pixelcnn_train("torch"), torch.cuda.device(codes.device):
         logits = net._forward_layers(x, True, *masks).reshape(F_, CLASSES, H * W)
         nll = torch.nn.functional.cross_entropy(logits / float(temperature), targets, reduction="none")
         if group == "all":

@@ -7,6 +7,7 @@ import torch
 import torch.nn as nn
 from torch.nn.utils import weight_norm as wn
 
+from . import train_ops
 from .utils import concat_elu
 
 
@@ -47,7 +48,18 @@ class gated_resnet(nn.Module):
         self.conv_out = conv_op(wide, wide)
         self.norm_out = norm()
 
+    def _fused(self):
+        """Whether the block is one the training kernels restate (train_ops): PONO norms, the concatenated ELU, dropout the identity"""
+        return (isinstance(self.norm_input, PONO) and isinstance(self.norm_out, PONO) and self.nonlinearity is concat_elu
+                and (self.dropout is identity or not self.training or self.dropout.p == 0))
+
     def forward(self, og_x, a=None, mask=None):
+        if train_ops.mode() == "hip" and self._fused():
+            # five calls: the two PONO + activation sites and the gate are one kernel each way (csrc/pixelcnn_train.hip)
+            celu = lambda t: train_ops.norm_act(t, norm=False, act="celu")
+            h = self.conv_input(celu(og_x), mask=mask)
+            h = train_ops.norm_act(h, skip=None if a is None else self.nin_skip(celu(a)), norm=True, act="celu")
+            return train_ops.gate(self.conv_out(h, mask=mask), og_x)
         act = self.nonlinearity
         h = self.norm_input(self.conv_input(act(og_x), mask=mask), mask=mask)
         if a is not None:

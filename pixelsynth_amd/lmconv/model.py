@@ -16,6 +16,7 @@ import torch.nn.functional as F
 from torch.nn.utils import weight_norm as wn
 
 from .. import _lib
+from . import train_ops
 from .layers import PONO, gated_resnet, identity, nin
 from .locally_masked_convolution import compact_mask, locally_masked_conv2d
 from .utils import concat_elu
@@ -272,7 +273,7 @@ class OurPixelCNN(nn.Module):
                  dropout_prob=0.5, conv_bias=True, conv_mask_weight=False, rematerialize=False, binarize=False):
         super(OurPixelCNN, self).__init__()
         assert resnet_nonlinearity == 'concat_elu'
-        self.resnet_nonlinearity = lambda x: concat_elu(x)
+        self.resnet_nonlinearity = concat_elu
         self.init_padding = None
         self.binarize = binarize
         mk = lambda cin, cout, dil=1: locally_masked_conv2d(cin, cout, kernel_size=kernel_size, dilation=dil,
@@ -362,7 +363,10 @@ class OurPixelCNN(nn.Module):
     def _forward_layers(self, x, sample, mask_init, mask_undilated, mask_dilated):
         """Layer-by-layer forward with the reference's dataflow (model.py:118-155); every lmconv is the HIP kernel.
         Up pass: u0 = norm(u_init([x, 1])), three groups of gated blocks separated by dilated convs, every u kept;
-        down pass: the same in reverse, each gated block consuming the latest unused u as its skip input."""
+        down pass: the same in reverse, each gated block consuming the latest unused u as its skip input.
+        Under pixelcnn_train("hip") (train_ops) the same dataflow with the passes between the convolutions on csrc/pixelcnn_train.hip."""
+        if train_ops.mode() == "hip":
+            return self._forward_layers_hip(x, mask_init, mask_undilated, mask_dilated)
         ones = x.new_ones(x.size(0), 1, x.size(2), x.size(3))
         stack = [self.norm_init(self.u_init(torch.cat((x, ones), 1), mask=mask_init), mask=mask_undilated)]
         for g in range(3):
@@ -378,6 +382,25 @@ class OurPixelCNN(nn.Module):
                 if self.norm_us:
                     u = self.norm_us[g](u, mask=mask_dilated)
         return self.nin_out(F.elu(u))
+
+    def _forward_layers_hip(self, x, mask_init, mask_undilated, mask_dilated):
+        """_forward_layers with every lone PONO and the last ELU through train_ops.norm_act (the gated blocks dispatch themselves); a
+        feature norm other than PONO keeps its own module.  The channel of ones is padded on: one pass, no concatenation."""
+        norm = lambda mod, t, mask: train_ops.norm_act(t, norm=True, act=None) if isinstance(mod, PONO) else mod(t, mask=mask)
+        stack = [norm(self.norm_init, self.u_init(F.pad(x, (0, 0, 0, 0, 0, 1), value=1.0), mask=mask_init), mask_undilated)]
+        for g in range(3):
+            stack.extend(self.up_layers[g](stack[-1], mask=mask_undilated))
+            if g < 2:
+                d = self.downsize_u_stream[g](stack[-1], mask=mask_dilated)
+                stack.append(norm(self.norm_ds[g], d, mask_dilated) if self.norm_ds else d)
+        u = stack.pop()
+        for g in range(3):
+            u = self.down_layers[g](u, stack, mask=mask_undilated)
+            if g < 2:
+                u = self.upsize_u_stream[g](u, mask=mask_dilated)
+                if self.norm_us:
+                    u = norm(self.norm_us[g], u, mask_dilated)
+        return self.nin_out(train_ops.norm_act(u, norm=False, act="elu"))
 
 
 import os
