@@ -6,9 +6,9 @@ _resample of each branch and their sum, under torch autograd on the same channel
     python tools/block_train_time.py [--frames 16] [--rounds 5] [--calls 5] [--shapes 0,1,2,3]
 
 Row (a), the 1 x 1 convolution: forward plus the gradients in x, weight and bias for one grad_output.  Row (b), the join: forward plus the
-gradient in both operands.  The two routes alternate call by call in one process, each call between two device events on a synchronised
-device; after WARM calls of each, a round is CALLS calls per route and gives one median per route; the range of the rounds' medians is
-reported.  The HIP route's kernels are the medians of their device times under torch's profiler in a run of their own.  The routes' gradients are
+gradient in both operands.  The two routes alternate call by call (_measure.alternate): after 3 warm-up calls of each, a round is CALLS
+calls per route and gives one median per route; the range of the rounds' medians is reported.  The HIP route's kernels are the medians of
+their device times under torch's profiler in a run of their own (_measure.device_events, kernel_medians).  The routes' gradients are
 compared with each other and, for the join, the first frame of each with torch autograd of the same resampling on the host.  One JSON
 line per shape and row."""
 import argparse
@@ -16,62 +16,17 @@ import json
 import os
 import sys
 
-import numpy as np
 import torch
 import torch.nn.functional as F
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from pixelsynth_amd import _lib  # noqa: E402
 from pixelsynth_amd.networks import architectures as A, block_train as BT  # noqa: E402
+from _measure import alternate, device_events, kernel_medians, span  # noqa: E402
 
-WARM = 3
 SHAPES = ((64, 128, "Down", 256), (128, 256, "Down", 128), (256, 128, "Up", 64), (128, 128, "Up", 128))      # (Ci, Co, join, H = W of the block's input)
+# (the _bwd names before their forward twins: the first name found in an event's is its kernel)
 KERNELS = ("k_grad_weight", "k_sum_parts", "k_conv1x1", "k_upsample_add_bwd", "k_pool_add_bwd", "k_upsample_add", "k_pool_add")
-
-
-def alternate(routes, rounds, calls):
-    """routes {name: callable}; -> {name: the medians of `rounds` rounds of `calls` event-timed calls, in ms}, the routes taking turns
-    call by call"""
-    def one(fn):
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        e1.synchronize()
-        return e0.elapsed_time(e1)
-    for _ in range(WARM):
-        for fn in routes.values():
-            one(fn)
-    medians = {name: [] for name in routes}
-    for _ in range(rounds):
-        times = {name: [] for name in routes}
-        for _ in range(calls):
-            for name, fn in routes.items():
-                times[name].append(one(fn))
-        for name in routes:
-            medians[name].append(float(np.median(times[name])))
-    return medians
-
-
-def kernel_medians(fn, calls):
-    """{kernel: median device time in ms} of the kernels of KERNELS that fn launches, under torch's profiler; {} where it records none"""
-    from torch.profiler import ProfilerActivity, profile
-    with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
-        for _ in range(calls):
-            fn()
-        torch.cuda.synchronize()
-    times = {}
-    for ev in prof.events():
-        for k in KERNELS:                       # (the _bwd names before their forward twins: the first name found in the event's is its kernel)
-            if k in ev.name and ev.device_time > 0:
-                times.setdefault(k, []).append(ev.device_time / 1e3)
-                break
-    return {k: round(float(np.median(v)), 4) for k, v in times.items()}
-
-
-def span(v):
-    return [round(min(v), 4), round(max(v), 4)]
 
 
 def main(argv):
@@ -101,7 +56,7 @@ def main(argv):
         med = alternate(conv, args.rounds, args.calls)
         ours, ref = conv["hip"](), conv["torch"]()
         diff = {k: float((p - q).abs().max() / q.abs().max()) for k, p, q in zip(("dx", "dw", "db"), ours, ref)}
-        kern = kernel_medians(conv["hip"], args.calls)
+        kern = kernel_medians(device_events(conv["hip"], args.calls), KERNELS)
         rec = dict(what="conv1x1_train", Ci=Ci, Co=Co, frames=B, H=H, W=W, rounds=args.rounds, calls=args.calls,
                    parts=_lib.call("ps_conv1x1_grad_weight_parts", B * H * W, Ci, Co), kernel_ms_median=kern, max_diff_over_max=diff,
                    **{f"{k}_ms_median_range": span(v) for k, v in med.items()})
@@ -124,7 +79,7 @@ def main(argv):
         host = torch.zeros(1, Co, H, W, requires_grad=True)
         (A._resample(kind, host) * g[:1].cpu().contiguous()).sum().backward()
         vs_host = {k: float((r[0][:1].cpu() - host.grad).abs().max() / host.grad.abs().max()) for k, r in (("hip", ours), ("torch", ref))}
-        kern = kernel_medians(join["hip"], args.calls)
+        kern = kernel_medians(device_events(join["hip"], args.calls), KERNELS)
         rec = dict(what="resample_sum_train", kind=kind, C=Co, frames=B, H=H, W=W, rounds=args.rounds, calls=args.calls, kernel_ms_median=kern,
                    max_diff_over_max=diff, max_diff_to_host_over_max=vs_host, **{f"{k}_ms_median_range": span(v) for k, v in med.items()})
         print("(b) join %s, %d channels, %d frames of %d x %d, forward + backward: HIP %.3f .. %.3f ms, torch autograd %.3f .. %.3f ms; "

@@ -4,7 +4,7 @@ the masked comparison and the sums), and check both give the same PSNR_vis.  Als
 
     python tools/consistency_time.py [--items 128] [--iters 50]
 
-Prints microseconds per batch (CUDA events, after warm-up) as one JSON line."""
+Prints microseconds per batch (_measure.looped_ms: one pair of device events around ITERS calls, after 5 warm-up calls) as one JSON line."""
 import argparse
 import json
 import os
@@ -20,6 +20,7 @@ import torch  # noqa: E402
 
 import consistency_ref64 as R  # noqa: E402
 from pixelsynth_amd import consistency as C  # noqa: E402
+from _measure import looped_ms  # noqa: E402
 
 S = R.S
 
@@ -61,24 +62,11 @@ def torch_formula(v1, v2, m1, m2, maps):
     return torch.stack(out, 1)
 
 
-def timed(fn, iters):
-    for _ in range(5):
-        fn()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(iters):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) * 1e3 / iters
-
-
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--items", type=int, default=128)
     ap.add_argument("--iters", type=int, default=50)
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     dev = torch.device("cuda:0")
     B = args.items
     case = ("time", 3, 8, (3.0, -2.0, 1.0), 0.5, "valid")
@@ -98,13 +86,13 @@ def main():
 
     def kernel():
         C._lib.call("ps_consistency", v1, strides(v1), v2, strides(v2), 1, m1, m2, 1, maps, B, S, S, 0, None, psnr, ws, nbytes)
-    t_kernel = timed(kernel, args.iters)
+    t_kernel = looped_ms(kernel, args.iters, 5) * 1e3
     pin = torch.empty((4 * B, S, S, 4), dtype=torch.float32, device=dev)
 
     def kernel_percsim():
         C._lib.call("ps_consistency", v1, strides(v1), v2, strides(v2), 1, m1, m2, 1, maps, B, S, S, 1, pin, psnr, ws, nbytes)
-    t_kernel_p = timed(kernel_percsim, args.iters)
-    t_torch = timed(lambda: torch_formula(v1, v2, m1, m2, maps), max(5, args.iters // 5))
+    t_kernel_p = looped_ms(kernel_percsim, args.iters, 5) * 1e3
+    t_torch = looped_ms(lambda: torch_formula(v1, v2, m1, m2, maps), max(5, args.iters // 5), 5) * 1e3
     kernel()
     diff = float((psnr - torch_formula(v1, v2, m1, m2, maps)).abs().max())
     print(json.dumps({"items": B, "size": S, "kernel_us": round(t_kernel, 1), "kernel_with_percsim_input_us": round(t_kernel_p, 1),

@@ -4,75 +4,38 @@ against the route a user has without it: torch autograd of the modules (MIOpen f
 
     python tools/content_loss_time.py [--pairs 16] [--size 256] [--rounds 5] [--calls 5]
 
-One call is forward + backward: the loss and its gradient in the prediction.  The two routes alternate call by call in one process, each
-call between two device events on a synchronised device; after WARM calls of each, a round is CALLS calls per route and gives one median
-per route; the range of the rounds' medians is reported.  The HIP route's kernels are the sums per call of their device times under
-torch's profiler in a run of their own.  The routes' totals and gradients are compared with each other.  One JSON line."""
+One call is forward + backward: the loss and its gradient in the prediction.  The two routes alternate call by call
+(_measure.alternate): after 3 warm-up calls of each, a round is CALLS calls per route and gives one median per route; the range of the
+rounds' medians is reported.  The HIP route's kernels are the sums per call of their device times under torch's profiler in a run of
+their own (_measure.device_events).  The routes' totals and gradients are compared with each other.  One JSON line."""
 import argparse
 import json
 import os
 import sys
 
-import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from pixelsynth_amd.losses import synthesis as S  # noqa: E402
 from pixelsynth_amd.networks.vgg19 import VGG19  # noqa: E402
+from _measure import alternate, device_events, span  # noqa: E402
 
-WARM = 3
 # (the first name found in an event's is its kernel: k_join_pooled before k_join, bwd_prepare's kernels under "bwd")
 KERNELS = ("k_input", "k_bias", "k_tap", "k_finish", "k_pool", "k_join_pooled", "k_join", "thin_in", "thin_out", "conv3x3", "f16x3", "prepare",
            "bwd", "scale")
 
 
-def alternate(routes, rounds, calls):
-    """routes {name: callable}; -> {name: the medians of `rounds` rounds of `calls` event-timed calls, in ms}, the routes taking turns
-    call by call"""
-    def one(fn):
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        e1.synchronize()
-        return e0.elapsed_time(e1)
-    for _ in range(WARM):
-        for fn in routes.values():
-            one(fn)
-    medians = {name: [] for name in routes}
-    for _ in range(rounds):
-        times = {name: [] for name in routes}
-        for _ in range(calls):
-            for name, fn in routes.items():
-                times[name].append(one(fn))
-        for name in routes:
-            medians[name].append(float(np.median(times[name])))
-    return medians
-
-
 def kernel_sums(fn, calls):
     """({kernel name: device ms per call}, every other kernel's device ms per call) of what fn launches, under torch's profiler"""
-    from torch.profiler import ProfilerActivity, profile
-    with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
-        for _ in range(calls):
-            fn()
-        torch.cuda.synchronize()
     times, other = {}, 0.0
-    for ev in prof.events():
-        if ev.device_time <= 0 or ev.device_type != torch.autograd.DeviceType.CUDA:
-            continue
+    for name, ms in device_events(fn, calls):
         for k in KERNELS:
-            if k in ev.name:
-                times[k] = times.get(k, 0.0) + ev.device_time / 1e3
+            if k in name:
+                times[k] = times.get(k, 0.0) + ms
                 break
         else:
-            other += ev.device_time / 1e3
+            other += ms
     return {k: round(v / calls, 4) for k, v in times.items()}, round(other / calls, 4)
-
-
-def span(v):
-    return [round(min(v), 4), round(max(v), 4)]
 
 
 def main(argv):

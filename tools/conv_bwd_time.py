@@ -5,72 +5,27 @@ refinement decoder's layer shapes -- 64 -> 64 and 128 -> 128 at 256 x 256, 128 -
     python tools/conv_bwd_time.py [--frames 16] [--rounds 5] [--calls 5] [--shapes 0,1,2,3,4,5]
 
 Both routes compute grad_input, grad_weight and grad_bias for the same grad_output; the forward passes (and the graphs) are made outside
-the timed part.  The two routes alternate call by call in one process, each call between two device events on a synchronised device;
-after WARM calls of each, a round is CALLS calls per route and gives one median per route; the range of the rounds' medians is reported.
-The HIP route's steps are timed the same way as calls of their own -- prepare (max |g|, grad_bias, g * s), grad_input (the forward kernel
-on the scaled g with the flipped weight, its packing included; the unscale pass), grad_weight (GEMM and adding kernel in one call) -- and
-its kernels as the medians of their device times under torch's profiler in a run of their own, which is what separates the GEMM from the
+the timed part.  The two routes alternate call by call (_measure.alternate): after 3 warm-up calls of each, a round is CALLS calls per
+route and gives one median per route; the range of the rounds' medians is reported.  The HIP route's steps are timed the same way as
+calls of their own -- prepare (max |g|, grad_bias, g * s), grad_input (the forward kernel on the scaled g with the flipped weight, its
+packing included; the unscale pass), grad_weight (GEMM and adding kernel in one call) -- and its kernels as the medians of their device
+times under torch's profiler in a run of their own (_measure.device_events, kernel_medians), which is what separates the GEMM from the
 adding kernel.  One JSON line per shape."""
 import argparse
 import json
 import os
 import sys
 
-import numpy as np
 import torch
 import torch.nn.functional as F
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from pixelsynth_amd import _lib  # noqa: E402
 from pixelsynth_amd.networks import f16x3  # noqa: E402
+from _measure import alternate, device_events, kernel_medians, span  # noqa: E402
 
-WARM = 3
 SHAPES = ((256, 64, 64), (256, 128, 128), (128, 128, 256), (128, 256, 256), (64, 256, 256), (64, 256, 128))      # (H = W, Ci, Co)
 KERNELS = ("k_prep_partial", "k_prep_finish", "k_scale", "k_grad_weight_parts", "k_grad_weight_sum", "k_conv3x3_f16x3", "k_pack")
-
-
-def alternate(routes, rounds, calls):
-    """routes {name: callable}; -> {name: the medians of `rounds` rounds of `calls` event-timed calls, in ms}, the routes taking turns
-    call by call"""
-    def one(fn):
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        e1.synchronize()
-        return e0.elapsed_time(e1)
-    for _ in range(WARM):
-        for fn in routes.values():
-            one(fn)
-    medians = {name: [] for name in routes}
-    for _ in range(rounds):
-        times = {name: [] for name in routes}
-        for _ in range(calls):
-            for name, fn in routes.items():
-                times[name].append(one(fn))
-        for name in routes:
-            medians[name].append(float(np.median(times[name])))
-    return medians
-
-
-def kernel_medians(fn, calls):
-    """{kernel: median device time in ms} of the kernels of KERNELS that fn launches, under torch's profiler; {} where it records none"""
-    from torch.profiler import ProfilerActivity, profile
-    with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
-        for _ in range(calls):
-            fn()
-        torch.cuda.synchronize()
-    times = {}
-    for ev in prof.events():
-        for k in KERNELS:
-            if k in ev.name and ev.device_time > 0:
-                times.setdefault(k, []).append(ev.device_time / 1e3)
-    return {k: round(float(np.median(v)), 4) for k, v in times.items()}
-
-
-def span(v):
-    return [round(min(v), 4), round(max(v), 4)]
 
 
 def main(argv):
@@ -114,7 +69,7 @@ def main(argv):
         med = alternate(routes, args.rounds, args.calls)
         ours, ref = routes["hip"](), routes["torch"]()
         diff = {k: float((p - q).abs().max() / q.abs().max()) for k, p, q in zip(("grad_input", "grad_weight", "grad_bias"), ours, ref)}
-        kern = kernel_medians(routes["hip"], args.calls)
+        kern = kernel_medians(device_events(routes["hip"], args.calls), KERNELS)
         flops = 2.0 * 9 * Ci * Co * B * H * W                       # of each of the two products (a third of what the split multiplies)
         rec = dict(what="conv3x3_backward", Ci=Ci, Co=Co, frames=B, H=H, W=W, rounds=args.rounds, calls=args.calls,
                    parts=_lib.call("ps_conv3x3_bwd_parts", B, H, W, Ci, Co), workspace_bytes=ws.numel(), flop_per_product=flops,

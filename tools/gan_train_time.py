@@ -5,10 +5,10 @@ matching with the gradient to the fake image, (b) the discriminator's, hinge on 
     python tools/gan_train_time.py [--pairs 16] [--size 256] [--ndf 64] [--rounds 5] [--calls 5]
 
 A call is forward plus backward of the mode's total.  The "hip" route (csrc/gan_train.hip: instance norm + LeakyReLU and the feature
-matching) and the "torch" route (F.instance_norm + F.leaky_relu, F.l1_loss per map, autograd's backward) alternate call by call in one
-process on the same weights and images, each call between two device events on a synchronised device; after WARM calls of each, a round
-is CALLS calls per route and gives one median per route; the range of the rounds' medians is reported.  Then the "hip" route once more
-under torch's profiler, in a run of its own: the device time of the new kernels by name, of the convolutions (what MIOpen and the BLAS
+matching) and the "torch" route (F.instance_norm + F.leaky_relu, F.l1_loss per map, autograd's backward) alternate call by call on the
+same weights and images (_measure.alternate): after 3 warm-up calls of each, a round is CALLS calls per route and gives one median per
+route; the range of the rounds' medians is reported.  Then the "hip" route once more under torch's profiler, in a run of its own
+(_measure.device_events): the device time of the new kernels by name, of the convolutions (what MIOpen and the BLAS
 launch, by their names) and of everything else, as shares of a call.  The convolutions are torch's on both routes.  The two routes'
 gradients are compared twice: as they are, and with no gradient through the elements within NEAR of a kink -- of the LeakyReLU behind
 a norm, of |f - r| in the feature matching -- where two fp32 evaluations may decide differently.  One JSON line per mode."""
@@ -24,7 +24,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from pixelsynth_amd import synthetic as syn  # noqa: E402
 from pixelsynth_amd.losses import DiscriminatorLoss  # noqa: E402
 from pixelsynth_amd.networks import gan_train as GT  # noqa: E402
-from norm_train_time import alternate, span  # noqa: E402
+from _measure import alternate, device_events, span  # noqa: E402
 
 NEAR = 1e-4        # |v| below which a normalised value counts as next to the LeakyReLU's kink in the routes' comparison
 OURS = ("k_norm_fwd_stream", "k_norm_bwd_stream", "k_norm_fwd", "k_norm_bwd", "k_feat_tiles", "k_feat_finish", "k_feat_bwd")
@@ -34,26 +34,18 @@ CONV_NAMES = ("conv", "Conv", "gemm", "Gemm", "GEMM", "Cijk", "igemm", "Igemm", 
 
 def shares(fn, calls):
     """{new kernel: median device ms per launch}, and the device ms of a call by class: ours, convolutions, the rest"""
-    from torch.profiler import ProfilerActivity, profile
-    with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
-        for _ in range(calls):
-            fn()
-        torch.cuda.synchronize()
     ours, total = {}, dict(ours=0.0, convolutions=0.0, rest=0.0)
     rest_names = {}
-    for ev in prof.events():
-        if ev.device_time <= 0 or ev.device_type != torch.autograd.DeviceType.CUDA:
-            continue
-        ms = ev.device_time / 1e3
-        mine = next((k for k in OURS if k in ev.name), None)
+    for name, ms in device_events(fn, calls):
+        mine = next((k for k in OURS if k in name), None)
         if mine:
             ours.setdefault(mine, []).append(ms)
             total["ours"] += ms
-        elif any(s in ev.name for s in CONV_NAMES):
+        elif any(s in name for s in CONV_NAMES):
             total["convolutions"] += ms
         else:
             total["rest"] += ms
-            rest_names[ev.name[:60]] = rest_names.get(ev.name[:60], 0.0) + ms
+            rest_names[name[:60]] = rest_names.get(name[:60], 0.0) + ms
     top = sorted(rest_names.items(), key=lambda kv: -kv[1])[:6]
     return ({k: [round(float(np.median(v)), 4), len(v) // calls] for k, v in ours.items()}, {k: round(v / calls, 3) for k, v in total.items()},
             [(n, round(v / calls, 3)) for n, v in top])

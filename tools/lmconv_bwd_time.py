@@ -5,23 +5,22 @@ against torch autograd through the reference's unfold formula (F.unfold, the mas
     python tools/lmconv_bwd_time.py [--frames 16] [--rounds 5] [--calls 10]
 
 Both routes compute grad_input, grad_weight and grad_bias for the same grad_output; the forward passes (and torch's graph) are made
-outside the timed part.  The two routes alternate call by call in one process, each call between two device events on a synchronised
-device; after WARM calls of each, a round is CALLS calls per route and gives one median per route; the range of the rounds' medians is
-reported, with the HIP route's two halves (grad_input alone; grad_weight and grad_bias alone) beside it, and the largest differences
-between the two routes' results.  One JSON line per shape."""
+outside the timed part.  The two routes alternate call by call (_measure.alternate): after 3 warm-up calls of each, a round is CALLS
+calls per route and gives one median per route; the range of the rounds' medians is reported, with the HIP route's two halves
+(grad_input alone; grad_weight and grad_bias alone) beside it, and the largest differences between the two routes' results.  One JSON
+line per shape."""
 import argparse
 import json
 import os
 import sys
 
-import numpy as np
 import torch
 import torch.nn.functional as F
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from pixelsynth_amd.lmconv.locally_masked_convolution import lmconv_backward  # noqa: E402
+from _measure import alternate, span  # noqa: E402
 
-WARM = 3
 H = W = 32
 SHAPES = ((513, 80, 1), (160, 80, 1), (160, 160, 1), (80, 80, 2))
 
@@ -32,35 +31,6 @@ def unfold_lmconv(x, m, w, b, dilation):
     xu = F.unfold(x, (3, 3), dilation=dilation, padding=dilation)
     xm = (xu.view(B, Ci, 9, -1) * m.unsqueeze(1)).view(B, Ci * 9, -1)
     return (w.view(w.size(0), -1).matmul(xm) + b.view(1, -1, 1)).view(B, -1, x.size(2), x.size(3))
-
-
-def alternate(routes, rounds, calls):
-    """routes {name: callable}; -> {name: the medians of `rounds` rounds of `calls` event-timed calls, in ms}, the routes taking turns
-    call by call"""
-    def one(fn):
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        e1.synchronize()
-        return e0.elapsed_time(e1)
-    for _ in range(WARM):
-        for fn in routes.values():
-            one(fn)
-    medians = {name: [] for name in routes}
-    for _ in range(rounds):
-        times = {name: [] for name in routes}
-        for _ in range(calls):
-            for name, fn in routes.items():
-                times[name].append(one(fn))
-        for name in routes:
-            medians[name].append(float(np.median(times[name])))
-    return medians
-
-
-def span(v):
-    return [round(min(v), 4), round(max(v), 4)]
 
 
 def main(argv):

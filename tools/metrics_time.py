@@ -4,7 +4,7 @@ evaluation/metrics.py) on the same GPU, and check both give the same numbers.
 
     python tools/metrics_time.py [--pairs 128] [--size 256] [--iters 50]
 
-Prints microseconds per batch (CUDA events, after warm-up) and, for the kernel, the fraction of two lower bounds from the shapes:
+Prints microseconds per batch (_measure.looped_ms: one pair of device events around ITERS calls, after 5 warm-up calls) and, for the kernel, the fraction of two lower bounds from the shapes:
 bytes / 8 TB/s and fp32-equivalent flops / 157.3 TFLOP/s (MI355X_MICROARCH.md; the kernel runs its filters in fp64, which this
 chip issues at the fp32 vector rate without packing)."""
 import argparse
@@ -20,6 +20,7 @@ import torch.nn.functional as F  # noqa: E402
 
 from pixelsynth_amd import synthetic as syn  # noqa: E402
 from pixelsynth_amd.image_metrics import image_metrics  # noqa: E402
+from _measure import looped_ms  # noqa: E402
 
 HBM = 8.0e12
 FP32 = 157.3e12
@@ -41,25 +42,12 @@ def torch_formula(a, b, m, window):
     return torch.stack([psnr, psnr_v, ssim, ssim_v], 1)
 
 
-def timed(fn, iters):
-    for _ in range(5):
-        fn()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(iters):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) * 1e3 / iters
-
-
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--pairs", type=int, default=128)
     ap.add_argument("--size", type=int, default=256)
     ap.add_argument("--iters", type=int, default=50)
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     dev = torch.device("cuda:0")
     B, C, S = args.pairs, 3, args.size
     h8 = [torch.from_numpy(x) for x in syn.metric_pair(1, B, C, S, S, "uint8")]
@@ -75,9 +63,9 @@ def main():
     bytes_u8 = px * C * 2 + px * 4
     # fp32-equivalent flops of the formula: 5 maps x 11 taps x 2 passes x 2 flops + 3 products + ~20 for the map and the sums
     flops = px * C * (5 * 11 * 2 * 2 + 3 + 20)
-    t_f32 = timed(lambda: image_metrics(a, b, m), args.iters)
-    t_u8 = timed(lambda: image_metrics(a8, b8, m), args.iters)
-    t_torch = timed(lambda: torch_formula(a, b, m, window), args.iters)
+    t_f32 = looped_ms(lambda: image_metrics(a, b, m), args.iters, 5) * 1e3
+    t_u8 = looped_ms(lambda: image_metrics(a8, b8, m), args.iters, 5) * 1e3
+    t_torch = looped_ms(lambda: torch_formula(a, b, m, window), args.iters, 5) * 1e3
     ours = image_metrics(a, b, m)[:, [0, 1, 3, 4]]
     ref = torch_formula(a, b, m, window)
     dp = (ours[:, :2] - ref[:, :2]).abs().max().item()

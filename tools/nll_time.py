@@ -4,16 +4,15 @@ sums per group with a mask -- and one score_codes call next to the engine's forw
 
     python tools/nll_time.py [--frames 128] [--rounds 5] [--calls 20]
 
-The logits are made once, outside the timed part (normal, magnitude 3).  The two routes alternate call by call in one process, each
-call between two device events on a synchronised device; after WARM calls of each, a round is CALLS calls per route and gives one
-median per route; the range of the rounds' medians is reported.  The results of the two routes are compared, and the bytes the kernel
+The logits are made once, outside the timed part (normal, magnitude 3).  The two routes alternate call by call (_measure.alternate):
+after 3 warm-up calls of each, a round is CALLS calls per route and gives one median per route; the range of the rounds' medians is
+reported.  The results of the two routes are compared, and the bytes the kernel
 has to move over 8 TB/s are given as its lower bound.  One JSON line per layout and one for score_codes at the end."""
 import argparse
 import json
 import os
 import sys
 
-import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -21,8 +20,8 @@ from pixelsynth_amd import synthetic as syn  # noqa: E402
 from pixelsynth_amd.likelihood import code_nll, score_codes  # noqa: E402
 from pixelsynth_amd.lmconv.model import OurPixelCNN  # noqa: E402
 from pixelsynth_amd.lmconv.layers import PONO  # noqa: E402
+from _measure import alternate, span  # noqa: E402
 
-WARM = 3
 HBM = 8.0e12
 L = 1024
 
@@ -38,35 +37,6 @@ def torch_route(logits, targets, region, T, layout):
     cols = torch.stack([torch.ones_like(nll, dtype=torch.float64), nll.double(), entropy.double(), hit.double()], -1)   # (F,L,4)
     frames = torch.stack([(cols * (~g)[..., None]).sum(1), (cols * g[..., None]).sum(1)], 1)
     return nll, entropy, hit, frames
-
-
-def alternate(routes, rounds, calls):
-    """routes {name: callable}; -> {name: the medians of `rounds` rounds of `calls` event-timed calls, in ms}, the routes taking turns
-    call by call"""
-    def one(fn):
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        e1.synchronize()
-        return e0.elapsed_time(e1)
-    for _ in range(WARM):
-        for fn in routes.values():
-            one(fn)
-    medians = {name: [] for name in routes}
-    for _ in range(rounds):
-        times = {name: [] for name in routes}
-        for _ in range(calls):
-            for name, fn in routes.items():
-                times[name].append(one(fn))
-        for name in routes:
-            medians[name].append(float(np.median(times[name])))
-    return medians
-
-
-def span(v):
-    return [round(min(v), 4), round(max(v), 4)]
 
 
 def make_net(device):

@@ -6,9 +6,9 @@ channels-last tensors.
     python tools/norm_train_time.py [--frames 16] [--rounds 5] [--calls 5] [--shapes 0,1,2,3,4]
 
 A call is forward plus backward: y and the update of the stored statistics, then the gradients in x, gain and bias for one grad_output.
-The two routes alternate call by call in one process, each call between two device events on a synchronised device; after WARM calls
-of each, a round is CALLS calls per route and gives one median per route; the range of the rounds' medians is reported.  The HIP route's
-kernels are the medians of their device times under torch's profiler in a run of their own, each with the bytes it has to move over
+The two routes alternate call by call (_measure.alternate): after 3 warm-up calls of each, a round is CALLS calls per route and gives one
+median per route; the range of the rounds' medians is reported.  The HIP route's kernels are the medians of their device times under
+torch's profiler in a run of their own (_measure.device_events, kernel_medians), each with the bytes it has to move over
 that time next to the 6.3 TB/s a float4 copy reaches on this GPU (MI355X_MICROARCH.md).  The two routes' gradients are compared on a
 grad_output that is zero where the value in front of the ReLU is within 1e-4 of 0.  One JSON line per shape."""
 import argparse
@@ -16,63 +16,18 @@ import json
 import os
 import sys
 
-import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from pixelsynth_amd import _lib  # noqa: E402
 from pixelsynth_amd.networks import architectures as A, norm_train as NT  # noqa: E402
+from _measure import alternate, device_events, kernel_medians, span  # noqa: E402
 
-WARM = 3
 COPY_TBS = 6.3
 SHAPES = ((64, 256), (128, 256), (128, 128), (256, 128), (256, 64))      # (C, H = W)
-# kernel -> passes over the activation it reads or writes (the partial slabs and per-channel tables are a thousandth of that)
+# kernel -> passes over the activation it reads or writes (the partial slabs and per-channel tables are a thousandth of that); in the
+# order kernel_medians needs: k_stats_finish before k_stats
 KERNELS = {"k_stats_finish": 0, "k_stats": 1, "k_apply": 2, "k_bwd_sums": 2, "k_bwd_frames": 0, "k_bwd_channels": 0, "k_bwd_dx": 3}
-
-
-def alternate(routes, rounds, calls):
-    """routes {name: callable}; -> {name: the medians of `rounds` rounds of `calls` event-timed calls, in ms}, the routes taking turns
-    call by call"""
-    def one(fn):
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        e1.synchronize()
-        return e0.elapsed_time(e1)
-    for _ in range(WARM):
-        for fn in routes.values():
-            one(fn)
-    medians = {name: [] for name in routes}
-    for _ in range(rounds):
-        times = {name: [] for name in routes}
-        for _ in range(calls):
-            for name, fn in routes.items():
-                times[name].append(one(fn))
-        for name in routes:
-            medians[name].append(float(np.median(times[name])))
-    return medians
-
-
-def kernel_medians(fn, calls):
-    """{kernel: median device time in ms} of the kernels of KERNELS that fn launches, under torch's profiler; {} where it records none"""
-    from torch.profiler import ProfilerActivity, profile
-    with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
-        for _ in range(calls):
-            fn()
-        torch.cuda.synchronize()
-    times = {}
-    for ev in prof.events():
-        for k in KERNELS:                       # (k_stats_finish before k_stats: the first name found in the event's is its kernel)
-            if k in ev.name and ev.device_time > 0:
-                times.setdefault(k, []).append(ev.device_time / 1e3)
-                break
-    return {k: round(float(np.median(v)), 4) for k, v in times.items()}
-
-
-def span(v):
-    return [round(min(v), 4), round(max(v), 4)]
 
 
 def main(argv):
@@ -114,7 +69,7 @@ def main(argv):
         del near0
         ours, ref = step("hip", gc), step("torch", gc)
         diff = {k: float((p - q).abs().max() / q.abs().max()) for k, p, q in zip(("dx", "dgain", "dbias"), ours, ref)}
-        kern = kernel_medians(routes["hip"], args.calls)
+        kern = kernel_medians(device_events(routes["hip"], args.calls), KERNELS)
         act = 4.0 * B * C * H * W                                       # bytes of one pass over the activation
         rates = {k: round(KERNELS[k] * act / (t * 1e-3) / 1e12, 3) for k, t in kern.items() if KERNELS[k]}
         rec = dict(what="norm_relu_train", C=C, frames=B, H=H, W=W, rounds=args.rounds, calls=args.calls,

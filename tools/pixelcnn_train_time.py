@@ -4,10 +4,10 @@ configuration on 32 x 32 grids at 16 and 64 frames (the reference's batch size),
     python tools/pixelcnn_train_time.py [--frames 16,64] [--grid 32] [--rounds 5] [--calls 5]
 
 The "hip" route (csrc/pixelcnn_train.hip: PONO + skip + activation, the gate, the loss's backward; lmconv/train_ops.py) and the
-"torch" route (the layers as plain torch, F.cross_entropy) alternate call by call in one process on the same weights, codes and masks,
-each call between two device events on a synchronised device; after WARM calls of each, a round is CALLS calls per route and gives one
-median per route; the range of the rounds' medians is reported.  Then each route once more under torch's profiler, in a run of its
-own: the device time of a call by class -- the masked convolutions (csrc/lmconv*.hip, both ways), the new kernels, the forward of the
+"torch" route (the layers as plain torch, F.cross_entropy) alternate call by call on the same weights, codes and masks
+(_measure.alternate): after 3 warm-up calls of each, a round is CALLS calls per route and gives one median per route; the range of the
+rounds' medians is reported.  Then each route once more under torch's profiler, in a run of its own (_measure.device_events): the
+device time of a call by class -- the masked convolutions (csrc/lmconv*.hip, both ways), the new kernels, the forward of the
 loss (csrc/code_nll.hip), the nin products (what the BLAS launches, by its names), everything else --, the number of kernel launches
 of a call, and, in a further run, torch.cuda.max_memory_allocated of a call.  The masked convolutions and the nin products are the
 same code on both routes.  One JSON line per number of frames."""
@@ -25,7 +25,7 @@ from pixelsynth_amd.likelihood import ar_loss  # noqa: E402
 from pixelsynth_amd.lmconv import train_ops  # noqa: E402
 from pixelsynth_amd.lmconv.layers import PONO  # noqa: E402
 from pixelsynth_amd.lmconv.model import OurPixelCNN  # noqa: E402
-from norm_train_time import alternate, span  # noqa: E402
+from _measure import alternate, device_events, span  # noqa: E402
 
 CLASSES = {
     "masked_convolutions": ("k_nchw_to_cl", "k_pack_conv", "k_gemm", "k_reduce_nchw", "k_to_cl", "k_grad_weight", "k_grad_bias", "k_adjoint_mask"),
@@ -41,20 +41,13 @@ def classify(name):
 
 def by_class(fn, calls):
     """-> (device ms of a call by class, kernel launches of a call by class, the six largest names of the rest) under torch's profiler"""
-    from torch.profiler import ProfilerActivity, profile
-    with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
-        for _ in range(calls):
-            fn()
-        torch.cuda.synchronize()
     ms, n, rest = dict.fromkeys(list(CLASSES) + ["rest"], 0.0), dict.fromkeys(list(CLASSES) + ["rest"], 0), {}
-    for ev in prof.events():
-        if ev.device_type != torch.autograd.DeviceType.CUDA or ev.device_time <= 0:
-            continue
-        k = classify(ev.name)
-        ms[k] += ev.device_time / 1e3
+    for name, t in device_events(fn, calls):
+        k = classify(name)
+        ms[k] += t
         n[k] += 1
         if k == "rest":
-            rest[ev.name[:60]] = rest.get(ev.name[:60], 0.0) + ev.device_time / 1e3
+            rest[name[:60]] = rest.get(name[:60], 0.0) + t
     top = sorted(rest.items(), key=lambda kv: -kv[1])[:6]
     return ({k: round(v / calls, 3) for k, v in ms.items()}, {k: round(v / calls, 1) for k, v in n.items()},
             [(name, round(v / calls, 3)) for name, v in top])

@@ -7,7 +7,7 @@ A chain is TWO frames (gen_scene, one direction, num_split = 1: first the far en
 source, rendered from the generated far end on top of its cloud) with everything of a frame in the loop: depth stand-in, reprojection
 + splat, AR plan, VQ-VAE codes, AR outpainting, decode, blend.  "splat" times the reprojection + splat of the same two frames alone (PtsManipulator.forward_scene_step
 against forward_justpts_cumulative per scene, masks fixed), the part this route replaces.  The two routes ALTERNATE within the call,
-after a warm-up of both; every sample is a pair of device events around work that ends in a synchronise; the figure is the median.
+after a warm-up of both (2 calls each); every sample is _measure.event_ms of work that ends in a synchronise; the figure is the median.
 At B = 1 forward_scene takes the B = 1 route itself: both columns then time the same code, and their difference is the noise floor.
 
 Prints one JSON line: ms per scene-frame per route and B, and the bytes of state and workspace per scene at the capacity used."""
@@ -27,6 +27,7 @@ import torch  # noqa: E402
 from pixelsynth_amd import _lib, synthetic as syn  # noqa: E402
 from pixelsynth_amd.projection.z_buffer_manipulator import SceneState  # noqa: E402
 from pixelsynth_amd.z_buffermodel import ZbufferModelPts  # noqa: E402
+from _measure import event_ms  # noqa: E402
 
 S, FRAMES = 256, 2
 
@@ -48,21 +49,10 @@ def scenes(B, dev):
     return torch.from_numpy(img).to(dev), cam
 
 
-def event_ms(fn):
-    """fn ends in a synchronise of its own or not: the second event is waited for either way"""
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1)
-
-
-def alternate(batched, single, iters):
+def take_turns(batched, single, iters):
     for _ in range(2):
         batched()
         single()
-    torch.cuda.synchronize()
     tb, ts = [], []
     for _ in range(iters):
         tb.append(event_ms(batched))
@@ -70,11 +60,11 @@ def alternate(batched, single, iters):
     return statistics.median(tb), statistics.median(ts)
 
 
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--batches", type=int, nargs="+", default=[1, 4, 16, 64])
     ap.add_argument("--iters", type=int, default=8)
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     dev = torch.device("cuda:0")
     m = make_model(dev)
     pm = m.pts_transformer
@@ -101,7 +91,7 @@ def main():
                 for one in ones:
                     m(one)
                 torch.cuda.synchronize()
-            t_b, t_s = alternate(scene_batched, scene_single, args.iters)
+            t_b, t_s = take_turns(scene_batched, scene_single, args.iters)
 
             # the reprojection + splat of the same two frames alone, on fixed inputs
             depth = syn.depth_from_image(img)
@@ -124,7 +114,7 @@ def main():
                     r = pm.forward_justpts_cumulative(*[a[sl] for a in args0], None, None, None, None)
                     pm.forward_justpts_cumulative(*[a[sl] for a in args1], r[2], r[3], bg[sl], RTinv[sl])
                 torch.cuda.synchronize()
-            p_b, p_s = alternate(splat_batched, splat_single, args.iters)
+            p_b, p_s = take_turns(splat_batched, splat_single, args.iters)
         per = 1.0 / (B * FRAMES)
         out["B"][str(B)] = {"batched_ms_per_scene_frame": round(t_b * per, 4), "b1_route_ms_per_scene_frame": round(t_s * per, 4),
                             "speedup": round(t_s / t_b, 2), "splat_batched_ms_per_scene_frame": round(p_b * per, 4),

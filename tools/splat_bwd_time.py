@@ -6,10 +6,10 @@ on the same saved lists on the device.
     python tools/splat_bwd_time.py [--frames 16] [--rounds 5] [--calls 5]
 
 Both routes compute grad_pts and grad_feat for the same grad_out; the forward passes (and torch's graph) are made outside the timed
-part.  The two routes alternate call by call in one process, each call between two device events on a synchronised device; after WARM
-calls of each, a round is CALLS calls per route and gives one median per route; the range of the rounds' medians is reported.  The HIP
-route's kernels (pixels, points) and the backward of the projection are reported separately, as the medians of their device times under
-torch's profiler in a run of their own.  Where the torch formula's tensors of B x C x S x S x K elements do not fit the device's free
+part.  The two routes alternate call by call (_measure.alternate): after 2 warm-up calls of each, a round is CALLS calls per route and
+gives one median per route; the range of the rounds' medians is reported.  The HIP route's kernels (pixels, points) and the backward of
+the projection are reported separately, as the medians of their device times under torch's profiler in a run of their own
+(_measure.device_events, kernel_medians).  Where the torch formula's tensors of B x C x S x S x K elements do not fit the device's free
 memory it is not timed, and the line says so.  One JSON line per shape."""
 import argparse
 import json
@@ -24,8 +24,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from pixelsynth_amd import _lib, synthetic as syn  # noqa: E402
 from pixelsynth_amd.layers.z_buffer_layers import splat_bwd_workspace, splat_workspace  # noqa: E402
 from pixelsynth_amd.projection.z_buffer_manipulator import PtsManipulator  # noqa: E402
+from _measure import alternate, device_events, kernel_medians, span  # noqa: E402
 
-WARM = 2
 S, RADIUS, TAU, RAD_POW, ACC = 256, 4.0, 1.0, 2, 0
 SHAPES = ((3, 8), (64, 8), (3, 128), (64, 128))       # (C, K)
 KERNELS = ("k_splat_bwd_pixels", "k_splat_bwd_points", "k_project_bwd")
@@ -46,51 +46,6 @@ def gather_formula(pts, feat, idx, N):
     w = a * torch.cat([torch.ones_like(a[..., :1]), torch.cumprod(1.0 - a, dim=-1)[..., :-1]], dim=-1)
     f = torch.gather(feat, 2, flat.unsqueeze(1).expand(B, C, -1)).reshape(B, C, *n.shape[1:])
     return (w.unsqueeze(1) * f).sum(-1)
-
-
-def one(fn):
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1)
-
-
-def alternate(routes, rounds, calls):
-    """routes {name: callable}; -> {name: the medians of `rounds` rounds of `calls` event-timed calls, in ms}, the routes taking turns"""
-    for _ in range(WARM):
-        for fn in routes.values():
-            one(fn)
-    medians = {name: [] for name in routes}
-    for _ in range(rounds):
-        times = {name: [] for name in routes}
-        for _ in range(calls):
-            for name, fn in routes.items():
-                times[name].append(one(fn))
-        for name in routes:
-            medians[name].append(float(np.median(times[name])))
-    return medians
-
-
-def kernel_medians(fn, calls):
-    """{kernel: median device time in ms} of the kernels of KERNELS that fn launches, under torch's profiler; {} where it records none"""
-    from torch.profiler import ProfilerActivity, profile
-    with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
-        for _ in range(calls):
-            fn()
-        torch.cuda.synchronize()
-    times = {}
-    for ev in prof.events():
-        for k in KERNELS:
-            if k in ev.name and ev.device_time > 0:
-                times.setdefault(k, []).append(ev.device_time / 1e3)
-    return {k: round(float(np.median(v)), 4) for k, v in times.items()}
-
-
-def span(v):
-    return [round(min(v), 4), round(max(v), 4)]
 
 
 def main(argv):
@@ -142,13 +97,13 @@ def main(argv):
             p_t, f_t = pts.clone().requires_grad_(), feat.clone().requires_grad_()
             y = gather_formula(p_t, f_t, idx, N)
             routes["torch"] = lambda: torch.autograd.grad(y, (p_t, f_t), g, retain_graph=True)
-        med = alternate(routes, args.rounds, args.calls)
+        med = alternate(routes, args.rounds, args.calls, warm=2)
         if "torch" in routes:
             hip()
             ref = routes["torch"]()
             diff = {"grad_pts": float((gp - ref[0]).abs().max()), "grad_feat": float((gf - ref[1]).abs().max())}
             del y, ref
-        kern = kernel_medians(lambda: (hip(), project()), args.calls)
+        kern = kernel_medians(device_events(lambda: (hip(), project()), args.calls), KERNELS)
         rec = dict(what="splat_backward", frames=B, S=S, N=N, C=C, K=K, radius_px=RADIUS, hits_per_pixel=round(hits, 2), rounds=args.rounds,
                    calls=args.calls, kernel_ms_median=kern, max_abs_diff=diff, note=note,
                    **{f"{k}_ms_median_range": span(v) for k, v in med.items()})

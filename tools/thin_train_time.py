@@ -4,71 +4,25 @@ they take without the opt-in: torch autograd of F.conv2d on the same channels-la
 
     python tools/thin_train_time.py [--frames 16] [--size 256] [--rounds 5] [--calls 5] [--layers 0,1,2,3]
 
-Per layer: forward plus the gradients in x, weight and bias for one grad_output.  The two routes alternate call by call in one process, each
-call between two device events on a synchronised device; after WARM calls of each, a round is CALLS calls per route and gives one median
-per route; the range of the rounds' medians is reported.  The HIP route's kernels are the medians of their device times under torch's
-profiler in a run of their own.  The routes' gradients are compared with each other.  One JSON line per layer."""
+Per layer: forward plus the gradients in x, weight and bias for one grad_output.  The two routes alternate call by call
+(_measure.alternate): after 3 warm-up calls of each, a round is CALLS calls per route and gives one median per route; the range of the
+rounds' medians is reported.  The HIP route's kernels are the medians of their device times under torch's profiler in a run of their own
+(_measure.device_events, kernel_medians).  The routes' gradients are compared with each other.  One JSON line per layer."""
 import argparse
 import json
 import os
 import sys
 
-import numpy as np
 import torch
 import torch.nn.functional as F
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from pixelsynth_amd import _lib  # noqa: E402
 from pixelsynth_amd.networks import thin_train as TT  # noqa: E402
+from _measure import alternate, device_events, kernel_medians, span  # noqa: E402
 
-WARM = 3
 LAYERS = (("in", 4, 64, 3), ("in", 4, 64, 1), ("out", 128, 3, 3), ("out", 128, 3, 1))      # (kind, Ci, Co, k)
 KERNELS = ("k_thin_grad_weight", "k_thin_sum_parts", "k_thin_expand", "k_thin_add_bias", "k_thin_in", "k_thin_out", "k_conv1x1")
-
-
-def alternate(routes, rounds, calls):
-    """routes {name: callable}; -> {name: the medians of `rounds` rounds of `calls` event-timed calls, in ms}, the routes taking turns
-    call by call"""
-    def one(fn):
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        e1.synchronize()
-        return e0.elapsed_time(e1)
-    for _ in range(WARM):
-        for fn in routes.values():
-            one(fn)
-    medians = {name: [] for name in routes}
-    for _ in range(rounds):
-        times = {name: [] for name in routes}
-        for _ in range(calls):
-            for name, fn in routes.items():
-                times[name].append(one(fn))
-        for name in routes:
-            medians[name].append(float(np.median(times[name])))
-    return medians
-
-
-def kernel_medians(fn, calls):
-    """{kernel: median device time in ms} of the kernels of KERNELS that fn launches, under torch's profiler; {} where it records none"""
-    from torch.profiler import ProfilerActivity, profile
-    with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
-        for _ in range(calls):
-            fn()
-        torch.cuda.synchronize()
-    times = {}
-    for ev in prof.events():
-        for k in KERNELS:                       # (the first name found in the event's is its kernel)
-            if k in ev.name and ev.device_time > 0:
-                times.setdefault(k, []).append(ev.device_time / 1e3)
-                break
-    return {k: round(float(np.median(v)), 4) for k, v in times.items()}
-
-
-def span(v):
-    return [round(min(v), 4), round(max(v), 4)]
 
 
 def main(argv):
@@ -98,7 +52,7 @@ def main(argv):
         med = alternate(routes, args.rounds, args.calls)
         ours, ref = routes["hip"](), routes["torch"]()
         diff = {n: float((p - q).abs().max() / q.abs().max()) for n, p, q in zip(("dx", "dw", "db"), ours, ref)}
-        kern = kernel_medians(routes["hip"], args.calls)
+        kern = kernel_medians(device_events(routes["hip"], args.calls), KERNELS)
         wide, T = (Co, Ci) if kind == "in" else (Ci, Co)
         rec = dict(what="conv_thin_%s_train" % kind, Ci=Ci, Co=Co, k=k, frames=B, H=H, W=W, rounds=args.rounds, calls=args.calls,
                    parts=_lib.call("ps_thin_train_parts", B, H, W, wide, T, k), kernel_ms_median=kern, max_diff_over_max=diff,

@@ -6,23 +6,21 @@ one-hot, two dense products against it, the EMA update, the straight-through out
     python tools/vq_train_time.py [--rounds 5] [--calls 10]
 
 Both routes compute quantize, diff and the codes, update the three buffers, and take the gradient with respect to the input for the same
-grad_quantize and grad_diff.  The routes alternate call by call in one process, each call between two device events on a synchronised
-device; after WARM calls of each, a round is CALLS calls per route and gives one median per route; the range of the rounds' medians is
-reported.  Beside the two whole routes: each with the codes GIVEN (what follows the arg-min), and ps_vq_nearest_f32 alone.  One JSON
+grad_quantize and grad_diff.  The routes alternate call by call (_measure.alternate): after 3 warm-up calls of each, a round is CALLS calls
+per route and gives one median per route; the range of the rounds' medians is reported.  Beside the two whole routes: each with the codes GIVEN (what follows the arg-min), and ps_vq_nearest_f32 alone.  One JSON
 line per shape."""
 import argparse
 import json
 import os
 import sys
 
-import numpy as np
 import torch
 import torch.nn.functional as F
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from pixelsynth_amd.vqvae2.vqvae import Quantize  # noqa: E402
+from _measure import alternate, span  # noqa: E402
 
-WARM = 3
 SHAPES = ((65536, 64, 512), (262144, 64, 512))
 
 
@@ -45,35 +43,6 @@ def torch_quantize(q, z, codes=None):
     q.embed.copy_(q.embed_avg / smoothed)
     residual = (chosen - z).detach()
     return z + residual, (z - chosen.detach()).pow(2).mean(), codes
-
-
-def alternate(routes, rounds, calls):
-    """routes {name: callable}; -> {name: the medians of `rounds` rounds of `calls` event-timed calls, in ms}, the routes taking turns
-    call by call"""
-    def one(fn):
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        e1.synchronize()
-        return e0.elapsed_time(e1)
-    for _ in range(WARM):
-        for fn in routes.values():
-            one(fn)
-    medians = {name: [] for name in routes}
-    for _ in range(rounds):
-        times = {name: [] for name in routes}
-        for _ in range(calls):
-            for name, fn in routes.items():
-                times[name].append(one(fn))
-        for name in routes:
-            medians[name].append(float(np.median(times[name])))
-    return medians
-
-
-def span(v):
-    return [round(min(v), 4), round(max(v), 4)]
 
 
 def main(argv):
