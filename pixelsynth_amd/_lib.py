@@ -265,12 +265,22 @@ PIXELCNN_TRAIN_PROTOS = {
     "ps_code_nll_backward_f32": (RC, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_double, c_int, c_int, c_void_p, c_void_p, STREAM]),
 }
 
+# libpixelsynth_train_glue.so (include/pixelsynth_train_glue.h): the depth head and the blend + mask channel into the decoder's NHWC input,
+# forward and backward, of the generator's training step
+TRAIN_GLUE_PROTOS = {
+    "ps_train_glue_last_error": (ctypes.c_char_p, []),
+    "ps_combine_mask_nhwc_f32": (RC, [c_void_p] * 3 + [c_int] * 3 + [c_void_p, STREAM]),
+    "ps_combine_mask_nhwc_backward_f32": (RC, [c_void_p] * 2 + [c_int] * 3 + [c_void_p, STREAM]),
+    "ps_depth_head_forward_f32": (RC, [c_void_p, c_int, c_double, c_double, ctypes.c_longlong, c_void_p, c_void_p, STREAM]),
+    "ps_depth_head_backward_f32": (RC, [c_void_p, c_void_p, c_int, c_double, c_double, ctypes.c_longlong, c_void_p, STREAM]),
+}
+
 # short name of _libraries.LIBRARIES -> its prototype table; _OWNER: entry point -> the table entry of its library, built once
 PROTOS = {"hip": _PROTOS, "percsim": PERCSIM_PROTOS, "consistency": CONSISTENCY_PROTOS, "fid": FID_PROTOS, "scene": SCENE_PROTOS,
           "plan": PLAN_PROTOS, "rank": RANK_PROTOS, "rank_groups": RANK_GROUPS_PROTOS, "nll": NLL_PROTOS, "lmconv_bwd": LMCONV_BWD_PROTOS, "splat_bwd": SPLAT_BWD_PROTOS,
           "vq_train": VQ_TRAIN_PROTOS, "conv_bwd": CONV_BWD_PROTOS, "norm_train": NORM_TRAIN_PROTOS,
           "block_train": BLOCK_TRAIN_PROTOS, "content": CONTENT_PROTOS, "thin_train": THIN_TRAIN_PROTOS,
-          "pixelcnn_train": PIXELCNN_TRAIN_PROTOS, "gan_train": GAN_TRAIN_PROTOS}
+          "pixelcnn_train": PIXELCNN_TRAIN_PROTOS, "train_glue": TRAIN_GLUE_PROTOS, "gan_train": GAN_TRAIN_PROTOS}
 _ENTRIES = {e.name: e for e in _libraries.LIBRARIES}
 assert set(PROTOS) == set(_ENTRIES)
 _OWNER = {fn: _ENTRIES[name] for name, table in PROTOS.items() for fn in table}

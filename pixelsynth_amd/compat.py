@@ -134,3 +134,15 @@ def install_gan_aliases(force=False):
     matching on the HIP kernels when training) under the reference's module names, so `from models.losses.gan_loss import
     DiscriminatorLoss` in models/base_model.py runs unchanged.  A table of its own: a caller picks the adversarial half by itself."""
     return _install(GAN_ALIASES, force)
+
+
+BASE_MODEL_ALIASES = {
+    "models.base_model": "pixelsynth_amd.base_model",
+}
+
+
+def install_base_model_aliases(force=False):
+    """Register the training step (BaseModel: the model, the discriminator, both optimisers, one step per call) under the reference's
+    module name, so a training script's `from models.base_model import BaseModel` runs unchanged.  A table of its own: the other
+    install_* functions register what they registered before, and a caller that keeps the reference's own step does not call this."""
+    return _install(BASE_MODEL_ALIASES, force)

@@ -1,0 +1,27 @@
+"""What a training loop of the generator needs beside the model (z_buffermodel.ZbufferModelPts.forward_train) and the step
+(base_model.BaseModel): the route switches of the training kernels as one context.
+
+Several of the training units are opt-in (their switches default to the torch formula, so that a model trained before they existed
+computes what it computed); hip_routes() turns all of them on for the calls inside."""
+import contextlib
+
+from .lmconv.train_ops import pixelcnn_train
+from .networks.block_train import decoder_block_train
+from .networks.f16x3 import decoder_conv_train
+from .networks.thin_train import decoder_thin_train
+from .networks.train_glue import train_glue
+
+# every training switch and its HIP value (routing.Switch); the norm's and the discriminator's switches default to "hip" already
+HIP_ROUTES = ((decoder_conv_train, "f16x3"), (decoder_block_train, "hip"), (decoder_thin_train, "hip"), (pixelcnn_train, "hip"),
+              (train_glue, "hip"))
+
+
+@contextlib.contextmanager
+def hip_routes():
+    """Every training switch at its HIP value for the calls inside, whatever the options and the environment say: decoder_conv_train
+    ("f16x3"), decoder_block_train, decoder_thin_train, pixelcnn_train, train_glue ("hip").  Blocks nest like the switches' own: a
+    switch forced inside this block wins there.  -> {switch name: mode} as Switch.forced() reports them inside the block."""
+    with contextlib.ExitStack() as stack:
+        for switch, value in HIP_ROUTES:
+            stack.enter_context(switch(value))
+        yield {switch.name: switch.forced() for switch, _ in HIP_ROUTES}

@@ -29,6 +29,7 @@ from .best_sample import RANK_ROUTES, RANK_SCOPES, _rank_route, _rank_scope, ran
 from .lmconv.layers import PONO
 from .lmconv.model import OurPixelCNN
 from .lmconv.sample import sample
+from .networks import train_glue
 from .networks.f16x3 import checked
 from .outpaint import OutpaintPipeline
 from .projection.z_buffer_manipulator import PtsManipulator
@@ -72,6 +73,9 @@ class ZbufferModelPts(OutpaintPipeline, SceneChain, nn.Module):
                         'DR': np.array([.15, .3, 0]), 'DL': np.array([.15, -.3, 0])}  # :113-114
         self.mapping = ['R', 'L', 'U', 'D', 'UL', 'UR', 'DR', 'DL']
         self.sample_batch = 32        # frames (candidates x views) a get_best_sample engine run takes at most
+        if getattr(opt, "losses", None):   # z_buffermodel.py:94 (the training options carry the list; an inference model has no loss)
+            from .losses.synthesis import SynthesisLoss
+            self.loss_function = SynthesisLoss(opt)
 
     # ---------------------------------------------------------------- what every entry point reads off the options and the batch
     @property
@@ -292,6 +296,88 @@ class ZbufferModelPts(OutpaintPipeline, SceneChain, nn.Module):
                 "ar_accuracy_sampled": score.accuracy("sampled"), "ar_frames": score.frames}
         return loss, outputs
 
+    # ---------------------------------------------------------------- the generator's training forward (z_buffermodel.py:291-419, 'train')
+    def forward_train(self, batch):
+        """The reference's forward_image with model_setting 'train' (z_buffermodel.py:291-419) as a DIFFERENTIABLE method, what
+        BaseModel (base_model.py) takes a step on.  batch: images [source, ..., target], cameras [source, ..., target], optional
+        "depths" (the source view's, (B,1,S,S)) for opt.use_gt_depth / opt.train_depth.  -> (loss, outputs) as the reference.
+          depth      the regressor's output through networks.train_glue.depth_head (:303-314), in grad mode; the given depth with
+                     opt.use_gt_depth (or where the model has no regressor)
+          splat      _features, then pts_transformer.forward_justpts: differentiable in the depth and the features (csrc/splat_bwd.hip)
+          opt.no_outpainting   PredImg = projector(gen_fs, None), no AR term (:383-384)
+          otherwise  the compact plan from the background mask, codes = vqvae.encode_codes(target) and input_gt =
+                     vqvae.decode_code(codes), all three without gradients (the VQ-VAE is frozen: train_dpr.py:431-433); unless
+                     opt.pretrain, autoreg_loss = likelihood.ar_loss over ALL locations at T = 1 (what nn.CrossEntropyLoss() gives at
+                     :362); the decoder's input is train_glue.combine_mask_nhwc(gen_fs, input_gt, background_mask) -- blend, mask
+                     channel and channels-last copy in one pass --, or, with opt.predict_residual (which adds the 3-channel blend to
+                     the decoder's output), get_combined and the decoder's own concatenation
+          loss       loss_function(PredImg, target) (SynthesisLoss, built where opt.losses exists); "autoreg_loss" = autoreg_loss /
+                     (B * prod(obs) * ln 2) * 1000 -- obs = [3,32,32], so the reference's stray factor 3 is kept --, "Total Loss" +=
+                     autoreg_loss * opt.lambda_autoreg (or += autoreg_loss where that option is absent or None); with opt.train_depth
+                     "depth_loss" = L1(depth, batch["depths"][0]) is added and reported.  The reference reads a `depth_img` there that
+                     its forward_image never binds (:316, :405); the SOURCE view's depth is this project's reading of it.
+                     Both additions are IN PLACE, as the reference writes them (:400-406): where opt.losses names a single term,
+                     SynthesisLoss hands that term's tensor out under both names, so the reported "L1" is then the total as well --
+                     the reference's logs show the same number, and the fixture recorded from it holds this to it.
+          outputs    InputImg, PredImg, PredDepthImg, ForegroundImg, OutputImg; no FeaturesImg (:385-417)
+        A model without a VQ-VAE would take the reference's mixture-of-logistics branch (:364-368, :374): NotImplementedError."""
+        opt = self.opt
+        if len(batch["images"]) < 2 or len(batch["cameras"]) < 2:
+            raise ValueError("forward_train: the batch carries the target view, images [source, target] and cameras [source, target]")
+        if not hasattr(self, "loss_function"):
+            raise RuntimeError("forward_train: the model has no loss_function (opt.losses names the terms of SynthesisLoss)")
+        dev, input_img, K, K_inv, input_RT, input_RTinv = self._source_view(batch)
+        output_img = batch["images"][-1].to(dev)
+        output_RT, output_RTinv = batch["cameras"][-1]["P"].to(dev), batch["cameras"][-1]["Pinv"].to(dev)
+        given = batch["depths"][0].to(dev) if "depths" in batch else None
+        if self.pts_regressor is None or getattr(opt, "use_gt_depth", False):
+            if given is None:
+                raise ValueError("no depth regressor (or opt.use_gt_depth): the batch must carry the depth")
+            regressed_pts, pred_depth = given, given / 5 - 1
+        else:
+            inverse = bool(getattr(opt, "use_inverse_depth", False))
+            regressed_pts, pred_depth = train_glue.depth_head(self.pts_regressor(input_img), int(inverse), getattr(opt, "min_z", 0.0),
+                                                              getattr(opt, "max_z", 0.0), opt)
+        gen_fs, background_mask = self.pts_transformer.forward_justpts(self._features(input_img), regressed_pts, K, K_inv, input_RT,
+                                                                      input_RTinv, output_RT, output_RTinv)
+        autoreg_loss = None
+        if getattr(opt, "no_outpainting", False):
+            gen_img = gen_fs if self.projector is None else self.projector(gen_fs, None)
+        else:
+            if self.vqvae is None:
+                raise NotImplementedError("forward_train: a model without a VQ-VAE trains the PixelCNN with the reference's "
+                                          "mixture-of-logistics loss (discretized_mix_logistic_loss, z_buffermodel.py:364-368), which is "
+                                          "not built")
+            with torch.no_grad():
+                codes = self.vqvae.encode_codes(output_img)
+                input_gt = self.vqvae.decode_code(codes.to(torch.int64))
+            if not getattr(opt, "pretrain", False):
+                from .likelihood import ar_loss
+                with torch.no_grad():
+                    plan = self.get_masks_for_batch(output_RT, input_RTinv, background_mask, compact=True)
+                autoreg_loss = ar_loss(self, codes.reshape(-1, self.obs[1], self.obs[2]), plan, group="all")
+            if self.projector is None:
+                gen_img = self.get_combined(gen_fs, input_gt, background_mask)
+            elif getattr(opt, "predict_residual", False):
+                gen_img = self.projector(self.get_combined(gen_fs, input_gt, background_mask), background_mask)
+            else:
+                gen_img = self.projector(train_glue.combine_mask_nhwc(gen_fs, input_gt, background_mask, opt))
+        outputs = {"InputImg": input_img, "PredImg": gen_img, "PredDepthImg": pred_depth,
+                   "ForegroundImg": (~background_mask).repeat(input_img.shape[0], 1, 1, 1).float()}
+        loss = self.loss_function(gen_img, output_img)
+        if autoreg_loss is not None:
+            loss["autoreg_loss"] = autoreg_loss / (input_img.shape[0] * np.prod(self.obs) * np.log(2.)) * 1000
+            lam = getattr(opt, "lambda_autoreg", None)
+            loss["Total Loss"] += autoreg_loss if lam is None else autoreg_loss * lam      # (in place, as the reference: see the docstring)
+        if getattr(opt, "train_depth", False):
+            if given is None:
+                raise ValueError("forward_train: opt.train_depth needs the source view's depth, batch['depths'][0]")
+            depth_loss = nn.L1Loss()(regressed_pts, given)
+            loss["Total Loss"] += depth_loss
+            loss["depth_loss"] = depth_loss
+        outputs["OutputImg"] = output_img
+        return loss, outputs
+
     # ---------------------------------------------------------------- sample ranking (8f.3, host logic)
     def _entropy_score(self, gen_img):
         """Entropy of the scene classifier on the candidate, including the reference's reinterpretation of the
@@ -398,4 +484,6 @@ class ZbufferModelPts(OutpaintPipeline, SceneChain, nn.Module):
             return self.forward_scene(batch, netD)
         if self.opt.model_setting == 'get_gen_order':
             return self.forward_gen_order(batch)
+        if self.opt.model_setting == 'train':
+            return self.forward_train(batch)
         return self.forward_image(batch, netD)

@@ -70,3 +70,50 @@ def kernel_medians(events, names):
         if k is not None:
             times.setdefault(k, []).append(ms)
     return {k: round(float(np.median(v)), 4) for k, v in times.items()}
+
+
+def marked(fn, name):
+    """fn wrapped in a torch.profiler.record_function range `name`: what by_range sorts device events by"""
+    def wrapper(*a, **k):
+        with torch.profiler.record_function(name):
+            return fn(*a, **k)
+    return wrapper
+
+
+def range_of(ev, prefix):
+    """The nearest record_function range whose name begins with `prefix` around the CPU event `ev` (its name without the prefix), or None"""
+    while ev is not None:
+        if ev.name.startswith(prefix):
+            return ev.name[len(prefix):]
+        ev = ev.cpu_parent
+    return None
+
+
+def by_range(fn, calls, prefix):
+    """[(range, backward, kernel name, device ms)] of what `calls` calls of fn run on the device under torch's profiler.  range: the
+    marked range (marked(), names beginning with `prefix`) around the operation that launched the kernel; for a kernel of the backward
+    pass -- launched outside every range -- the range of the forward operation it differentiates, found through the profiler's sequence
+    numbers (backward True); None where neither gives one."""
+    from torch.profiler import ProfilerActivity, profile
+    with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
+        for _ in range(calls):
+            fn()
+        torch.cuda.synchronize()
+    events = [e for e in prof.events() if e.device_type == torch.autograd.DeviceType.CPU]
+    forward = {}            # sequence number of a forward operation -> its range
+    for e in events:
+        r = range_of(e, prefix)
+        if r is not None and getattr(e, "sequence_nr", -1) >= 0 and getattr(e, "scope", 0) == 0:
+            forward.setdefault(e.sequence_nr, r)
+    out = []
+    for e in events:
+        kernels = getattr(e, "kernels", None) or []
+        if not kernels:
+            continue
+        r, backward, up = range_of(e, prefix), False, e
+        while r is None and up is not None:
+            if getattr(up, "sequence_nr", -1) >= 0 and up.sequence_nr in forward and "Backward" in up.name:
+                r, backward = forward[up.sequence_nr], True
+            up = up.cpu_parent
+        out.extend((r, backward, k.name, k.duration / 1e3) for k in kernels)
+    return out
