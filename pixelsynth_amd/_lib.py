@@ -242,6 +242,16 @@ THIN_TRAIN_PROTOS = {
     "ps_thin_add_bias_f32": (RC, [c_void_p, c_void_p, c_size_t, c_int, STREAM]),
 }
 
+# libpixelsynth_disc_conv.so (include/pixelsynth_disc_conv.h): the discriminator's 4 x 4 convolution on the fp16 matrix pipe, forward and backward
+DISC_CONV_PROTOS = {
+    "ps_disc_conv_last_error": (ctypes.c_char_p, []),
+    "ps_disc_conv_takes": (c_int, [c_int] * 7),
+    "ps_disc_conv_workspace_bytes": (c_size_t, [c_int] * 7),
+    "ps_disc_conv_parts": (c_int, [c_int] * 7),
+    "ps_disc_conv_forward_f16x3": (RC, [c_void_p, c_void_p] + [c_int] * 7 + [c_void_p, c_void_p, c_void_p, c_size_t, STREAM]),
+    "ps_disc_conv_backward_f16x3": (RC, [c_void_p] * 3 + [c_int] * 7 + [c_void_p] * 6 + [c_size_t, STREAM]),
+}
+
 # libpixelsynth_gan_train.so (include/pixelsynth_gan_train.h): instance norm + LeakyReLU and the feature-matching L1 of the discriminator's
 # training pass.  maps, half_elems, weights and grads are host tables (ctypes arrays)
 GAN_TRAIN_PROTOS = {
@@ -280,7 +290,8 @@ PROTOS = {"hip": _PROTOS, "percsim": PERCSIM_PROTOS, "consistency": CONSISTENCY_
           "plan": PLAN_PROTOS, "rank": RANK_PROTOS, "rank_groups": RANK_GROUPS_PROTOS, "nll": NLL_PROTOS, "lmconv_bwd": LMCONV_BWD_PROTOS, "splat_bwd": SPLAT_BWD_PROTOS,
           "vq_train": VQ_TRAIN_PROTOS, "conv_bwd": CONV_BWD_PROTOS, "norm_train": NORM_TRAIN_PROTOS,
           "block_train": BLOCK_TRAIN_PROTOS, "content": CONTENT_PROTOS, "thin_train": THIN_TRAIN_PROTOS,
-          "pixelcnn_train": PIXELCNN_TRAIN_PROTOS, "train_glue": TRAIN_GLUE_PROTOS, "gan_train": GAN_TRAIN_PROTOS}
+          "pixelcnn_train": PIXELCNN_TRAIN_PROTOS, "train_glue": TRAIN_GLUE_PROTOS, "disc_conv": DISC_CONV_PROTOS,
+          "gan_train": GAN_TRAIN_PROTOS}
 _ENTRIES = {e.name: e for e in _libraries.LIBRARIES}
 assert set(PROTOS) == set(_ENTRIES)
 _OWNER = {fn: _ENTRIES[name] for name, table in PROTOS.items() for fn in table}

@@ -8,13 +8,15 @@ stay torch ops on MIOpen's convolutions -- this net scores a handful of candidat
 
 Training form, with opt.isTrain (what the reference's train options set; module.training alone does not select it): _SNConv in train()
 runs the hook's power iteration and keeps sigma in the graph, and under grad mode the InstanceNorm2d + LeakyReLU pairs of model1..3 go
-through gan_train.instance_norm_lrelu_train (csrc/gan_train.hip on the "hip" route).  The convolutions stay torch's."""
+through gan_train.instance_norm_lrelu_train (csrc/gan_train.hip on the "hip" route).  The convolutions are torch's, unless
+disc_conv.discriminator_conv_train("f16") (opt.discriminator_conv_train, PS_DISCRIMINATOR_CONV_TRAIN) sends the 4 x 4 convolutions of
+model1..3 through disc_conv.conv4x4_train (csrc/disc_conv.hip, the fp16 matrix pipe): with opt.isTrain, in grad mode, where it takes them."""
 import numpy as np
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import gan_train
+from . import disc_conv, gan_train
 
 
 class _SNConv(nn.Module):
@@ -47,7 +49,11 @@ class _SNConv(nn.Module):
         return self.weight_orig / sigma
 
     def forward(self, x):
-        return F.conv2d(x, self.weight(), None, self.stride, self.pad)
+        w = self.weight()
+        if (disc_conv.mode(self.opt) == "f16" and getattr(self.opt, "isTrain", False) and torch.is_grad_enabled()
+                and disc_conv.takes(x, w, self.stride, self.pad)):
+            return disc_conv.conv4x4_train(x, w, self.stride, self.opt)
+        return F.conv2d(x, w, None, self.stride, self.pad)
 
 
 class NLayerDiscriminator(nn.Module):

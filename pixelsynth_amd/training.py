@@ -7,6 +7,7 @@ import contextlib
 
 from .lmconv.train_ops import pixelcnn_train
 from .networks.block_train import decoder_block_train
+from .networks.disc_conv import discriminator_conv_train
 from .networks.f16x3 import decoder_conv_train
 from .networks.thin_train import decoder_thin_train
 from .networks.train_glue import train_glue
@@ -25,3 +26,12 @@ def hip_routes():
         for switch, value in HIP_ROUTES:
             stack.enter_context(switch(value))
         yield {switch.name: switch.forced() for switch, _ in HIP_ROUTES}
+
+
+@contextlib.contextmanager
+def hip_routes_with_discriminator():
+    """hip_routes() and, on top, discriminator_conv_train("f16"): the 4 x 4 convolutions of the discriminator's model1..3 through
+    networks/disc_conv.py as well -- exactly `with hip_routes(), discriminator_conv_train("f16"):`.  That switch is not one of HIP_ROUTES
+    (its default is "torch").  -> hip_routes()'s dict with the sixth switch added."""
+    with hip_routes() as forced, discriminator_conv_train("f16"):
+        yield dict(forced, **{discriminator_conv_train.name: discriminator_conv_train.forced()})

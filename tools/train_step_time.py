@@ -8,8 +8,9 @@ PixelCNN as the model builds it, the discriminator on, predict_residual off (so 
 reference's scripts set it, and forward_train then takes the torch blend: docstring there).  A call is one BaseModel step: forward, the
 generator's backward and Adam step, the discriminator's forward, backward and Adam step.
 
-Two routes alternate call by call between device events (_measure.alternate) on the same model and batch: "hip", the step under
-training.hip_routes() (every opt-in training kernel on), and "default", every switch where the process has it.  After the warm-up calls
+Three routes alternate call by call between device events (_measure.alternate) on the same model and batch: "hip", the step under
+training.hip_routes() (every opt-in training kernel on), "default", every switch where the process has it, and "hip+disc", the step
+under training.hip_routes_with_discriminator() (the discriminator's 4 x 4 convolutions through csrc/disc_conv.hip as well).  After the warm-up calls
 a round is CALLS calls per route and gives one median per route; the range of the ROUNDS medians is reported, with
 torch.cuda.max_memory_allocated of each route (the largest over its calls, reset before every call).  The yardstick for either number is the other, of the
 same tree in the same process; nothing else is claimed.
@@ -45,6 +46,7 @@ CONV_NAMES = ("conv", "Conv", "gemm", "Gemm", "GEMM", "Cijk", "igemm", "Igemm", 
 LMCONV_NAMES = ("k_gemm", "k_nchw_to_cl", "k_to_cl", "k_pack_conv", "k_reduce_nchw", "k_adjoint_mask", "k_grad_weight", "k_grad_bias")   # csrc/lmconv*.hip
 NORM_NAMES = ("norm", "Norm", "k_stats", "k_apply", "welford", "Welford")
 PREFIX = "ps_step::"
+ROUTES = {"hip": training.hip_routes, "default": contextlib.nullcontext, "hip+disc": training.hip_routes_with_discriminator}
 
 
 def refine(part, kernel):
@@ -141,21 +143,23 @@ def main(argv):
 
         def step(route):
             torch.cuda.reset_peak_memory_stats()      # (every call's peak is its own route's)
-            with training.hip_routes() if route == "hip" else contextlib.nullcontext():
+            with ROUTES[route]():
                 trainer(batch)
             peak[route] = max(peak.get(route, 0), torch.cuda.max_memory_allocated())
-        med = alternate({"hip": lambda: step("hip"), "default": lambda: step("default")}, args.rounds, args.calls, warm=2)
+        med = alternate({route: (lambda r=route: step(r)) for route in ROUTES}, args.rounds, args.calls, warm=2)
         classes = {}
-        for route in ("hip", "default"):
+        for route in ROUTES:
             totals, rest = by_class(lambda: step(route), args.profile_calls)
             classes[route] = dict(device_ms_per_call=totals, everything_else_top=rest, device_ms_total=round(sum(totals.values()), 3))
         rec = dict(what="train_step", pairs=B, ngf=args.ngf, ndf=args.ndf, unet=args.unet, rounds=args.rounds, calls=args.calls,
                    hip_ms_median_range=span(med["hip"]), default_ms_median_range=span(med["default"]),
+                   hip_disc_ms_median_range=span(med["hip+disc"]),
                    max_memory_allocated_mb={k: round(v / 2 ** 20, 1) for k, v in peak.items()}, classes=classes)
-        print("%d pairs: hip routes %.1f .. %.1f ms, default routes %.1f .. %.1f ms (medians of %d rounds of %d steps); peak memory %s MB"
-              % (B, *span(med["hip"]), *span(med["default"]), args.rounds, args.calls, rec["max_memory_allocated_mb"]))
+        print("%d pairs: hip routes %.1f .. %.1f ms, default routes %.1f .. %.1f ms, hip routes with the discriminator's convolutions %.1f .. %.1f ms "
+              "(medians of %d rounds of %d steps); peak memory %s MB"
+              % (B, *span(med["hip"]), *span(med["default"]), *span(med["hip+disc"]), args.rounds, args.calls, rec["max_memory_allocated_mb"]))
         for c in CLASSES:
-            print("  %-28s hip %9.3f ms   default %9.3f ms" % (c, classes["hip"]["device_ms_per_call"][c], classes["default"]["device_ms_per_call"][c]))
+            print("  %-28s hip %9.3f ms   default %9.3f ms   hip+disc %9.3f ms" % (c, *(classes[r]["device_ms_per_call"][c] for r in ROUTES)))
         print(json.dumps(rec), flush=True)
         del batch
         torch.cuda.empty_cache()
