@@ -32,7 +32,7 @@ ALL_SHAPES = SHAPES + BRANCH_SHAPES
 
 # ---- the plan (include/pixelsynth_disc_conv.h) ---------------------------------------------------------------------------------------------
 MAX_PARTS, TARGET_WGS, MIN_CHUNK = 256, 512, 8
-Plan = namedtuple("Plan", "Ho Wo Wo8 nch Q spf steps blocks chunk parts last straddle odd_tail pixel_groups")
+Plan = namedtuple("Plan", "Ho Wo Wo8 nch Q spf steps blocks chunk parts last straddle odd_tail pixel_groups launches")
 
 
 def plan(B, Ci, Co, H, W, stride, pad=PAD):
@@ -45,8 +45,70 @@ def plan(B, Ci, Co, H, W, stride, pad=PAD):
     blocks = (Co // 64) * (Ci // 32)
     chunk = max(MIN_CHUNK, -(-steps // min(MAX_PARTS, -(-TARGET_WGS // blocks))))
     ranges = [(t, min(t + chunk, steps)) for t in range(0, steps, chunk)]
+    # grad_x's launches, (Hm, Wm) each: the frame at stride 1, the four parities (py, px) of the input pixel at stride 2
+    launches = [(H, W)] if stride == 1 else [((H - py + 1) // 2, (W - px + 1) // 2) for py in range(2) for px in range(2)]
     return Plan(Ho, Wo, Wo8, nch, Q, spf, steps, blocks, chunk, len(ranges), ranges[-1][1] - ranges[-1][0],
-                [i for i, (lo, hi) in enumerate(ranges) if lo // spf != (hi - 1) // spf], Q % 2 == 1, -(-(Ho * Wo) // 256))
+                [i for i, (lo, hi) in enumerate(ranges) if lo // spf != (hi - 1) // spf], Q % 2 == 1, -(-(Ho * Wo) // 256), launches)
+
+
+# ---- the route cases (test_disc_routes_cpu.py asserts each reaches its branches and no shape of ALL_SHAPES does; test_disc_routes_gpu.py
+# runs them) --------------------------------------------------------------------------------------------------------------------------------
+# name -> predicate over (shape, plan(*shape)), each the kernel's own line restated
+BRANCHES = {
+    # make_plan: `if (want > PS_DISC_CONV_MAX_PARTS) want = PS_DISC_CONV_MAX_PARTS` decides, and k_disc_conv_gw_sum adds 256 parts
+    "parts-cap": lambda s, p: p.parts == MAX_PARTS,
+    # the workload's plan in small: steps per part from ceil(steps / want) above the 8 and 9 of the operator shapes, over a hundred parts
+    # for k_disc_conv_gw_sum, a shorter last part, parts in two frames, the product's grid of many pixel workgroups
+    "workload-plan": lambda s, p: p.chunk >= 10 and p.parts > 100 and 1 < p.last < p.chunk and len(p.straddle) >= 3 and p.pixel_groups > 16,
+    # k_disc_conv_gw_parts: `st1 = min(st0 + a.chunk, a.steps)` leaves the last of several parts one step
+    "one-step-part": lambda s, p: p.parts > 1 and p.last == 1,
+    # k_disc_conv_mfma: Cin / 16 = 32 channel steps per tap; k_disc_conv_gw_parts: ncib = 16; k_disc_conv_pack: n_in = 512 (forward)
+    "ci-512": lambda s, p: s[1] == 512,
+    # k_disc_conv_rows: `if (jj < Wo && ...)` holds for every j of every chunk: no row has a zero tail
+    "wo-mult-8": lambda s, p: p.Wo % 8 == 0,
+    # ... and for one j of a row's last chunk: seven zeros behind one value.  At stride 2 the operator shape (2, 128, 256, 17, 17, 2) has
+    # Wo = 9 already (x = 2 jj + kx - 2 of k_disc_conv_rows); what no test runs is that row at stride 1, where the last chunk's one value
+    # reads x[W - 2 + kx], past the frame for kx >= 2
+    "wo-one-over": lambda s, p: p.Wo % 8 == 1 and s[5] == 1,
+    # launch_conv: `if (a.Hm <= 0 || a.Wm <= 0) return PS_OK`
+    "empty-parity": lambda s, p: any(hm <= 0 or wm <= 0 for hm, wm in p.launches),
+    # ps_disc_conv_backward_f16x3: the launches of py = 1 write the rows 1, 3 .. H - 1: the frame's last row belongs to them
+    "even-h-stride-2": lambda s, p: s[5] == 2 and s[3] % 2 == 0,
+}
+# (B, Ci, Co, H, W, stride) -> the branches the case is there for
+ROUTES = {
+    (16, 64, 64, 47, 41, 1): ("parts-cap",),                     # 2304 steps, 9 per part, exactly 256 parts
+    (4, 64, 128, 129, 129, 2): ("workload-plan",),               # 118 parts of 10, the last of 2, parts 29 / 58 / 87 in two frames, 17 pixel
+                                                                 # workgroups, parity launches of 65 and 64 rows
+    (1, 64, 64, 16, 5, 1): ("one-step-part",),                   # 9 steps, 2 parts, the last of one step, a zero chunk behind the frame
+    (1, 512, 64, 5, 5, 1): ("ci-512",),
+    (1, 512, 512, 3, 3, 2): ("ci-512",),
+    (2, 512, 128, 9, 10, 1): ("ci-512",),                        # ... with 3 parts, one in two frames
+    (2, 64, 64, 6, 7, 1): ("wo-mult-8",),                        # Wo = 8 at stride 1
+    (1, 64, 64, 9, 15, 2): ("wo-mult-8",),                       # Wo = 8 at stride 2
+    (1, 64, 64, 3, 8, 1): ("wo-one-over",),                      # Wo = 9, Wo8 = 16
+    (2, 64, 64, 1, 1, 2): ("empty-parity",),                     # three of the four launches are empty
+    (1, 64, 64, 1, 6, 2): ("empty-parity",),
+    (1, 64, 64, 4, 1, 2): ("empty-parity", "even-h-stride-2"),
+    (1, 64, 64, 4, 6, 2): ("even-h-stride-2",),
+    (1, 64, 64, 2, 2, 2): ("even-h-stride-2",),
+}
+ROUTE_SHAPES = list(ROUTES)
+ABI_SHAPES = [(16, 64, 64, 47, 41, 1), (1, 512, 512, 3, 3, 2), (1, 64, 64, 3, 8, 1), (2, 64, 64, 1, 1, 2)]      # through the C ABI inside rims
+TINY_SHAPE, TINY_EXPONENTS = (2, 64, 64, 5, 7, 2), (8, 16, -115)       # the gradient under the held exponent: x 2^8, w 2^16, g 2^-115
+
+
+def workspace_bytes(B, Ci, Co, H, W, stride, pad=PAD):
+    """make_plan's regions in their order, each rounded up to 256 bytes -> (bytes, the offset of the parts, the bytes of the parts)"""
+    p = plan(B, Ci, Co, H, W, stride, pad)
+    Hp, Wp = H + 2 * pad, W + 2 * pad
+    halves = [16 * Co * Ci, B * Hp * Wp * Ci, B * (p.Ho + 2) * (p.Wo + 2) * Co, B * Co * p.Ho * p.Wo8, 4 * B * Ci * Hp * p.Wo8]
+    part = p.parts * 16 * Co * Ci * 4
+    regions = [256 * 4, 2 * 4] + [4 * n for n in halves] + [part]
+    at = 0
+    for n in regions[:-1]:
+        at += -(-n // 256) * 256
+    return at + -(-part // 256) * 256, at, part
 
 
 # ---- the formulas --------------------------------------------------------------------------------------------------------------------------
@@ -134,6 +196,22 @@ def integers(shape):
     y = conv(leaves[0], leaves[1], stride)
     gx, gw = torch.autograd.grad(y, leaves, g.double())
     return x, w, g, y.detach().float(), gx.float(), gw.float()
+
+
+def scaled_integers(shape, ex, ew, eg):
+    """integers(shape) with x times 2^ex, w times 2^ew, g times 2^eg: powers of two, so every operand and the fp64 results times
+    2^(ex + ew), 2^(ew + eg), 2^(ex + eg) are the exact ones -> the same six tensors as fp32.  Asserts what the comparison bit for bit
+    rests on: each fp64 value survives the way through fp32, and none of them is a subnormal fp32."""
+    x, w, g, y, gx, gw = integers(shape)
+    d, tiny = torch.double, torch.finfo(torch.float32).tiny
+    out = []
+    for t, e in ((x, ex), (w, ew), (g, eg), (y, ex + ew), (gx, ew + eg), (gw, ex + eg)):
+        t64 = t.to(d) * 2.0 ** e
+        t32 = t64.float()
+        assert torch.equal(t32.to(d), t64) and torch.equal(t32.to(d) * 2.0 ** -e, t.to(d)), e
+        assert t32.any() and (t64[t64 != 0].abs() >= tiny).all() and torch.isfinite(t32).all(), e
+        out.append(t32)
+    return tuple(out)
 
 
 def inputs(shape, seed=1, g_scale=1.0):

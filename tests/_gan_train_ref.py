@@ -46,6 +46,31 @@ def form(hw):
     return "stream", 0
 
 
+# The boundaries of values_per_thread that the operator cases of tests/test_gan_train_gpu.py leave on both sides: hw | hw + 1 are two
+# forms.  Both sides of each are a route case (test_disc_routes_cpu.py, test_disc_routes_gpu.py): five planes up to 1793 values, so that
+# the wave form's last workgroup has one wavefront at work, two planes above.  They reach k_norm_fwd / k_norm_bwd <64, NV> at
+# NV = 12, 16, 24, 28 and <256, NV> at NV = 24, 28, the six instantiations no other test launches, twice each.
+NORM_ROUTE_BOUNDARIES = [512, 768, 1024, 1280, 1536, 1792, 4096, 5120, 6144, 7168]
+NORM_ROUTE_CASES = [(1, 5 if hw <= 1793 else 2, 1, hw) for b in NORM_ROUTE_BOUNDARIES for hw in (b, b + 1)]
+NORM_ROUTE_FORMS = [("wave", 12), ("wave", 16), ("wave", 24), ("wave", 28), ("workgroup", 24), ("workgroup", 28)]
+# k_feat_finish stages the tiles of a map 256 at a time: a map of more than 256 tiles takes a second trip round the reused `stage`.
+# "staged": 258 tiles (a full trip, a trip of 2, a ragged last tile), then maps whose first tiles are at no multiple of 256;
+# "staged-exact": two full trips
+FEAT_STAGE = 256
+FEAT_ROUTE_LISTS = {"staged": [(2, 257 * TILE + 3), (2, 5), (2, TILE)], "staged-exact": [(2, 512 * TILE)]}
+
+
+def feat_tiles(shapes):
+    """Tiles per map of a list of map shapes (2P, ...): ceil(values per half / TILE)"""
+    out = []
+    for s in shapes:
+        n = 1
+        for v in s:
+            n *= v
+        out.append(-(-(n // 2) // TILE))
+    return out
+
+
 def norm_inputs(shape, seed=0):
     """x = 0.3 + 1.5 randn and dy = randn, as the tests draw them"""
     gen = torch.Generator().manual_seed(seed)

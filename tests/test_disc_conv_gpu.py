@@ -45,23 +45,29 @@ def _flags():
 
 
 # ---------------------------------------------------------------- the index walk, bit for bit
-@pytest.mark.parametrize("shape", ref.ALL_SHAPES, ids=str)
-def test_integers_bit_for_bit(shape):
-    x, w, g, y64, gx64, gw64 = ref.integers(shape)
+def integers_bit_for_bit(shape, run=_run, operands=None):
+    """The body of test_integers_bit_for_bit (tests/test_disc_routes_gpu.py runs its cases through it too, with a `run` of its own: the
+    entry points with their outputs inside rims; and with `operands`, the six tensors of ref.integers times powers of two)"""
+    x, w, g, y64, gx64, gw64 = operands or ref.integers(shape)
     _clear()
-    y, gx, gw = _run(x, w, g, shape[5])
+    y, gx, gw = run(x, w, g, shape[5])
     assert tuple(y.shape) == ref.out_shape(*shape)
     assert torch.equal(y.cpu(), y64), f"y: {(y.cpu() != y64).sum().item()} of {y64.numel()} differ"
     assert torch.equal(gx.cpu(), gx64), f"grad_x: {(gx.cpu() != gx64).sum().item()} of {gx64.numel()} differ"
     assert torch.equal(gw.cpu(), gw64), f"grad_weight: {(gw.cpu() != gw64).sum().item()} of {gw64.numel()} differ"
     assert _flags() == (0, 0)
     # every output twice: the same bits; and each gradient alone (needs_input_grad) is the same gradient
-    y2, gx2, gw2 = _run(x, w, g, shape[5])
+    y2, gx2, gw2 = run(x, w, g, shape[5])
     assert torch.equal(y, y2) and torch.equal(gx, gx2) and torch.equal(gw, gw2)
-    _, gx3, none = _run(x, w, g, shape[5], need=(True, False))
+    _, gx3, none = run(x, w, g, shape[5], need=(True, False))
     assert none is None and torch.equal(gx3, gx)
-    _, none, gw3 = _run(x, w, g, shape[5], need=(False, True))
+    _, none, gw3 = run(x, w, g, shape[5], need=(False, True))
     assert none is None and torch.equal(gw3, gw)
+
+
+@pytest.mark.parametrize("shape", ref.ALL_SHAPES, ids=str)
+def test_integers_bit_for_bit(shape):
+    integers_bit_for_bit(shape)
 
 
 # ---------------------------------------------------------------- accuracy
@@ -71,17 +77,22 @@ def _reference(shape, small):
     return x, w, g, ref.reference(x, w, g, shape[5])
 
 
-@pytest.mark.parametrize("shape", ref.SHAPES, ids=str)
-def test_accuracy_under_both_rules(shape):
+def accuracy_under_both_rules(shape, run=_run):
+    """The body of test_accuracy_under_both_rules (tests/test_disc_routes_gpu.py runs its cases through it too)"""
     x, w, g, r = _reference(shape, False)
     _clear()
-    y, gx, gw = _run(x, w, g, shape[5])
+    y, gx, gw = run(x, w, g, shape[5])
     ref.check(f"{shape} y", y, r.y)
     ref.check(f"{shape} grad_x", gx, r.x)
     ref.check(f"{shape} grad_weight", gw, r.weight)
     assert _flags() == (0, 0)
-    y2, gx2, gw2 = _run(x, w, g, shape[5])
+    y2, gx2, gw2 = run(x, w, g, shape[5])
     assert torch.equal(y, y2) and torch.equal(gx, gx2) and torch.equal(gw, gw2)
+
+
+@pytest.mark.parametrize("shape", ref.SHAPES, ids=str)
+def test_accuracy_under_both_rules(shape):
+    accuracy_under_both_rules(shape)
 
 
 @pytest.mark.parametrize("shape", [ref.SHAPES[3], ref.SHAPES[4]], ids=str)

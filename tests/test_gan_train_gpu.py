@@ -48,12 +48,12 @@ def _norm(x, dy=None):
     return [t.cpu() for t in out]
 
 
-@pytest.mark.parametrize("shape", CASES, ids=lambda s: "x".join(map(str, s)))
-def test_norm_forward_and_backward_against_fp64(shape):
+def norm_against_fp64(shape, norm=_norm):
+    """The body of test_norm_forward_and_backward_against_fp64 (tests/test_disc_routes_gpu.py runs its cases through it too, and gives a
+    `norm` of its own: the entry points with their outputs inside rims)"""
     hw = shape[2] * shape[3]
-    assert FORMS.get(shape, ref.form(hw)) == ref.form(hw)
     x, dy = ref.norm_inputs(shape, seed=sum(shape))
-    y, mean, rstd, dx = _norm(x, dy)
+    y, mean, rstd, dx = norm(x, dy)
     f = ref.norm_forward64(x, EPS, SLOPE)
     mean_b, rstd_b, _ = ref.stat_bounds(f, EPS)
     assert ref.check("mean", mean, f["mean"], mean_b) <= 1.0
@@ -72,6 +72,13 @@ def test_norm_forward_and_backward_against_fp64(shape):
     assert torch.equal(out.detach().cpu(), y) and torch.equal(xg.grad.cpu(), dx)
     with torch.no_grad():
         assert torch.equal(GT.instance_norm_lrelu_train(x.to(DEV), EPS, SLOPE).cpu(), y)
+
+
+@pytest.mark.parametrize("shape", CASES, ids=lambda s: "x".join(map(str, s)))
+def test_norm_forward_and_backward_against_fp64(shape):
+    hw = shape[2] * shape[3]
+    assert FORMS.get(shape, ref.form(hw)) == ref.form(hw)
+    norm_against_fp64(shape)
 
 
 def test_an_ill_conditioned_plane():
@@ -122,7 +129,12 @@ def _int_bits(t):
 
 @pytest.mark.parametrize("name", list(MAP_LISTS))
 def test_feature_matching_values_and_gradients(name):
-    shapes = MAP_LISTS[name]
+    feature_matching_against_fp64(name, MAP_LISTS[name])
+
+
+def feature_matching_against_fp64(name, shapes):
+    """The body of test_feature_matching_values_and_gradients (tests/test_disc_routes_gpu.py runs its lists through it too) -> the
+    maps, per_map and the total of the first run, on the host"""
     maps = ref.feat_maps(shapes, seed=len(shapes))
     w, gt = 5.0, 0.75
     leaves = [m.to(DEV).requires_grad_() for m in maps]
@@ -155,6 +167,7 @@ def test_feature_matching_values_and_gradients(name):
         assert torch.equal(t2, total.detach()) and torch.equal(p2, per_map)
         _, p_last = GT.feature_matching([maps[-1].to(DEV)], w, per_map=True)
         assert torch.equal(p_last[0], per_map[-1])
+    return maps, per_map.cpu(), total.detach().cpu()
 
 
 def test_feature_matching_keeps_a_nan_in_its_map():

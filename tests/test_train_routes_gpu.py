@@ -140,17 +140,7 @@ def test_norm_of_a_single_value():
 
 
 # ---- the 1 x 1 convolution's weight and bias gradient ---------------------------------------------------------------------------------------------
-GUARD, SENTINEL = 64, 12345.0          # floats in front of and behind each output (256 bytes: the outputs stay aligned)
-
-
-def _guarded(n):
-    buf = torch.full((GUARD + n + GUARD,), SENTINEL, device=DEV)
-    buf[GUARD:GUARD + n] = NAN
-    return buf, buf[GUARD:GUARD + n]
-
-
-def _untouched(buf, n):
-    return bool((buf[:GUARD] == SENTINEL).all() and (buf[GUARD + n:] == SENTINEL).all())
+from _rims import GUARD, SENTINEL, guarded as _guarded, untouched as _untouched  # noqa: E402,F401  (the route tests take them from here)
 
 
 def _gw_reference(shape):
