@@ -252,6 +252,17 @@ DISC_CONV_PROTOS = {
     "ps_disc_conv_backward_f16x3": (RC, [c_void_p] * 3 + [c_int] * 7 + [c_void_p] * 6 + [c_size_t, STREAM]),
 }
 
+# libpixelsynth_spectral_train.so (include/pixelsynth_spectral_train.h): the spectral normalisation of a table of layers in training,
+# forward and backward.  The tables of ps_spectral_plan and grads are host arrays (ctypes arrays); table / table_host are host images
+SPECTRAL_TRAIN_PROTOS = {
+    "ps_spectral_train_last_error": (ctypes.c_char_p, []),
+    "ps_spectral_table_bytes": (c_size_t, []),
+    "ps_spectral_plan": (RC, [c_void_p] * 8 + [c_int, c_void_p, c_size_t] + [c_void_p] * 3),
+    "ps_spectral_workspace_bytes": (c_size_t, [c_void_p]),
+    "ps_spectral_forward_f32": (RC, [c_void_p] * 7 + [c_size_t, STREAM]),
+    "ps_spectral_backward_f32": (RC, [c_void_p] * 9 + [c_size_t, STREAM]),
+}
+
 # libpixelsynth_gan_train.so (include/pixelsynth_gan_train.h): instance norm + LeakyReLU and the feature-matching L1 of the discriminator's
 # training pass.  maps, half_elems, weights and grads are host tables (ctypes arrays)
 GAN_TRAIN_PROTOS = {
@@ -290,8 +301,8 @@ PROTOS = {"hip": _PROTOS, "percsim": PERCSIM_PROTOS, "consistency": CONSISTENCY_
           "plan": PLAN_PROTOS, "rank": RANK_PROTOS, "rank_groups": RANK_GROUPS_PROTOS, "nll": NLL_PROTOS, "lmconv_bwd": LMCONV_BWD_PROTOS, "splat_bwd": SPLAT_BWD_PROTOS,
           "vq_train": VQ_TRAIN_PROTOS, "conv_bwd": CONV_BWD_PROTOS, "norm_train": NORM_TRAIN_PROTOS,
           "block_train": BLOCK_TRAIN_PROTOS, "content": CONTENT_PROTOS, "thin_train": THIN_TRAIN_PROTOS,
-          "pixelcnn_train": PIXELCNN_TRAIN_PROTOS, "train_glue": TRAIN_GLUE_PROTOS, "disc_conv": DISC_CONV_PROTOS,
-          "gan_train": GAN_TRAIN_PROTOS}
+          "pixelcnn_train": PIXELCNN_TRAIN_PROTOS, "train_glue": TRAIN_GLUE_PROTOS, "spectral_train": SPECTRAL_TRAIN_PROTOS,
+          "disc_conv": DISC_CONV_PROTOS, "gan_train": GAN_TRAIN_PROTOS}
 _ENTRIES = {e.name: e for e in _libraries.LIBRARIES}
 assert set(PROTOS) == set(_ENTRIES)
 _OWNER = {fn: _ENTRIES[name] for name, table in PROTOS.items() for fn in table}

@@ -34,7 +34,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import _lib
-from . import conv_routes, norm_train
+from . import conv_routes, norm_train, spectral_train
 from .block_train import decoder_block_train  # noqa: F401
 from .norm_train import decoder_norm_train  # noqa: F401
 from .thin_train import decoder_thin_train  # noqa: F401
@@ -44,7 +44,7 @@ from .f16x3 import check_f16x3_overflow, decoder_conv, decoder_conv_train  # noq
 from .conv_routes import (_conv2d_batches, _conv_mode, _conv_split, _f16x3_conv, _f16x3_takes, _f16x3_train_conv,  # noqa: F401
                           _normalised_weight, _overflow_flag, _plain_conv_weight, _resample, _resample_sum, _sn_hooks, _sn_linear,
                           _thin_conv, conv1x1, plain_conv)
-from .routing import empty_nhwc, gpu_f32, per_sample
+from .routing import empty_nhwc, gpu_f32, has_pending, per_sample
 from .vgg19 import VGG19  # noqa: F401  (the content loss's network, where the reference keeps it)
 
 NOISE_SZ = 20
@@ -348,6 +348,9 @@ class ResNetDecoder(nn.Module):
         else:
             h = x if background_mask is None else torch.cat((x, (~background_mask).unsqueeze(1).float()), 1)
             h = _nhwc(self, h)
+        if h.is_cuda and spectral_train.active(self, self.opt):
+            # the 22 convolutions and 32 noise linears in one batched pass; each takes its weight where it asks for it (_normalised_weight)
+            spectral_train.normalise(spectral_train.sn_modules(self), self.opt)
         if noise is None and h.is_cuda:
             # the reference draws each layer's noise on the host and sends it over (normalization.py:36-37): sixteen small blocking
             # copies per pass.  The same sixteen draws, in the same order from the same generator, in ONE copy.
@@ -397,8 +400,9 @@ class Unet(nn.Module):
     @staticmethod
     def _conv(conv, x):
         """conv(x); in eval mode without autograd with the spectral-normalised weight computed once per checkpoint (_normalised_weight)
-        instead of at every forward -- torch's hook costs five small launches per layer, a fifth of this network's time at 8 images."""
-        if x.is_cuda and not torch.is_grad_enabled() and not conv.training:
+        instead of at every forward -- torch's hook costs five small launches per layer, a fifth of this network's time at 8 images; and
+        with the weight spectral_train.normalise left pending at the top of forward() instead of the hook's."""
+        if has_pending(conv) or (x.is_cuda and not torch.is_grad_enabled() and not conv.training):
             weight = _plain_conv_weight(conv, x)
             if weight is not None:
                 return F.conv2d(x, weight, conv.bias, conv.stride, conv.padding, conv.dilation, conv.groups)
@@ -410,6 +414,8 @@ class Unet(nn.Module):
             if input.size(0) > n:
                 return torch.cat([self.forward(input[i:i + n]) for i in range(0, input.size(0), n)])
         skips, h = [], _nhwc(self, input)
+        if h.is_cuda and spectral_train.active(self):      # (this network keeps no options: the switch's block, or PS_SPECTRAL_TRAIN)
+            spectral_train.normalise(spectral_train.sn_modules(self))
         for i in range(8):
             h = self._conv(getattr(self, f"conv{i + 1}"), h if i == 0 else F.leaky_relu(h, 0.2))
             if self._ENC_NORM[i]:

@@ -12,7 +12,7 @@ from torch.nn.utils.spectral_norm import SpectralNorm
 from .. import _lib
 from . import block_train, f16x3, thin_train
 from .f16x3 import flag as _overflow_flag  # noqa: F401  (architectures.py hands it on)
-from .routing import cached, empty_nhwc, gpu_f32
+from .routing import cached, empty_nhwc, gpu_f32, has_pending, take_pending
 
 _conv_mode = f16x3.decoder_conv.resolve      # which convolutions a decoder block takes: "f16x3" | "fp32" (everything through torch / MIOpen)
 
@@ -49,7 +49,9 @@ def _normalised_weight(mod, pre, x):
     """mod.weight as mod's spectral-norm pre-hooks leave it.  In eval mode the hook does no power iteration -- weight_orig / sigma with
     sigma from the stored u, v is a constant of the checkpoint, yet torch recomputes it at every forward (a matrix-vector product, a
     dot and a division: ~270 launches of a few microseconds per decoder pass, a tenth of its time once the convolutions are
-    fast).  Here it is computed once and kept until weight_orig / u / v change (their storage or version counters)."""
+    fast).  Here it is computed once and kept until weight_orig / u / v change (their storage or version counters).  In train() or grad
+    mode: the weight spectral_train.normalise left pending on `mod`, taken once and assigned to mod.weight as the hook would; with
+    nothing pending, the hook."""
     if not pre:
         return mod.weight
 
@@ -58,7 +60,11 @@ def _normalised_weight(mod, pre, x):
             hook(mod, (x,))
         return mod.weight
     if mod.training or torch.is_grad_enabled():
-        return hooked()
+        weight = take_pending(mod)
+        if weight is None:
+            return hooked()
+        mod.weight = weight
+        return weight
     return cached(mod, "_ps_sn_cache", (mod.weight_orig, mod.weight_u, mod.weight_v), lambda: hooked().detach())
 
 
@@ -125,6 +131,11 @@ def _conv_split(conv, x, mode=None, opt=None):
     y = _thin_train_conv(conv, x, opt)
     if y is not None:
         return y, None
+    if has_pending(conv):       # (its normalised weight is there already: conv(x) would run the hook's power iteration a second time)
+        weight = _plain_conv_weight(conv, x)
+        if weight is not None:
+            return _conv2d_batches(lambda t: F.conv2d(t, weight, conv.bias, conv.stride, conv.padding, conv.dilation, conv.groups), x,
+                                   conv.out_channels, conv.stride[0]), None
     if conv.bias is None or torch.is_grad_enabled() or not gpu_f32(x, multiple=4) or conv.out_channels % 4:
         return _conv2d_batches(conv, x, conv.out_channels, conv.stride[0]), None
     weight = _plain_conv_weight(conv, x)

@@ -10,13 +10,16 @@ Training form, with opt.isTrain (what the reference's train options set; module.
 runs the hook's power iteration and keeps sigma in the graph, and under grad mode the InstanceNorm2d + LeakyReLU pairs of model1..3 go
 through gan_train.instance_norm_lrelu_train (csrc/gan_train.hip on the "hip" route).  The convolutions are torch's, unless
 disc_conv.discriminator_conv_train("f16") (opt.discriminator_conv_train, PS_DISCRIMINATOR_CONV_TRAIN) sends the 4 x 4 convolutions of
-model1..3 through disc_conv.conv4x4_train (csrc/disc_conv.hip, the fp16 matrix pipe): with opt.isTrain, in grad mode, where it takes them."""
+model1..3 through disc_conv.conv4x4_train (csrc/disc_conv.hip, the fp16 matrix pipe): with opt.isTrain, in grad mode, where it takes them.
+Under spectral_train("hip") (opt.spectral_train, PS_SPECTRAL_TRAIN) MultiscaleDiscriminator.forward normalises its six _SNConvs in one
+batched pass (networks/spectral_train.py) and _SNConv.weight() takes what that left pending."""
 import numpy as np
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import disc_conv, gan_train
+from . import disc_conv, gan_train, spectral_train
+from .routing import take_pending
 
 
 class _SNConv(nn.Module):
@@ -36,6 +39,9 @@ class _SNConv(nn.Module):
             self.weight_v.copy_(F.normalize(torch.randn(cin * k * k), dim=0))
 
     def weight(self):
+        pending = take_pending(self)        # (spectral_train.normalise at the top of MultiscaleDiscriminator.forward, taken once)
+        if pending is not None:
+            return pending
         wm = self.weight_orig.reshape(self.weight_orig.size(0), -1)
         if self.training and getattr(self.opt, "isTrain", False):
             # torch.nn.utils.spectral_norm in training: one power iteration on the stored vectors, in place and outside the graph;
@@ -104,6 +110,8 @@ class MultiscaleDiscriminator(nn.Module):
         return F.avg_pool2d(input, kernel_size=3, stride=2, padding=[1, 1], count_include_pad=False)
 
     def forward(self, input):
+        if spectral_train.active(self, self.opt):       # both scales' _SNConvs in one batched pass
+            spectral_train.normalise(spectral_train.sn_modules(self), self.opt)
         result = []
         for _, D in self.named_children():
             out = D(input)

@@ -69,6 +69,31 @@ def cached(mod, slot, sources, make):
     return entry[1]
 
 
+PENDING = "_ps_sn_pending"    # mod.__dict__ slot of a spectral-normalised weight computed ahead of the module's call (spectral_train.py)
+
+
+def _sn_versions(mod):
+    return tuple((t.data_ptr(), t._version) for t in (mod.weight_orig, mod.weight_u, mod.weight_v))
+
+
+def leave_pending(mod, weight):
+    """Leave `weight` -- weight_orig / sigma as the batched pass computed it -- for the module's next request of its weight"""
+    mod.__dict__[PENDING] = (weight, _sn_versions(mod))
+
+
+def has_pending(mod):
+    return PENDING in mod.__dict__
+
+
+def take_pending(mod):
+    """The weight left pending on `mod`, once: it is removed.  None where nothing is pending, or where weight_orig / u / v were replaced
+    or written to since (an optimiser step, the hook itself): a weight of another state is dropped, not used."""
+    entry = mod.__dict__.pop(PENDING, None)
+    if entry is None or entry[1] != _sn_versions(mod):
+        return None
+    return entry[0]
+
+
 def gpu_f32(t, layout=torch.channels_last, multiple=1, aligned=False, dims=4):
     """Whether `t` is a tensor the kernels take by raw pointer: on the GPU, fp32, of `dims` dimensions (None: any), dense in `layout`
     (None: any storage), size(1) a multiple of `multiple`, and, where `aligned`, at an address that is a multiple of 16 bytes.  The

@@ -9,6 +9,7 @@ from .lmconv.train_ops import pixelcnn_train
 from .networks.block_train import decoder_block_train
 from .networks.disc_conv import discriminator_conv_train
 from .networks.f16x3 import decoder_conv_train
+from .networks.spectral_train import spectral_train
 from .networks.thin_train import decoder_thin_train
 from .networks.train_glue import train_glue
 
@@ -35,3 +36,12 @@ def hip_routes_with_discriminator():
     (its default is "torch").  -> hip_routes()'s dict with the sixth switch added."""
     with hip_routes() as forced, discriminator_conv_train("f16"):
         yield dict(forced, **{discriminator_conv_train.name: discriminator_conv_train.forced()})
+
+
+@contextlib.contextmanager
+def hip_routes_with_spectral(discriminator=False):
+    """hip_routes() -- or, with `discriminator`, hip_routes_with_discriminator() -- and, on top, spectral_train("hip"): the spectral
+    normalisation of the decoder's, the Unet's and the discriminator's layers as one batched pass per forward (networks/spectral_train.py).
+    That switch is not one of HIP_ROUTES either (its default is "torch").  -> the inner context's dict with this switch added."""
+    with (hip_routes_with_discriminator() if discriminator else hip_routes()) as forced, spectral_train("hip"):
+        yield dict(forced, **{spectral_train.name: spectral_train.forced()})

@@ -8,9 +8,11 @@ PixelCNN as the model builds it, the discriminator on, predict_residual off (so 
 reference's scripts set it, and forward_train then takes the torch blend: docstring there).  A call is one BaseModel step: forward, the
 generator's backward and Adam step, the discriminator's forward, backward and Adam step.
 
-Three routes alternate call by call between device events (_measure.alternate) on the same model and batch: "hip", the step under
-training.hip_routes() (every opt-in training kernel on), "default", every switch where the process has it, and "hip+disc", the step
-under training.hip_routes_with_discriminator() (the discriminator's 4 x 4 convolutions through csrc/disc_conv.hip as well).  After the warm-up calls
+Four routes alternate call by call between device events (_measure.alternate) on the same model and batch: "hip", the step under
+training.hip_routes() (every opt-in training kernel on), "default", every switch where the process has it, "hip+disc", the step
+under training.hip_routes_with_discriminator() (the discriminator's 4 x 4 convolutions through csrc/disc_conv.hip as well), and "hip+sn",
+the step under training.hip_routes_with_spectral() (the spectral normalisation of the decoder's, the Unet's and the discriminator's layers
+as one batched pass per forward, csrc/spectral_train.hip).  After the warm-up calls
 a round is CALLS calls per route and gives one median per route; the range of the ROUNDS medians is reported, with
 torch.cuda.max_memory_allocated of each route (the largest over its calls, reset before every call).  The yardstick for either number is the other, of the
 same tree in the same process; nothing else is claimed.
@@ -19,8 +21,8 @@ Then each route once more under torch's profiler, in a run of its own (_measure'
 calls): device time by CLASS (_measure.by_range).  A kernel belongs to the class of the part of the step that launched it -- the parts are
 marked with torch.profiler.record_function ranges around the modules' forwards and the optimisers' steps, a backward kernel goes to the class
 of the forward operation it differentiates (the profiler's sequence numbers) -- refined by the kernel's name where a part holds several
-classes (the PixelCNN: masked convolutions against the rest; the decoder: convolutions, norms, joins) and for the new glue kernels,
-which are found by name wherever they run.  What no rule reaches is "everything else"; its largest names are listed.  One JSON line
+classes (the PixelCNN: masked convolutions against the rest; the decoder: convolutions, norms, joins) and for the new glue kernels
+and the k_sn_* kernels of the batched spectral norm ("spectral norm"), which are found by name wherever they run.  What no rule reaches is "everything else"; its largest names are listed.  One JSON line
 per batch size."""
 import argparse
 import contextlib
@@ -39,20 +41,24 @@ from _measure import alternate, by_range, marked as _marked, span  # noqa: E402
 
 CLASSES = ("Unet", "splat forward", "splat backward", "planning", "VQ-VAE", "masked convolutions", "PixelCNN kernels",
            "decoder convolutions", "decoder norms", "decoder joins", "content loss", "discriminator convolutions", "discriminator rest",
-           "glue kernels", "optimisers", "everything else")
+           "glue kernels", "spectral norm", "optimisers", "everything else")
 GLUE = ("k_combine_fwd", "k_combine_bwd", "k_depth_fwd", "k_depth_bwd")
+SPECTRAL = ("k_sn_wtu", "k_sn_wv", "k_sn_v", "k_sn_u", "k_sn_div", "k_sn_dot", "k_sn_dw")      # csrc/spectral_train.hip
 CONV_NAMES = ("conv", "Conv", "gemm", "Gemm", "GEMM", "Cijk", "igemm", "Igemm", "miopen", "MIOpen", "naive_", "gridwise", "col2im", "im2col",
               "Im2Col", "Col2Im", "wrw", "bwd_data", "xdlops", "SubTensorOp", "batched_transpose", "transpose_", "k_thin", "k_f16x3", "k_wgrad")
 LMCONV_NAMES = ("k_gemm", "k_nchw_to_cl", "k_to_cl", "k_pack_conv", "k_reduce_nchw", "k_adjoint_mask", "k_grad_weight", "k_grad_bias")   # csrc/lmconv*.hip
 NORM_NAMES = ("norm", "Norm", "k_stats", "k_apply", "welford", "Welford")
 PREFIX = "ps_step::"
 ROUTES = {"hip": training.hip_routes, "default": contextlib.nullcontext, "hip+disc": training.hip_routes_with_discriminator}
+SPECTRAL_ROUTES = {"hip+sn": training.hip_routes_with_spectral}        # measured beside ROUTES
 
 
 def refine(part, kernel):
     """The class of a device event `kernel` launched inside the marked part `part` (None: outside every range)"""
     if any(k in kernel for k in GLUE):
         return "glue kernels"
+    if any(k in kernel for k in SPECTRAL):
+        return "spectral norm"
     if part == "pixelcnn":
         return "masked convolutions" if any(s in kernel for s in LMCONV_NAMES) else "PixelCNN kernels"
     if part == "decoder":
@@ -137,29 +143,31 @@ def main(argv):
         p.requires_grad = False
     trainer = BaseModel(model, opt).to(device)
     mark_parts(trainer)
+    routes = dict(ROUTES, **SPECTRAL_ROUTES)
     for B in args.pairs:
         batch = make_batch(B, device)
         peak = {}
 
         def step(route):
             torch.cuda.reset_peak_memory_stats()      # (every call's peak is its own route's)
-            with ROUTES[route]():
+            with routes[route]():
                 trainer(batch)
             peak[route] = max(peak.get(route, 0), torch.cuda.max_memory_allocated())
-        med = alternate({route: (lambda r=route: step(r)) for route in ROUTES}, args.rounds, args.calls, warm=2)
+        med = alternate({route: (lambda r=route: step(r)) for route in routes}, args.rounds, args.calls, warm=2)
         classes = {}
-        for route in ROUTES:
+        for route in routes:
             totals, rest = by_class(lambda: step(route), args.profile_calls)
             classes[route] = dict(device_ms_per_call=totals, everything_else_top=rest, device_ms_total=round(sum(totals.values()), 3))
         rec = dict(what="train_step", pairs=B, ngf=args.ngf, ndf=args.ndf, unet=args.unet, rounds=args.rounds, calls=args.calls,
                    hip_ms_median_range=span(med["hip"]), default_ms_median_range=span(med["default"]),
-                   hip_disc_ms_median_range=span(med["hip+disc"]),
+                   hip_disc_ms_median_range=span(med["hip+disc"]), hip_sn_ms_median_range=span(med["hip+sn"]),
                    max_memory_allocated_mb={k: round(v / 2 ** 20, 1) for k, v in peak.items()}, classes=classes)
-        print("%d pairs: hip routes %.1f .. %.1f ms, default routes %.1f .. %.1f ms, hip routes with the discriminator's convolutions %.1f .. %.1f ms "
-              "(medians of %d rounds of %d steps); peak memory %s MB"
-              % (B, *span(med["hip"]), *span(med["default"]), *span(med["hip+disc"]), args.rounds, args.calls, rec["max_memory_allocated_mb"]))
+        print("%d pairs: hip routes %.1f .. %.1f ms, default routes %.1f .. %.1f ms, hip routes with the discriminator's convolutions %.1f .. %.1f ms, "
+              "hip routes with the batched spectral norm %.1f .. %.1f ms (medians of %d rounds of %d steps); peak memory %s MB"
+              % (B, *span(med["hip"]), *span(med["default"]), *span(med["hip+disc"]), *span(med["hip+sn"]), args.rounds, args.calls,
+                 rec["max_memory_allocated_mb"]))
         for c in CLASSES:
-            print("  %-28s hip %9.3f ms   default %9.3f ms   hip+disc %9.3f ms" % (c, *(classes[r]["device_ms_per_call"][c] for r in ROUTES)))
+            print("  %-28s " % c + "   ".join("%s %9.3f ms" % (r, classes[r]["device_ms_per_call"][c]) for r in routes))
         print(json.dumps(rec), flush=True)
         del batch
         torch.cuda.empty_cache()
