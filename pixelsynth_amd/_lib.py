@@ -263,6 +263,19 @@ SPECTRAL_TRAIN_PROTOS = {
     "ps_spectral_backward_f32": (RC, [c_void_p] * 9 + [c_size_t, STREAM]),
 }
 
+# libpixelsynth_unet_train.so (include/pixelsynth_unet_train.h): the depth Unet's batch norm + leaky ReLU and its relu -> bilinear x2 of a
+# skip join, forward and backward
+UNET_TRAIN_PROTOS = {
+    "ps_unet_train_last_error": (ctypes.c_char_p, []),
+    "ps_unet_train_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "ps_unet_train_parts": (c_int, [c_int, c_int]),
+    "ps_bn_stats_f32": (RC, [c_void_p, c_int, c_int, c_float, c_float] + [c_void_p] * 7 + [c_size_t, STREAM]),
+    "ps_bn_act_apply_f32": (RC, [c_void_p] * 5 + [c_int, c_int, c_float, c_void_p, c_void_p, STREAM]),
+    "ps_bn_act_backward_f32": (RC, [c_void_p] * 7 + [c_int, c_int, c_float] + [c_void_p] * 4 + [c_size_t, STREAM]),
+    "ps_relu_up2_cat_f32": (RC, [c_void_p, c_void_p] + [c_int] * 5 + [c_void_p, STREAM]),
+    "ps_relu_up2_cat_backward_f32": (RC, [c_void_p, c_void_p] + [c_int] * 6 + [c_void_p, STREAM]),
+}
+
 # libpixelsynth_gan_train.so (include/pixelsynth_gan_train.h): instance norm + LeakyReLU and the feature-matching L1 of the discriminator's
 # training pass.  maps, half_elems, weights and grads are host tables (ctypes arrays)
 GAN_TRAIN_PROTOS = {
@@ -302,7 +315,7 @@ PROTOS = {"hip": _PROTOS, "percsim": PERCSIM_PROTOS, "consistency": CONSISTENCY_
           "vq_train": VQ_TRAIN_PROTOS, "conv_bwd": CONV_BWD_PROTOS, "norm_train": NORM_TRAIN_PROTOS,
           "block_train": BLOCK_TRAIN_PROTOS, "content": CONTENT_PROTOS, "thin_train": THIN_TRAIN_PROTOS,
           "pixelcnn_train": PIXELCNN_TRAIN_PROTOS, "train_glue": TRAIN_GLUE_PROTOS, "spectral_train": SPECTRAL_TRAIN_PROTOS,
-          "disc_conv": DISC_CONV_PROTOS, "gan_train": GAN_TRAIN_PROTOS}
+          "unet_train": UNET_TRAIN_PROTOS, "disc_conv": DISC_CONV_PROTOS, "gan_train": GAN_TRAIN_PROTOS}
 _ENTRIES = {e.name: e for e in _libraries.LIBRARIES}
 assert set(PROTOS) == set(_ENTRIES)
 _OWNER = {fn: _ENTRIES[name] for name, table in PROTOS.items() for fn in table}

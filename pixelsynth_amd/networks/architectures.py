@@ -34,7 +34,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import _lib
-from . import conv_routes, norm_train, spectral_train
+from . import conv_routes, norm_train, spectral_train, unet_train
 from .block_train import decoder_block_train  # noqa: F401
 from .norm_train import decoder_norm_train  # noqa: F401
 from .thin_train import decoder_thin_train  # noqa: F401
@@ -416,6 +416,8 @@ class Unet(nn.Module):
         skips, h = [], _nhwc(self, input)
         if h.is_cuda and spectral_train.active(self):      # (this network keeps no options: the switch's block, or PS_SPECTRAL_TRAIN)
             spectral_train.normalise(spectral_train.sn_modules(self))
+        if unet_train.active(self, h):
+            return self._forward_hip(h)
         for i in range(8):
             h = self._conv(getattr(self, f"conv{i + 1}"), h if i == 0 else F.leaky_relu(h, 0.2))
             if self._ENC_NORM[i]:
@@ -431,6 +433,31 @@ class Unet(nn.Module):
             h = self._conv(getattr(self, f"dconv{i + 1}"), h)
             if self._DEC_NORM[i]:
                 h = torch.cat((getattr(self, self._DEC_NORM[i])(h), skips[6 - i]), 1)
+        return h.contiguous()
+
+    def _forward_hip(self, h):
+        """The loop of forward() under unet_train("hip") (networks/unet_train.py): a norm and the leaky ReLU behind it in one pass, the
+        skip tensor and the tensor beside it never concatenated -- relu and the bilinear x2 read both where they lie --, the wide 3 x 3
+        convolutions through conv_routes._unet_train_conv.  Each piece hands what it does not take to the expression of forward().  What a
+        convolution hands on is made channels-last where it is not (torch's own kernels, with the library's switched off, answer in
+        NCHW): no copy otherwise."""
+        nhwc = lambda t: t.contiguous(memory_format=torch.channels_last)
+        skips, act = [], h
+        for i in range(8):
+            h = nhwc(self._conv(getattr(self, f"conv{i + 1}"), act))
+            if self._ENC_NORM[i]:
+                h, act = unet_train.bn_act_train(h, getattr(self, self._ENC_NORM[i]), 0.2)
+            elif i < 7:
+                act = F.leaky_relu(h, 0.2)
+            skips.append(h)
+        a, b = h, None
+        for i in range(8):
+            h = unet_train.relu_up2_cat(a, b)
+            conv = getattr(self, f"dconv{i + 1}")
+            y = conv_routes._unet_train_conv(conv, h)
+            h = nhwc(self._conv(conv, h)) if y is None else y
+            if self._DEC_NORM[i]:
+                a, b = unet_train.bn_act_train(h, getattr(self, self._DEC_NORM[i])), skips[6 - i]
         return h.contiguous()
 
 

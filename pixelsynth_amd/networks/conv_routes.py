@@ -1,7 +1,8 @@
 """Which kernel a convolution of the refinement decoder gets (the blocks' dataflow is architectures.py's): the weight a module's forward
 would use, taken apart only where that is safe (_plain_conv_weight) and cached per module (routing.cached); the batch cut of what still goes
 through torch (_conv2d_batches); the no-grad routes -- conv1x1 (csrc/conv1x1.hip), _thin_conv (csrc/conv_thin.hip), _f16x3_conv
-(csrc/conv_f16x3.hip through f16x3.py) --; the three training routes behind one gate (_train_route); and the join of a block's branches
+(csrc/conv_f16x3.hip through f16x3.py) --; the three training routes behind one gate (_train_route) and the depth Unet's
+(_unet_train_conv); and the join of a block's branches
 (_resample_sum, csrc/nets.hip).  Every route returns None for what it does not take and the caller goes on to the next; _conv_split ends
 at the module's own forward."""
 import torch
@@ -10,7 +11,7 @@ import torch.nn.functional as F
 from torch.nn.utils.spectral_norm import SpectralNorm
 
 from .. import _lib
-from . import block_train, f16x3, thin_train
+from . import block_train, f16x3, thin_train, unet_train
 from .f16x3 import flag as _overflow_flag  # noqa: F401  (architectures.py hands it on)
 from .routing import cached, empty_nhwc, gpu_f32, has_pending, take_pending
 
@@ -198,6 +199,33 @@ def _thin_train_conv(conv, x, opt=None):
     return _train_route(conv, x, opt, thin_train.decoder_thin_train, "hip", k, k // 2,
                         lambda Ci, Co: takes(Ci, Co, k, x.size(2), x.size(3)),
                         thin_train.conv_thin_in_train if thin_in else thin_train.conv_thin_out_train)
+
+
+def _unet_train_conv(conv, x):
+    """conv(x) WITH its bias for a 3 x 3 convolution of the depth Unet's way up, or None: only in grad mode under unet_train("hip") --
+    that switch alone, not decoder_conv_train or decoder_thin_train -- with the decoder's convolutions on "f16x3" (_conv_mode), for a
+    plain 3 x 3 convolution on a CUDA fp32 input: through f16x3.conv3x3_train where f16x3.train_takes holds (dconv4..6 of Unet(32) at
+    256 x 256), through thin_train.conv_thin_out_train where thin_train.takes_out holds (dconv8).  The weight is the module's own as
+    Unet._conv takes it: a pending spectral_train result, else the hook's.  A weight fp16 cannot hold, or anything else the Functions
+    refuse: torch, on the weight already normalised."""
+    if not (torch.is_grad_enabled() and unet_train.mode() == "hip" and _conv_mode() == "f16x3" and plain_conv(conv, 3, 1)
+            and gpu_f32(x, layout=None)):
+        return None
+    Ci, Co, H, W = conv.in_channels, conv.out_channels, x.size(2), x.size(3)
+    if f16x3.train_takes(Ci, Co, H, W):
+        run = f16x3.conv3x3_train
+    elif thin_train.takes_out(Ci, Co, 3, H, W):
+        run = thin_train.conv_thin_out_train
+    else:
+        return None
+    weight = _plain_conv_weight(conv, x)
+    if weight is None or weight.dtype != torch.float32 or weight.device != x.device:
+        return None
+    x = x.contiguous(memory_format=torch.channels_last)
+    try:
+        return run(x, weight, conv.bias)
+    except ValueError:
+        return F.conv2d(x, weight, conv.bias, 1, 1)
 
 
 # ---- the no-grad 3 x 3 routes ------------------------------------------------------------------------------------------------------------

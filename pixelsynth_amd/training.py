@@ -12,6 +12,7 @@ from .networks.f16x3 import decoder_conv_train
 from .networks.spectral_train import spectral_train
 from .networks.thin_train import decoder_thin_train
 from .networks.train_glue import train_glue
+from .networks.unet_train import unet_train
 
 # every training switch and its HIP value (routing.Switch); the norm's and the discriminator's switches default to "hip" already
 HIP_ROUTES = ((decoder_conv_train, "f16x3"), (decoder_block_train, "hip"), (decoder_thin_train, "hip"), (pixelcnn_train, "hip"),
@@ -45,3 +46,12 @@ def hip_routes_with_spectral(discriminator=False):
     That switch is not one of HIP_ROUTES either (its default is "torch").  -> the inner context's dict with this switch added."""
     with (hip_routes_with_discriminator() if discriminator else hip_routes()) as forced, spectral_train("hip"):
         yield dict(forced, **{spectral_train.name: spectral_train.forced()})
+
+
+@contextlib.contextmanager
+def hip_routes_with_unet(discriminator=False):
+    """hip_routes_with_spectral(discriminator) and, on top, unet_train("hip"): the depth Unet's batch norms, skip joins and wide 3 x 3
+    convolutions through networks/unet_train.py and conv_routes._unet_train_conv.  That switch is not one of HIP_ROUTES either (its
+    default is "torch").  -> the inner context's dict with this switch added."""
+    with hip_routes_with_spectral(discriminator) as forced, unet_train("hip"):
+        yield dict(forced, **{unet_train.name: unet_train.forced()})

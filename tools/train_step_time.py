@@ -8,11 +8,13 @@ PixelCNN as the model builds it, the discriminator on, predict_residual off (so 
 reference's scripts set it, and forward_train then takes the torch blend: docstring there).  A call is one BaseModel step: forward, the
 generator's backward and Adam step, the discriminator's forward, backward and Adam step.
 
-Four routes alternate call by call between device events (_measure.alternate) on the same model and batch: "hip", the step under
+Five routes alternate call by call between device events (_measure.alternate) on the same model and batch: "hip", the step under
 training.hip_routes() (every opt-in training kernel on), "default", every switch where the process has it, "hip+disc", the step
 under training.hip_routes_with_discriminator() (the discriminator's 4 x 4 convolutions through csrc/disc_conv.hip as well), and "hip+sn",
 the step under training.hip_routes_with_spectral() (the spectral normalisation of the decoder's, the Unet's and the discriminator's layers
-as one batched pass per forward, csrc/spectral_train.hip).  After the warm-up calls
+as one batched pass per forward, csrc/spectral_train.hip).  A fifth, "hip+sn+unet", is the step under training.hip_routes_with_unet():
+the depth Unet's norms, skip joins and wide 3 x 3 convolutions on HIP as well (networks/unet_train.py; its kernels stay in the class
+"Unet", by the range around the regressor's forward).  After the warm-up calls
 a round is CALLS calls per route and gives one median per route; the range of the ROUNDS medians is reported, with
 torch.cuda.max_memory_allocated of each route (the largest over its calls, reset before every call).  The yardstick for either number is the other, of the
 same tree in the same process; nothing else is claimed.
@@ -51,6 +53,7 @@ NORM_NAMES = ("norm", "Norm", "k_stats", "k_apply", "welford", "Welford")
 PREFIX = "ps_step::"
 ROUTES = {"hip": training.hip_routes, "default": contextlib.nullcontext, "hip+disc": training.hip_routes_with_discriminator}
 SPECTRAL_ROUTES = {"hip+sn": training.hip_routes_with_spectral}        # measured beside ROUTES
+UNET_ROUTES = {"hip+sn+unet": training.hip_routes_with_unet}           # and beside those
 
 
 def refine(part, kernel):
@@ -143,7 +146,7 @@ def main(argv):
         p.requires_grad = False
     trainer = BaseModel(model, opt).to(device)
     mark_parts(trainer)
-    routes = dict(ROUTES, **SPECTRAL_ROUTES)
+    routes = dict(ROUTES, **SPECTRAL_ROUTES, **UNET_ROUTES)
     for B in args.pairs:
         batch = make_batch(B, device)
         peak = {}
@@ -161,10 +164,12 @@ def main(argv):
         rec = dict(what="train_step", pairs=B, ngf=args.ngf, ndf=args.ndf, unet=args.unet, rounds=args.rounds, calls=args.calls,
                    hip_ms_median_range=span(med["hip"]), default_ms_median_range=span(med["default"]),
                    hip_disc_ms_median_range=span(med["hip+disc"]), hip_sn_ms_median_range=span(med["hip+sn"]),
+                   hip_sn_unet_ms_median_range=span(med["hip+sn+unet"]),
                    max_memory_allocated_mb={k: round(v / 2 ** 20, 1) for k, v in peak.items()}, classes=classes)
         print("%d pairs: hip routes %.1f .. %.1f ms, default routes %.1f .. %.1f ms, hip routes with the discriminator's convolutions %.1f .. %.1f ms, "
-              "hip routes with the batched spectral norm %.1f .. %.1f ms (medians of %d rounds of %d steps); peak memory %s MB"
-              % (B, *span(med["hip"]), *span(med["default"]), *span(med["hip+disc"]), *span(med["hip+sn"]), args.rounds, args.calls,
+              "hip routes with the batched spectral norm %.1f .. %.1f ms, with the Unet's route on top %.1f .. %.1f ms (medians of %d rounds of %d "
+              "steps); peak memory %s MB"
+              % (B, *span(med["hip"]), *span(med["default"]), *span(med["hip+disc"]), *span(med["hip+sn"]), *span(med["hip+sn+unet"]), args.rounds, args.calls,
                  rec["max_memory_allocated_mb"]))
         for c in CLASSES:
             print("  %-28s " % c + "   ".join("%s %9.3f ms" % (r, classes[r]["device_ms_per_call"][c]) for r in routes))
