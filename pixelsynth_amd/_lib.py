@@ -276,6 +276,19 @@ UNET_TRAIN_PROTOS = {
     "ps_relu_up2_cat_backward_f32": (RC, [c_void_p, c_void_p] + [c_int] * 6 + [c_void_p, STREAM]),
 }
 
+# libpixelsynth_vq_conv_train.so (include/pixelsynth_vq_conv_train.h): the passes that make the VQ-VAE's convolutions differentiable (ReLU /
+# space-to-depth pack, gate, fold) and the backward passes of its two 3-channel ends
+VQ_CONV_TRAIN_PROTOS = {
+    "ps_vq_conv_train_last_error": (ctypes.c_char_p, []),
+    "ps_vq_conv_train_parts": (c_int, [ctypes.c_longlong]),
+    "ps_vq_conv_train_workspace_bytes": (c_size_t, [ctypes.c_longlong]),
+    "ps_vq_relu_pack_f32": (RC, [c_void_p] + [c_int] * 6 + [c_void_p, STREAM]),
+    "ps_vq_gate_f32": (RC, [c_void_p] * 4 + [c_size_t, STREAM]),
+    "ps_vq_fold_f32": (RC, [c_void_p] + [c_int] * 3 + [c_void_p, STREAM]),
+    "ps_vq_ends_grad_weight_f32": (RC, [c_void_p, c_void_p] + [c_int] * 4 + [c_void_p] * 3 + [c_size_t, STREAM]),
+    "ps_vq_head_grad_input_f32": (RC, [c_void_p] * 3 + [c_int] * 3 + [c_void_p, STREAM]),
+}
+
 # libpixelsynth_gan_train.so (include/pixelsynth_gan_train.h): instance norm + LeakyReLU and the feature-matching L1 of the discriminator's
 # training pass.  maps, half_elems, weights and grads are host tables (ctypes arrays)
 GAN_TRAIN_PROTOS = {
@@ -315,7 +328,7 @@ PROTOS = {"hip": _PROTOS, "percsim": PERCSIM_PROTOS, "consistency": CONSISTENCY_
           "vq_train": VQ_TRAIN_PROTOS, "conv_bwd": CONV_BWD_PROTOS, "norm_train": NORM_TRAIN_PROTOS,
           "block_train": BLOCK_TRAIN_PROTOS, "content": CONTENT_PROTOS, "thin_train": THIN_TRAIN_PROTOS,
           "pixelcnn_train": PIXELCNN_TRAIN_PROTOS, "train_glue": TRAIN_GLUE_PROTOS, "spectral_train": SPECTRAL_TRAIN_PROTOS,
-          "unet_train": UNET_TRAIN_PROTOS, "disc_conv": DISC_CONV_PROTOS, "gan_train": GAN_TRAIN_PROTOS}
+          "vq_conv_train": VQ_CONV_TRAIN_PROTOS, "unet_train": UNET_TRAIN_PROTOS, "disc_conv": DISC_CONV_PROTOS, "gan_train": GAN_TRAIN_PROTOS}
 _ENTRIES = {e.name: e for e in _libraries.LIBRARIES}
 assert set(PROTOS) == set(_ENTRIES)
 _OWNER = {fn: _ENTRIES[name] for name, table in PROTOS.items() for fn in table}

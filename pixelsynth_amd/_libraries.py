@@ -1,7 +1,7 @@
 """The table of the native libraries: what build.py compiles and _lib.py loads.  No imports beyond os (build.py runs without torch).
 
 libpixelsynth_hip.so ("hip") is the C ABI of include/pixelsynth_hip.h, pinned at version 2; what was added after the pin (PercSim,
-the homography consistency score, the FID network's passes, the batched chained-scene step, the AR plan's orders on the device, the scoring of best-of-N candidates, their ranking per view of a batch, the likelihood of given codes, the backward pass of the locally masked convolution, the backward pass of the splat and of the reprojection, the training half of the VQ-VAE's quantiser, the backward pass of the split-fp16 3 x 3 convolution, the noise-conditioned batch norm in training mode, the 1 x 1 shortcut's weight gradient and the resampling adjoints of a decoder block, the passes between the convolutions of the VGG19 content loss, the backward passes of the decoder's thin first and last layers, the instance norm + LeakyReLU and the feature-matching L1 of the discriminator's training pass, the passes between the masked convolutions of the PixelCNN's training pass and its cross entropy's backward, the depth head and the decoder-input blend of the generator's training step, the discriminator's 4 x 4 convolutions with their backward pass, the spectral normalisation of a network's layers in training, the batch norm + leaky ReLU and the relu -> bilinear x2 of a skip join of the depth Unet in training) lives in a library of its own beside it,
+the homography consistency score, the FID network's passes, the batched chained-scene step, the AR plan's orders on the device, the scoring of best-of-N candidates, their ranking per view of a batch, the likelihood of given codes, the backward pass of the locally masked convolution, the backward pass of the splat and of the reprojection, the training half of the VQ-VAE's quantiser, the backward pass of the split-fp16 3 x 3 convolution, the noise-conditioned batch norm in training mode, the 1 x 1 shortcut's weight gradient and the resampling adjoints of a decoder block, the passes between the convolutions of the VGG19 content loss, the backward passes of the decoder's thin first and last layers, the instance norm + LeakyReLU and the feature-matching L1 of the discriminator's training pass, the passes between the masked convolutions of the PixelCNN's training pass and its cross entropy's backward, the depth head and the decoder-input blend of the generator's training step, the discriminator's 4 x 4 convolutions with their backward pass, the spectral normalisation of a network's layers in training, the batch norm + leaky ReLU and the relu -> bilinear x2 of a skip join of the depth Unet in training, the passes that make the VQ-VAE's convolutions differentiable and the backward passes of its 3-channel ends) lives in a library of its own beside it,
 with its own header and its own last-error function, so that the pinned set of exports never moves.  A further library is one more
 entry here and one prototype table in _lib.py.
 """
@@ -51,6 +51,8 @@ LIBRARIES = (
             "ps_train_glue_last_error"),
     Library("spectral_train", "libpixelsynth_spectral_train.so", [("spectral_train.hip", NO_CONTRACT)], ("pixelsynth_spectral_train.h",),
             "ps_spectral_train_last_error"),
+    Library("vq_conv_train", "libpixelsynth_vq_conv_train.so", [("vq_conv_train.hip", NO_CONTRACT)], ("pixelsynth_vq_conv_train.h",),
+            "ps_vq_conv_train_last_error"),
     Library("unet_train", "libpixelsynth_unet_train.so", [("unet_train.hip", NO_CONTRACT)], ("pixelsynth_unet_train.h",),
             "ps_unet_train_last_error"),
     Library("disc_conv", "libpixelsynth_disc_conv.so", [("disc_conv.hip", NO_CONTRACT)], ("pixelsynth_disc_conv.h",),

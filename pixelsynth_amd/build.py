@@ -4,7 +4,7 @@
 
 One object per translation unit of csrc/, linked into the library the table names for it: libpixelsynth_hip.so and, beside it,
 libpixelsynth_percsim.so, libpixelsynth_consistency.so, libpixelsynth_fid.so, libpixelsynth_scene.so (scene.hip and splat.hip share
-the splat's kernels through the header splat_pipeline.h), libpixelsynth_plan.so, libpixelsynth_rank.so, libpixelsynth_rank_groups.so, libpixelsynth_nll.so, libpixelsynth_lmconv_bwd.so, libpixelsynth_splat_bwd.so, libpixelsynth_vq_train.so, libpixelsynth_conv_bwd.so, libpixelsynth_norm_train.so, libpixelsynth_block_train.so, libpixelsynth_content.so, libpixelsynth_thin_train.so, libpixelsynth_gan_train.so, libpixelsynth_disc_conv.so, libpixelsynth_pixelcnn_train.so, libpixelsynth_train_glue.so, libpixelsynth_spectral_train.so and libpixelsynth_unet_train.so.  The HIP units are built with -ffp-contract=off: the splat family
+the splat's kernels through the header splat_pipeline.h), libpixelsynth_plan.so, libpixelsynth_rank.so, libpixelsynth_rank_groups.so, libpixelsynth_nll.so, libpixelsynth_lmconv_bwd.so, libpixelsynth_splat_bwd.so, libpixelsynth_vq_train.so, libpixelsynth_conv_bwd.so, libpixelsynth_norm_train.so, libpixelsynth_block_train.so, libpixelsynth_content.so, libpixelsynth_thin_train.so, libpixelsynth_gan_train.so, libpixelsynth_disc_conv.so, libpixelsynth_pixelcnn_train.so, libpixelsynth_train_glue.so, libpixelsynth_spectral_train.so, libpixelsynth_unet_train.so and libpixelsynth_vq_conv_train.so.  The HIP units are built with -ffp-contract=off: the splat family
 (splat.hip, zbuffer.hip, scene.hip, splat_bwd.hip, which share splat_math.h) because its index paths must be bit-exact against the
 oracle, the lmconv*.hip units (lmconv_plan.hip, the planning of the whole-grid pass, with them: it shares their headers) so that the post ops inlined into different kernels (whole-grid vs column step) round identically, the
 metric units because their fp32 steps restate the reference's in its order; the matrix products are explicit MFMA intrinsics and are

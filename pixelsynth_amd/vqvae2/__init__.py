@@ -1,1 +1,1 @@
-from .vqvae import VQVAETop, Quantize  # noqa: F401
+from .vqvae import VQVAETop, Quantize, vqvae_train  # noqa: F401

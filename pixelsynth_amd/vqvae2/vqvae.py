@@ -17,8 +17,12 @@ PS_VQVAE_CONV=fp32 (or networks.f16x3.decoder_conv("fp32") in effect) sends ever
 Training: in ``train()`` mode ``Quantize.forward`` is the reference's (:41-74) on csrc/vq_train.hip -- the straight-through output and the
 commitment term, the per-code counts and sums (a product with the one-hot matrix on the fp32 MFMA, built in registers from the int32
 codes), their sum over the ranks, the EMA update of ``cluster_size`` / ``embed_avg`` / ``embed`` in place, and a backward pass that
-keeps the codes and the codebook as it was (never an (N, dim) residual).  The convolutions of ``forward`` run through torch whenever grad
-mode is on or the module trains; vqvae2/train.py has the training step.
+keeps the codes and the codebook as it was (never an (N, dim) residual).  The convolutions of ``forward`` in grad mode: under
+vqvae_train("torch") -- the default; PS_VQVAE_TRAIN -- they run through torch; under vqvae_train("hip") ``forward`` runs enc_b, enc_t,
+quantize_conv_t, dec_t, quantize_conv_b, upsample_t and dec on the Functions of vqvae2/conv_train.py (csrc/vq_conv_train.hip around the
+split-fp16 and fp32 matrix products, forward bit for bit the fast path's) when the call is one the fast path would take: a float32 CUDA
+image, fp32 parameters within fp16's range, VQVAETop's own layers; any other call goes through torch.  ``encode`` / ``decode`` are
+torch's either way.  vqvae2/train.py has the training step.
 
 One reference quirk is part of the numerics: ResBlock starts with an *in-place* ReLU, so the residual it adds is
 relu(x), not x (:93-95).
@@ -31,8 +35,14 @@ from torch.nn import functional as F
 
 from .. import _lib
 from ..networks.f16x3 import checked, conv3x3, forced_mode, pack3x3
+from ..networks.routing import Switch
 
 VQVAE_CONV = os.environ.get("PS_VQVAE_CONV", "f16x3")   # "f16x3" | "fp32" (every convolution through torch / MIOpen)
+
+# with vqvae_train("hip"): ... -- in grad mode VQVAETop.forward inside runs its convolutions on vqvae2/conv_train.py; "torch": through
+# torch autograd.  The process default is VQVAE_TRAIN, read from PS_VQVAE_TRAIN at import and again at every call.
+vqvae_train = Switch("vqvae_train", "PS_VQVAE_TRAIN", ("hip", "torch"), "torch", __name__, "VQVAE_TRAIN")
+VQVAE_TRAIN = vqvae_train.from_env()
 
 
 def _s2d(x):
@@ -455,6 +465,11 @@ class VQVAETop(nn.Module):
         return quant_t, quant_b, diff_t + diff_b, id_t, id_b
 
     def forward(self, input):
+        if vqvae_train.resolve() == "hip":
+            from . import conv_train                      # (it imports this module)
+            scale = conv_train.scale_for(self, input)     # (None: a call the route does not take)
+            if scale is not None:
+                return conv_train.forward_train(self, input, scale)
         quant_t, _, diff, _, _ = self.encode(input)
         return self.decode(quant_t), diff
 
